@@ -9,14 +9,23 @@ sticky-flag check (one host sync, as the reference's forward does 27).  N>1: one
 (torchrun), every rank runs the same per-GPU batch on its own images (weak scaling, images are
 independent: no data-path collective), barrier + max-over-ranks timing.
 
-Prints ONE JSON line. Extra objects:
+Prints ONE JSON line. A plain run sets up, warms up, times `--steps` forwards and prints the headline
+(`value` images/s, `ms_per_step`). `--dump-outputs DIR` writes the three prediction tensors of the last
+timed step as DIR/pred_s{32,16,8}.npy (float32, 60 MB at most in all: a tensor that does not fit
+keeps a fixed, seeded sample of its cells), so that two builds can be compared output for output on
+identical inputs (seeded weights and images).
+
+`--full` adds the secondary legs, each with its own objects in the line:
+  forward_bf16  the same forward in bf16.
+  train         fine-tune steps (fp32, bf16 autocast, HIP graph, Config-3 multi-scale).
+  config5       608x608 fp16 forward + decode + NMS.
   roofline      the conv kernel family (v_mfma_f32_32x32x2_f32 implicit GEMM): algorithmic conv
                 FLOPs of one step / sum of the per-launch durations measured with HIP events on the
                 launch stream, vs the 157.3 TFLOP/s dense f32 matrix peak.
   cpu_baseline  the oracle (CPU restatement of the reference, torch CPU ops) timed on this host on
                 a bounded sample of the same workload (rank 0, N=1 only).
   nms           secondary metric of BASELINE.json: boxes/s of batched NMS at 10,000 post-threshold
-                boxes per image (device path vs the list-based CPU port).
+                boxes per image (device path vs the list-based CPU port); also decode, targets, mAP.
 """
 import argparse
 import json
@@ -72,6 +81,32 @@ def seeded_model(yt, nc, device, seed=0, gain=0.8):
                 mod.running_mean.copy_(0.1 * torch.randn(mod.running_mean.shape, generator=g))
                 mod.running_var.copy_(0.5 + torch.rand(mod.running_var.shape, generator=g))
     return m.to(device).eval()
+
+
+DUMP_BYTES = 60_000_000               # --dump-outputs: all prediction tensors together (the limit is 64 MB)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(outs, size, out_dir):
+    """Write the prediction tensors of one forward as <out_dir>/pred_s<stride>.npy (float32). Smallest first, each
+    tensor may use an equal share of what DUMP_BYTES has left; one that does not fit keeps a fixed, seeded sample of
+    its cells (rows of 5 + classes values, in cell order) as a 2-D array."""
+    os.makedirs(out_dir, exist_ok=True)
+    order = sorted(range(len(outs)), key=lambda j: outs[j].numel())
+    left = DUMP_BYTES
+    for k, i in enumerate(order):
+        o = outs[i]
+        arr = o.detach().float()
+        n_keep = max(1, left // (len(outs) - k) // (arr.shape[-1] * 4))
+        if arr.numel() // arr.shape[-1] > n_keep:
+            cells = arr.reshape(-1, arr.shape[-1])
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED + i)
+            idx = np.sort(rng.choice(cells.shape[0], n_keep, replace=False))
+            arr = cells[torch.from_numpy(idx).to(cells.device)]
+        name = f"pred_s{size // o.shape[2]}"
+        np.save(os.path.join(out_dir, name + ".npy"), arr.cpu().numpy().astype(np.float32))
+        left -= arr.numel() * 4
+        log(f"dumped {name}: {tuple(o.shape)} -> {tuple(arr.shape)}")
 
 
 def conv_flops(plan):
@@ -449,6 +484,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE configs[1]: 32)")
     ap.add_argument("--size", type=int, default=416)
     ap.add_argument("--classes", type=int, default=80)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's predictions as DIR/pred_s<stride>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: bf16 forward, fine-tune steps, config 5, roofline, NMS / decode / targets / mAP, "
+                         "CPU baseline (the --no-* and --per-layer options below apply to these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-nms", action="store_true")
     ap.add_argument("--torch-sgd", action="store_true", help="fine-tune legs: torch.optim.SGD instead of yt.SGD (same update, ~19 launches)")
@@ -467,6 +507,8 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 outside torchrun: print the child command line (JSON) instead of starting it")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 from a plain `python bench.py --gpus N`: start the N ranks OURSELVES, as a child process, before anything in
     # this process touches the GPU (no HIP call, no library load: replacing or forking a GPU-initialised process is not
@@ -500,13 +542,21 @@ def main():
     g = torch.Generator().manual_seed(100 + rank)
     x = torch.rand((args.batch, 3, args.size, args.size), generator=g).to(device)   # resident in HBM before timing
     log(f"model + input ready on {device}")
+    last = []                                   # --dump-outputs: the predictions of the latest step
+
+    def step_keep():
+        last[:] = [model(x)]
+    step = step_keep if args.dump_outputs else (lambda: model(x))
     with torch.no_grad():
-        elapsed = ydist.timed_steps(lambda: model(x), args.steps, args.warmup, dist, device)
+        elapsed = ydist.timed_steps(step, args.steps, args.warmup, dist, device)
     log(f"timed region: {elapsed:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.size, args.dump_outputs)
+    last.clear()
     # ---- the same forward in bf16 (BASELINE configs[3-5] arithmetic; conv3_dma_h16 is its dominant kernel): a secondary
-    # line of the default run, never `value`
+    # line of the --full run, never `value`
     h16, m16, el16 = None, None, 0.0
-    if args.dtype == "fp32" and not args.no_h16:
+    if args.full and args.dtype == "fp32" and not args.no_h16:
         m16 = seeded_model(yt, args.classes, device)
         m16._engine.compute_dtype = "bf16"
         with torch.no_grad():
@@ -522,7 +572,7 @@ def main():
         log(f"bf16 forward leg: {h16['value']} img/s")
     # ---------------------------------------------------------------- fwd+bwd leg (fine-tune step)
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         from tests import golden_inputs as gi           # seeded synthetic targets / turbine anchors (data only)
         tm = seeded_model(yt, args.train_classes, device, seed=1).train()
         if dist is not None:
@@ -630,7 +680,7 @@ def main():
 
     # ---------------------------------------------------------------- config 5 leg (optional)
     cfg5 = None
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         m5 = seeded_model(yt, 80, device, seed=2)
         m5._engine.compute_dtype = "fp16"
         x5 = torch.rand((16, 3, 608, 608), generator=g).to(device)
@@ -670,7 +720,7 @@ def main():
         result["train"] = train
     if cfg5 is not None:
         result["config5"] = cfg5
-    if rank == 0:
+    if rank == 0 and args.full:
         # ------------------------------------------------------------ roofline (dominant kernel)
         result["roofline"] = conv_roofline(model, x, args.dtype, args, elapsed, gflop_img)
         if h16 is not None:
@@ -729,6 +779,7 @@ def main():
                 cb["nms"]["sample"] = "1 image x 10,000 post-threshold boxes per leg, list-based port (oracle/postprocess.py:nms_list, utils.py:150-191), 1 thread"
                 result["nms"]["cpu_port_boxes_per_s"] = cb["nms"]["uniform_80_classes"]["boxes_per_s"]
                 result["nms"]["cpu_port_sample"] = "1 image x 10,000 boxes, list-based port (oracle/postprocess.py:nms_list)"
+    if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(result) + "\n").encode())
     if dist is not None:

@@ -1299,7 +1299,7 @@ def test_bench_runs_over_rccl_with_one_rank(tmp_path):
     env = dict(os.environ, YOLO_FORCE_DIST="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29653", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--size", "160", "--train-steps", "2", "--no-cpu-baseline", "--no-nms", "--no-config5", "--no-config3"],
+                        "--size", "160", "--full", "--train-steps", "2", "--no-cpu-baseline", "--no-nms", "--no-config5", "--no-config3"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
