@@ -215,6 +215,9 @@ int yolo_conv_dgrad_s2(const void* dz, int dz_ld, int dz_off, const void* w_pack
                        void* dx, int dx_ld, int dx_off, int n, int ho, int wo, int cin, int cout, int dtype, void* stream);
 /* upstream gradient in the head layout (B,3,g,g,D) fp32, any strides -> NHWC (B,g,g,ld) in dtype, channel a*D+k, pads 0 */
 int yolo_head_grad_to_nhwc(const float* dp, const int64_t* strides5, void* out, int b, int g, int d, int ld, int dtype, void* stream);
+/* the same for a rectangular grid: (B,3,gh,gw,D) -> NHWC (B,gh,gw,ld); yolo_head_grad_to_nhwc is the gh = gw = g case */
+int yolo_head_grad_to_nhwc_hw(const float* dp, const int64_t* strides5, void* out, int b, int gh, int gw, int d, int ld, int dtype,
+                              void* stream);
 
 /* ---- launch tables for the train-mode forward and the backward (train.py:41-82 run eagerly) -------------------------------- */
 /* The reference's loop issues its step one Python statement at a time; here that is ~900 launches, and issued through an FFI
@@ -227,7 +230,8 @@ int yolo_head_grad_to_nhwc(const float* dp, const int64_t* strides5, void* out, 
 enum { YOLO_FN_FILL_ZERO = 1, YOLO_FN_COPY_D2D, YOLO_FN_NCHW_TO_NHWC, YOLO_FN_STEM_FWD, YOLO_FN_CONV_FWD, YOLO_FN_BN_STATS,
        YOLO_FN_BN_ACT_FWD, YOLO_FN_BN_ACT_BWD, YOLO_FN_UPSAMPLE2X_BWD, YOLO_FN_CONV_WGRAD, YOLO_FN_PACK_WEIGHTS_DGRAD,
        YOLO_FN_PACK_WEIGHTS_BATCH, YOLO_FN_CONV_DGRAD_S2, YOLO_FN_HEAD_GRAD_TO_NHWC, YOLO_FN_CONV_FWD_STATS,
-       YOLO_FN_BN_STATS_FROM_PARTIALS, YOLO_FN_CONV_DGRAD_BSTATS, YOLO_FN_BN_ACT_BWD_ROWS, YOLO_FN_CONV_FWD_WS };
+       YOLO_FN_BN_STATS_FROM_PARTIALS, YOLO_FN_CONV_DGRAD_BSTATS, YOLO_FN_BN_ACT_BWD_ROWS, YOLO_FN_CONV_FWD_WS,
+       YOLO_FN_HEAD_GRAD_TO_NHWC_HW };
 #define YOLO_CALL_MAX_ARGS 24
 typedef struct yolo_call { int32_t fn; int32_t reserved; uint64_t a[YOLO_CALL_MAX_ARGS]; } yolo_call;
 typedef struct yolo_reloc { int32_t call, arg, slot, reserved; int64_t offset; } yolo_reloc;
@@ -246,6 +250,14 @@ int yolo_copy_d2d(void* dst, const void* src, size_t bytes, void* stream);
 /* img: uint8 (h, w, 3) on the device; out: fp32 (3, size, size). new_hw / pad_tl (host pointers, may be NULL) receive the
  * resized size and the top / left padding, which un-letterboxing the boxes needs (utils.py:475-501). */
 int yolo_letterbox(const unsigned char* img_hwc, int h, int w, int size, float* out_chw, int* new_hw, int* pad_tl, void* stream);
+/* Canvas of a batch of n images (hw: host int32 [n][2] original sizes). rect = 0: (size, size). rect != 0: the smallest
+ * multiples of 32 that hold every image resized so that its longer side is size (the resize rule of yolo_letterbox).
+ * canvas_hw (host, out): [2]. */
+int yolo_letterbox_canvas(const int32_t* hw, int n, int size, int rect, int32_t* canvas_hw);
+/* yolo_letterbox onto a (canvas_h, canvas_w) canvas: same resize arithmetic, top / left padding = floor(diff / 2) per axis;
+ * out: fp32 (3, canvas_h, canvas_w). yolo_letterbox is the canvas_h = canvas_w = size case. */
+int yolo_letterbox_hw(const unsigned char* img_hwc, int h, int w, int size, int canvas_h, int canvas_w, float* out_chw, int* new_hw,
+                      int* pad_tl, void* stream);
 
 /* ---- ground-truth tensors (next to the hot path: dataset.py:119-161) ------------------------ */
 /* boxes (B, max_boxes, 5) fp32 [x, y, w, h, class] normalised to [0,1), counts (B) valid boxes per image (list order
@@ -254,6 +266,12 @@ int yolo_letterbox(const unsigned char* img_hwc, int h, int w, int size, float* 
  * here first. Same assignment rule and quirks as the reference loop (see csrc/targets.hip). */
 int yolo_build_targets(const float* boxes, const int32_t* counts, int max_boxes, const float* anchors_9x2, int b, int image_size,
                        float ignore_iou, float* t0, float* t1, float* t2, void* stream);
+/* The same for an (image_h, image_w) canvas (multiples of 32): target k is (B,3,gh_k,gw_k,6), per axis i = int(gh y),
+ * j = int(gw x), rows [gw x - j, gh y - i, w gw, h gh, ...]; anchors are ranked by IoU of (w W/L, h H/L), L = max(H, W),
+ * against the normalised anchors (the square canvas of side L with its padding cropped away). Square input: the same bits
+ * as yolo_build_targets. */
+int yolo_build_targets_hw(const float* boxes, const int32_t* counts, int max_boxes, const float* anchors_9x2, int b, int image_h,
+                          int image_w, float ignore_iou, float* t0, float* t1, float* t2, void* stream);
 
 /* ---- evaluation: average precision per class (utils.py:193-274) ----------------------------- */
 /* rows are [image, x, y, w, h, objectness, class] fp32. dets_sorted: class ascending, objectness descending (stable);
@@ -268,6 +286,9 @@ int yolo_map_match(const float* dets_sorted, const int32_t* det_class_offsets, c
  * on object cells, objectness correct on no-object cells, n_noobj]; pred / target as for yolo_loss_fwd. */
 int yolo_accuracy_counts(const float* pred, const int64_t* strides5, const float* target, int b, int g, int nc, float obj_threshold,
                          unsigned long long* counts5, void* stream);
+/* rectangular grid (B,3,gh,gw,·); yolo_accuracy_counts is the gh = gw = g case */
+int yolo_accuracy_counts_hw(const float* pred, const int64_t* strides5, const float* target, int b, int gh, int gw, int nc,
+                            float obj_threshold, unsigned long long* counts5, void* stream);
 
 /* ---- fused per-scale loss (optional replacement of YOLOLoss.forward, loss.py:29-81) -------- */
 /* pred (B,3,g,g,5+nc) fp32 through element strides; target (B,3,g,g,6) fp32 contiguous
@@ -281,6 +302,12 @@ int yolo_loss_fwd(const float* pred, const int64_t* strides5, const float* targe
 /* dpred (B,3,g,g,5+nc) contiguous = sum_k grad_losses4[k] * d losses4[k] / d pred */
 int yolo_loss_bwd(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int g, int nc,
                   const float* counts2, const float* grad_losses4, float* dpred, void* stream);
+/* rectangular grid (B,3,gh,gw,·); the three functions above are the gh = gw = g case */
+size_t yolo_loss_workspace_bytes_hw(int b, int gh, int gw);
+int yolo_loss_fwd_hw(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                     int nc, float* losses4, float* counts2, void* workspace, size_t workspace_bytes, void* stream);
+int yolo_loss_bwd_hw(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                     int nc, const float* counts2, const float* grad_losses4, float* dpred, void* stream);
 
 /* ---- optimizer step (code/train.py:171-172 torch.optim.SGD(model.parameters(), lr, momentum, weight_decay); :68 step) ---- */
 /* One launch over every parameter tensor; the same bits as torch.optim.SGD's default implementation (each of its passes
@@ -316,6 +343,13 @@ int yolo_decode3(void* const* preds3, const int64_t* strides15, const float* con
  * (utils.py:106-110) - for callers that never look at the predictions again (demo.py:44-55, utils.py:300-321): the kernel's
  * writes drop to the algorithmic 24 bytes per box. yolo_decode takes the same choice as is_pred = 2. */
 int yolo_decode3_ex(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids3, int b, int nc,
+                    int write_back, float* boxes, int n_total, void* stream);
+/* Rectangular grids (B,3,gh,gw,5+nc): rows box_offset + a*gh*gw + row*gw + col, and per axis cx = (1/gw)(sig + col),
+ * cy = (1/gh)(sig + row), w = (1/gw)(e^tw aw), h = (1/gh)(e^th ah) with anchors in grid cells. grids_hw6 = [gh0, gw0, gh1,
+ * gw1, gh2, gw2]. The square functions above are the gh = gw case (same bits). */
+int yolo_decode_hw(void* pred, const int64_t* strides5, const float* anchors_3x2, int b, int gh, int gw, int nc,
+                   int is_pred, float* boxes, int n_total, int box_offset, void* stream);
+int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
                     int write_back, float* boxes, int n_total, void* stream);
 
 /* Replaces non_max_suppression (utils.py:150-191) with calc_iou (utils.py:38-84) inlined,

@@ -95,6 +95,9 @@ int run_one(int fn, const uint64_t* a, void* s) {
     case YOLO_FN_HEAD_GRAD_TO_NHWC:
         return yolo_head_grad_to_nhwc(p_of<const float>(a[0]), p_of<const int64_t>(a[1]), p_of<void>(a[2]), (int)a[3], (int)a[4],
                                       (int)a[5], (int)a[6], (int)a[7], s);
+    case YOLO_FN_HEAD_GRAD_TO_NHWC_HW:
+        return yolo_head_grad_to_nhwc_hw(p_of<const float>(a[0]), p_of<const int64_t>(a[1]), p_of<void>(a[2]), (int)a[3], (int)a[4],
+                                         (int)a[5], (int)a[6], (int)a[7], (int)a[8], s);
     case YOLO_FN_CONV_FWD_STATS:
         return yolo_conv_fwd_stats(p_of<const yolo_conv_desc>(a[0]), p_of<const void>(a[1]), p_of<const void>(a[2]), p_of<void>(a[3]),
                                    p_of<float>(a[4]), (size_t)a[5], s);

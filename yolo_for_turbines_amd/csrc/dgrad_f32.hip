@@ -179,17 +179,17 @@ __global__ void pack_dgrad_frag(const float* __restrict__ w, float* __restrict__
     }
 }
 
-// (B,3,g,g,D) head-layout gradient -> NHWC (B,g,g,ld) with channel a*D+k, pad channels zeroed
+// (B,3,gh,gw,D) head-layout gradient -> NHWC (B,gh,gw,ld) with channel a*D+k, pad channels zeroed
 template <typename T>
 __global__ void head_grad_to_nhwc_kernel(const float* __restrict__ dp, long long sb, long long sa, long long sy, long long sx,
-                                         long long sk, typename Elt<T>::S* __restrict__ out, int B, int g, int D, int ld) {
-    const long long total = (long long)B * g * g * ld;
+                                         long long sk, typename Elt<T>::S* __restrict__ out, int B, int gh, int gw, int D, int ld) {
+    const long long total = (long long)B * gh * gw * ld;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int ch = (int)(i % ld);
         const long long pix = i / ld;
-        const int x = (int)(pix % g);
-        const int y = (int)((pix / g) % g);
-        const int b = (int)(pix / ((long long)g * g));
+        const int x = (int)(pix % gw);
+        const int y = (int)((pix / gw) % gh);
+        const int b = (int)(pix / ((long long)gh * gw));
         float v = 0.f;
         if (ch < 3 * D) {
             const int a = ch / D, k = ch - a * D;
@@ -263,13 +263,19 @@ int yolo_conv_dgrad_s2(const void* dz, int dz_ld, int dz_off, const void* w_pack
 }
 
 int yolo_head_grad_to_nhwc(const float* dp, const int64_t* strides5, void* out, int b, int g, int d, int ld, int dtype, void* stream) {
-    if (!dp || !strides5 || !out || b <= 0 || g <= 0 || d <= 0 || ld < 3 * d) return fail(YOLO_ERR_ARG, "head_grad_to_nhwc: bad arguments");
-    const long long total = (long long)b * g * g * ld;
+    return yolo_head_grad_to_nhwc_hw(dp, strides5, out, b, g, g, d, ld, dtype, stream);
+}
+
+int yolo_head_grad_to_nhwc_hw(const float* dp, const int64_t* strides5, void* out, int b, int gh, int gw, int d, int ld, int dtype,
+                              void* stream) {
+    if (!dp || !strides5 || !out || b <= 0 || gh <= 0 || gw <= 0 || d <= 0 || ld < 3 * d)
+        return fail(YOLO_ERR_ARG, "head_grad_to_nhwc: bad arguments");
+    const long long total = (long long)b * gh * gw * ld;
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     YOLO_DISPATCH_DTYPE(dtype, "head_grad_to_nhwc",
         hipLaunchKernelGGL(head_grad_to_nhwc_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dp, (long long)strides5[0],
                            (long long)strides5[1], (long long)strides5[2], (long long)strides5[3], (long long)strides5[4], (Elt<T>::S*)out,
-                           b, g, d, ld));
+                           b, gh, gw, d, ld));
     return check_launch("head_grad_to_nhwc");
 }
 

@@ -17,11 +17,11 @@
 namespace yolo {
 
 struct LossArgs {
-    const float* pred;          // (B,3,g,g,5+nc) through element strides
-    const float* tgt;           // (B,3,g,g,6) contiguous
+    const float* pred;          // (B,3,gh,gw,5+nc) through element strides
+    const float* tgt;           // (B,3,gh,gw,6) contiguous
     const float* anchors;       // (3,2) in grid units
     long long sb, sa, sy, sx, sk;
-    int B, g, nc;
+    int B, gh, gw, nc;
     long long cells;
 };
 
@@ -39,10 +39,10 @@ __device__ __forceinline__ float iou_center(float ax, float ay, float aw, float 
 }
 
 __device__ __forceinline__ const float* cell_ptr(const LossArgs& p, long long cell, int* a_out) {
-    const int x = (int)(cell % p.g);
-    const long long r1 = cell / p.g;
-    const int y = (int)(r1 % p.g);
-    const long long r2 = r1 / p.g;
+    const int x = (int)(cell % p.gw);
+    const long long r1 = cell / p.gw;
+    const int y = (int)(r1 % p.gh);
+    const long long r2 = r1 / p.gh;
     const int a = (int)(r2 % 3);
     const long long b = r2 / 3;
     *a_out = a;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64) void loss_finalize(const double* __restrict__ p
     counts2[1] = (float)n_noobj;
 }
 
-// dpred (B,3,g,g,5+nc) contiguous = sum_k gout[k] * d loss_k / d pred
+// dpred (B,3,gh,gw,5+nc) contiguous = sum_k gout[k] * d loss_k / d pred
 __global__ __launch_bounds__(256) void loss_grad(const LossArgs p, const float* __restrict__ counts2, const float* __restrict__ gout4,
                                                  float* __restrict__ dpred) {
     const float n_obj = counts2[0], n_noobj = counts2[1];
@@ -177,25 +177,34 @@ using namespace yolo;
 
 extern "C" {
 
-size_t yolo_loss_workspace_bytes(int b, int g) {
-    if (b <= 0 || g <= 0) return 0;
-    return (size_t)loss_blocks((long long)b * 3 * g * g) * 6 * sizeof(double);
+size_t yolo_loss_workspace_bytes(int b, int g) { return yolo_loss_workspace_bytes_hw(b, g, g); }
+
+size_t yolo_loss_workspace_bytes_hw(int b, int gh, int gw) {
+    if (b <= 0 || gh <= 0 || gw <= 0) return 0;
+    return (size_t)loss_blocks((long long)b * 3 * gh * gw) * 6 * sizeof(double);
 }
 
-static int fill_loss_args(LossArgs* a, const float* pred, const int64_t* s5, const float* target, const float* anchors, int b, int g, int nc) {
-    if (!pred || !s5 || !target || !anchors || b <= 0 || g <= 0 || nc <= 0) return fail(YOLO_ERR_ARG, "loss: bad arguments");
+static int fill_loss_args(LossArgs* a, const float* pred, const int64_t* s5, const float* target, const float* anchors, int b, int gh,
+                          int gw, int nc) {
+    if (!pred || !s5 || !target || !anchors || b <= 0 || gh <= 0 || gw <= 0 || nc <= 0) return fail(YOLO_ERR_ARG, "loss: bad arguments");
     a->pred = pred; a->tgt = target; a->anchors = anchors;
     a->sb = s5[0]; a->sa = s5[1]; a->sy = s5[2]; a->sx = s5[3]; a->sk = s5[4];
-    a->B = b; a->g = g; a->nc = nc; a->cells = (long long)b * 3 * g * g;
+    a->B = b; a->gh = gh; a->gw = gw; a->nc = nc; a->cells = (long long)b * 3 * gh * gw;
     return YOLO_OK;
 }
 
 int yolo_loss_fwd(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int g, int nc,
                   float* losses4, float* counts2, void* workspace, size_t workspace_bytes, void* stream) {
+    return yolo_loss_fwd_hw(pred, strides5, target, anchors_3x2, b, g, g, nc, losses4, counts2, workspace, workspace_bytes, stream);
+}
+
+int yolo_loss_fwd_hw(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                     int nc, float* losses4, float* counts2, void* workspace, size_t workspace_bytes, void* stream) {
     LossArgs a;
-    int rc = fill_loss_args(&a, pred, strides5, target, anchors_3x2, b, g, nc);
+    int rc = fill_loss_args(&a, pred, strides5, target, anchors_3x2, b, gh, gw, nc);
     if (rc) return rc;
-    if (!losses4 || !counts2 || !workspace || workspace_bytes < yolo_loss_workspace_bytes(b, g)) return fail(YOLO_ERR_WORKSPACE, "loss: workspace");
+    if (!losses4 || !counts2 || !workspace || workspace_bytes < yolo_loss_workspace_bytes_hw(b, gh, gw))
+        return fail(YOLO_ERR_WORKSPACE, "loss: workspace");
     const int nblk = loss_blocks(a.cells);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(loss_partial, dim3(nblk), dim3(256), 0, s, a, (double*)workspace);
@@ -207,8 +216,13 @@ int yolo_loss_fwd(const float* pred, const int64_t* strides5, const float* targe
 
 int yolo_loss_bwd(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int g, int nc,
                   const float* counts2, const float* grad_losses4, float* dpred, void* stream) {
+    return yolo_loss_bwd_hw(pred, strides5, target, anchors_3x2, b, g, g, nc, counts2, grad_losses4, dpred, stream);
+}
+
+int yolo_loss_bwd_hw(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                     int nc, const float* counts2, const float* grad_losses4, float* dpred, void* stream) {
     LossArgs a;
-    int rc = fill_loss_args(&a, pred, strides5, target, anchors_3x2, b, g, nc);
+    int rc = fill_loss_args(&a, pred, strides5, target, anchors_3x2, b, gh, gw, nc);
     if (rc) return rc;
     if (!counts2 || !grad_losses4 || !dpred) return fail(YOLO_ERR_ARG, "loss_bwd: null pointer");
     hipLaunchKernelGGL(loss_grad, dim3(loss_blocks(a.cells)), dim3(256), 0, (hipStream_t)stream, a, counts2, grad_losses4, dpred);

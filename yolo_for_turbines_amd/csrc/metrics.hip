@@ -129,16 +129,16 @@ __global__ __launch_bounds__(256) void map_ap_kernel(const float* __restrict__ t
 // check_model_accuracy (utils.py:334-381) for one scale of one batch: five integer counters, accumulated with integer
 // atomics (order-independent, so still deterministic): [class correct, n_obj, obj correct, noobj correct, n_noobj].
 __global__ __launch_bounds__(256) void accuracy_kernel(const float* __restrict__ pred, long long sb, long long sa, long long sy, long long sx,
-                                                       long long sk, const float* __restrict__ tgt, long long cells, int g, int nc,
-                                                       float thr, unsigned long long* __restrict__ counts) {
+                                                       long long sk, const float* __restrict__ tgt, long long cells, int gh, int gw,
+                                                       int nc, float thr, unsigned long long* __restrict__ counts) {
     unsigned c_cls = 0, c_nobj = 0, c_obj = 0, c_noobj = 0, c_nnoobj = 0;
     for (long long cell = blockIdx.x * 256LL + threadIdx.x; cell < cells; cell += (long long)gridDim.x * 256) {
         const float t4 = tgt[cell * 6 + 4];
         if (t4 != 1.f && t4 != 0.f) continue;
-        const int x = (int)(cell % g);
-        const long long r1 = cell / g;
-        const int y = (int)(r1 % g);
-        const long long r2 = r1 / g;
+        const int x = (int)(cell % gw);
+        const long long r1 = cell / gw;
+        const int y = (int)(r1 % gh);
+        const long long r2 = r1 / gh;
         const float* q = pred + (r2 / 3) * sb + (r2 % 3) * sa + y * sy + x * sx;
         const bool obj_pred = 1.f / (1.f + expf(-q[4 * sk])) > thr;
         if (t4 == 1.f) {
@@ -190,12 +190,18 @@ int yolo_map_match(const float* dets_sorted, const int32_t* det_class_offsets, c
 
 int yolo_accuracy_counts(const float* pred, const int64_t* strides5, const float* target, int b, int g, int nc, float obj_threshold,
                          unsigned long long* counts5, void* stream) {
-    if (!pred || !strides5 || !target || !counts5 || b <= 0 || g <= 0 || nc <= 0) return fail(YOLO_ERR_ARG, "accuracy: bad arguments");
-    const long long cells = (long long)b * 3 * g * g;
+    return yolo_accuracy_counts_hw(pred, strides5, target, b, g, g, nc, obj_threshold, counts5, stream);
+}
+
+int yolo_accuracy_counts_hw(const float* pred, const int64_t* strides5, const float* target, int b, int gh, int gw, int nc,
+                            float obj_threshold, unsigned long long* counts5, void* stream) {
+    if (!pred || !strides5 || !target || !counts5 || b <= 0 || gh <= 0 || gw <= 0 || nc <= 0)
+        return fail(YOLO_ERR_ARG, "accuracy: bad arguments");
+    const long long cells = (long long)b * 3 * gh * gw;
     long long nb = (cells + 255) / 256;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(accuracy_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, pred, (long long)strides5[0],
-                       (long long)strides5[1], (long long)strides5[2], (long long)strides5[3], (long long)strides5[4], target, cells, g, nc,
+                       (long long)strides5[1], (long long)strides5[2], (long long)strides5[3], (long long)strides5[4], target, cells, gh, gw, nc,
                        obj_threshold, counts5);
     return check_launch("accuracy");
 }

@@ -40,19 +40,19 @@ __device__ __forceinline__ int pp_fdiv(int x, unsigned m, int d) {
     return (int)(q * (unsigned)d > (unsigned)x ? q - 1 : q);
 }
 static unsigned pp_magic(long long d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + (unsigned long long)d - 1) / (unsigned long long)d); }
-static DecodeMagic decode_magic(int g) { return DecodeMagic{pp_magic(g), pp_magic((long long)g * g), pp_magic(3LL * g * g)}; }
+static DecodeMagic decode_magic(int gh, int gw) { return DecodeMagic{pp_magic(gw), pp_magic((long long)gh * gw), pp_magic(3LL * gh * gw)}; }
 
 // one cell's box from its (5 + nc) values at src (LDS tile or global memory): called by the four lanes q of the cell together
 __device__ __forceinline__ void decode_cell(float* __restrict__ pred, long long sb, long long sa, long long sy, long long sx, long long sk,
-                                            const float* __restrict__ anchors, int g, int nc, int is_pred, float* __restrict__ boxes,
+                                            const float* __restrict__ anchors, int gh, int gw, int nc, int is_pred, float* __restrict__ boxes,
                                             int n_total, int box_offset, long long cell, const float* src, long long kstride, bool staged, int q,
                                             const DecodeMagic mg) {
     // cell -> (b, a, row, col) by multiply-high (cells < 2^31, checked on the host): as four 64-bit divisions per lane this index
     // arithmetic was most of the kernel's issue time (~4.6 us per 64-cell tile)
-    const int c32 = (int)cell, gg = g * g;
+    const int c32 = (int)cell, gg = gh * gw;
     const int b = pp_fdiv(c32, mg.m3gg, 3 * gg), r1 = c32 - b * 3 * gg;
     const int a = pp_fdiv(r1, mg.mgg, gg), r2 = r1 - a * gg;
-    const int row = pp_fdiv(r2, mg.mg, g), col = r2 - row * g;
+    const int row = pp_fdiv(r2, mg.mg, gw), col = r2 - row * gw;
     float* gp = pred + b * sb + a * sa + row * sy + col * sx;
     if (!staged) src = gp;
     float cls;
@@ -86,8 +86,9 @@ __device__ __forceinline__ void decode_cell(float* __restrict__ pred, long long 
     } else {
         cls = 0.f;
     }
-    const float inv = (float)(1.0 / (double)g);          // `1 / grid_size` is a Python float, cast to fp32 by the multiply
-    float* o = boxes + ((size_t)b * n_total + box_offset + (size_t)a * g * g + (size_t)row * g + col) * 6;
+    // `1 / grid_size` is a Python float, cast to fp32 by the multiply; per axis: x and w by 1/gw, y and h by 1/gh
+    const float inv_w = (float)(1.0 / (double)gw), inv_h = (float)(1.0 / (double)gh);
+    float* o = boxes + ((size_t)b * n_total + box_offset + (size_t)a * gg + (size_t)row * gw + col) * 6;
     if (is_pred) {
         // The four box values of a cell go to its four lanes (x, y: sigmoid; w, h: exp * anchor): the kernel is bound by VALU
         // issue (an expf is ~50 instructions for the whole wave however few lanes are active), and with lane 0 doing all five
@@ -100,16 +101,16 @@ __device__ __forceinline__ void decode_cell(float* __restrict__ pred, long long 
         // are a partial-line write per cell, 1.7x the algorithmic 24 bytes per box of this kernel's writes
         if (is_pred == 1) gp[q * sk] = v;
         const float add = q == 0 ? (float)col : (float)row;
-        o[q] = inv * (q < 2 ? v + add : v);
+        o[q] = ((q & 1) ? inv_h : inv_w) * (q < 2 ? v + add : v);
         if (q == 0) {
             o[4] = sigmoid_f(src[4 * kstride]);
             o[5] = cls;
         }
     } else if (q == 0) {
-        o[0] = inv * (src[0] + (float)col);
-        o[1] = inv * (src[kstride] + (float)row);
-        o[2] = inv * src[2 * kstride];
-        o[3] = inv * src[3 * kstride];
+        o[0] = inv_w * (src[0] + (float)col);
+        o[1] = inv_h * (src[kstride] + (float)row);
+        o[2] = inv_w * src[2 * kstride];
+        o[3] = inv_h * src[3 * kstride];
         o[4] = src[4 * kstride];
         o[5] = src[5 * kstride];
     }
@@ -122,16 +123,16 @@ __device__ __forceinline__ void decode_cell(float* __restrict__ pred, long long 
 // the maximum). Lane 0 of the cell finishes it. (One lane per cell and 64-thread blocks left 6-7 waves per CU, each
 // waiting on its own loads and then on 80 dependent LDS reads: 2.5 TB/s.)
 __device__ __forceinline__ void decode_block(float* __restrict__ pred, long long sb, long long sa, long long sy, long long sx, long long sk,
-                                             const float* __restrict__ anchors, int B, int g, int nc, int is_pred,
+                                             const float* __restrict__ anchors, int B, int gh, int gw, int nc, int is_pred,
                                              float* __restrict__ boxes, int n_total, int box_offset, long long blk, const DecodeMagic mg) {
     extern __shared__ __attribute__((aligned(16))) float tile[];           // [64][D] when sk == 1 && cells contiguous, else unused
     const int D = 5 + nc;
     const int q = threadIdx.x & 3, cl = threadIdx.x >> 2;
-    const long long cells = (long long)B * 3 * g * g;
+    const long long cells = (long long)B * 3 * gh * gw;
     const long long cell0 = blk * 64;
     const long long cell = cell0 + cl;
-    const bool contiguous = (sk == 1 && sx == D && sy == (long long)g * D && sa == (long long)g * g * D &&
-                             sb == 3LL * g * g * D);
+    const bool contiguous = (sk == 1 && sx == D && sy == (long long)gw * D && sa == (long long)gh * gw * D &&
+                             sb == 3LL * gh * gw * D);
     const float* src;
     long long kstride;
     if (contiguous) {
@@ -161,24 +162,24 @@ __device__ __forceinline__ void decode_block(float* __restrict__ pred, long long
         kstride = sk;
     }
     if (cell >= cells) return;                                               // the four lanes of a cell leave together
-    decode_cell(pred, sb, sa, sy, sx, sk, anchors, g, nc, is_pred, boxes, n_total, box_offset, cell, src, kstride, contiguous, q, mg);
+    decode_cell(pred, sb, sa, sy, sx, sk, anchors, gh, gw, nc, is_pred, boxes, n_total, box_offset, cell, src, kstride, contiguous, q, mg);
 }
 
 __global__ void decode_kernel(float* __restrict__ pred, long long sb, long long sa, long long sy, long long sx, long long sk,
-                              const float* __restrict__ anchors, int B, int g, int nc, int is_pred,
+                              const float* __restrict__ anchors, int B, int gh, int gw, int nc, int is_pred,
                               float* __restrict__ boxes, int n_total, int box_offset, const DecodeMagic mg) {
-    decode_block(pred, sb, sa, sy, sx, sk, anchors, B, g, nc, is_pred, boxes, n_total, box_offset, blockIdx.x, mg);
+    decode_block(pred, sb, sa, sy, sx, sk, anchors, B, gh, gw, nc, is_pred, boxes, n_total, box_offset, blockIdx.x, mg);
 }
 
 // the three scales of one forward in ONE launch (demo.py:44-51 / utils.py:300-309 order): at batch 32 the three separate
 // launches were launch-latency-bound (3 x ~25 us for 129 MB)
-struct DecodeScale { float* pred; long long sb, sa, sy, sx, sk; const float* anchors; int g, box_offset; long long first_block; DecodeMagic mg; };
+struct DecodeScale { float* pred; long long sb, sa, sy, sx, sk; const float* anchors; int gh, gw, box_offset; long long first_block; DecodeMagic mg; };
 struct Decode3Args { DecodeScale sc[3]; int B, nc, n_total, is_pred; float* boxes; };
 
 __global__ void decode3_kernel(const Decode3Args a) {
     const int k = (long long)blockIdx.x >= a.sc[2].first_block ? 2 : ((long long)blockIdx.x >= a.sc[1].first_block ? 1 : 0);
     const DecodeScale& d = a.sc[k];
-    decode_block(d.pred, d.sb, d.sa, d.sy, d.sx, d.sk, d.anchors, a.B, d.g, a.nc, a.is_pred, a.boxes, a.n_total, d.box_offset,
+    decode_block(d.pred, d.sb, d.sa, d.sy, d.sx, d.sk, d.anchors, a.B, d.gh, d.gw, a.nc, a.is_pred, a.boxes, a.n_total, d.box_offset,
                  (long long)blockIdx.x - d.first_block, d.mg);
 }
 
@@ -1421,18 +1422,23 @@ extern "C" {
 
 int yolo_decode(void* pred, const int64_t* s, const float* anchors, int b, int g, int nc, int is_pred, float* boxes,
                 int n_total, int box_offset, void* stream) {
-    if (!pred || !s || !boxes || b <= 0 || g <= 0 || nc < 1) return fail(YOLO_ERR_ARG, "decode: bad arguments");
+    return yolo_decode_hw(pred, s, anchors, b, g, g, nc, is_pred, boxes, n_total, box_offset, stream);
+}
+
+int yolo_decode_hw(void* pred, const int64_t* s, const float* anchors, int b, int gh, int gw, int nc, int is_pred, float* boxes,
+                   int n_total, int box_offset, void* stream) {
+    if (!pred || !s || !boxes || b <= 0 || gh <= 0 || gw <= 0 || nc < 1) return fail(YOLO_ERR_ARG, "decode: bad arguments");
     if (is_pred && !anchors) return fail(YOLO_ERR_ARG, "decode: anchors required");
     if (!is_pred && nc != 1) return fail(YOLO_ERR_ARG, "decode: targets must have last dim 6");
-    if (box_offset < 0 || box_offset + 3 * g * g > n_total) return fail(YOLO_ERR_ARG, "decode: box range outside n_total");
-    const long long cells = (long long)b * 3 * g * g;
+    if (box_offset < 0 || (long long)box_offset + 3LL * gh * gw > n_total) return fail(YOLO_ERR_ARG, "decode: box range outside n_total");
+    const long long cells = (long long)b * 3 * gh * gw;
     if (cells > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "decode: too many cells");
     const int D = 5 + nc;
     const size_t lds = (size_t)64 * D * sizeof(float);
     if (lds > 64 * 1024) return fail(YOLO_ERR_UNSUPPORTED, "decode: %d classes exceed the staging tile", nc);
     hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((cells + 63) / 64)), dim3(256), lds, (hipStream_t)stream, (float*)pred,
-                       (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], anchors, b, g, nc,
-                       is_pred, boxes, n_total, box_offset, decode_magic(g));
+                       (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], anchors, b, gh, gw, nc,
+                       is_pred, boxes, n_total, box_offset, decode_magic(gh, gw));
     return check_launch("decode");
 }
 
@@ -1443,22 +1449,30 @@ int yolo_decode3(void* const* preds3, const int64_t* strides15, const float* con
 
 int yolo_decode3_ex(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids3, int b, int nc,
                     int write_back, float* boxes, int n_total, void* stream) {
-    if (!preds3 || !strides15 || !anchors3 || !grids3 || !boxes || b <= 0 || nc < 1) return fail(YOLO_ERR_ARG, "decode3: bad arguments");
+    if (!grids3) return fail(YOLO_ERR_ARG, "decode3: bad arguments");
+    const int hw6[6] = {grids3[0], grids3[0], grids3[1], grids3[1], grids3[2], grids3[2]};
+    return yolo_decode3_hw(preds3, strides15, anchors3, hw6, b, nc, write_back, boxes, n_total, stream);
+}
+
+int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
+                    int write_back, float* boxes, int n_total, void* stream) {
+    if (!preds3 || !strides15 || !anchors3 || !grids_hw6 || !boxes || b <= 0 || nc < 1) return fail(YOLO_ERR_ARG, "decode3: bad arguments");
     Decode3Args a;
     a.B = b; a.nc = nc; a.n_total = n_total; a.boxes = boxes; a.is_pred = write_back ? 1 : 2;
     long long blocks = 0;
-    int off = 0;
+    long long off = 0;
     for (int k = 0; k < 3; ++k) {
-        const int g = grids3[k];
-        if (!preds3[k] || !anchors3[k] || g <= 0) return fail(YOLO_ERR_ARG, "decode3: bad scale %d", k);
+        const int gh = grids_hw6[2 * k], gw = grids_hw6[2 * k + 1];
+        if (!preds3[k] || !anchors3[k] || gh <= 0 || gw <= 0) return fail(YOLO_ERR_ARG, "decode3: bad scale %d", k);
+        if ((long long)b * 3 * gh * gw > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "decode3: too many cells");
         DecodeScale& d = a.sc[k];
-        d.pred = (float*)preds3[k]; d.anchors = anchors3[k]; d.g = g; d.box_offset = off; d.first_block = blocks; d.mg = decode_magic(g);
-        if ((long long)b * 3 * g * g > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "decode3: too many cells");
+        d.pred = (float*)preds3[k]; d.anchors = anchors3[k]; d.gh = gh; d.gw = gw; d.box_offset = (int)off; d.first_block = blocks;
+        d.mg = decode_magic(gh, gw);
         d.sb = strides15[5 * k]; d.sa = strides15[5 * k + 1]; d.sy = strides15[5 * k + 2]; d.sx = strides15[5 * k + 3]; d.sk = strides15[5 * k + 4];
-        off += 3 * g * g;
-        blocks += ((long long)b * 3 * g * g + 63) / 64;
+        off += 3LL * gh * gw;
+        blocks += ((long long)b * 3 * gh * gw + 63) / 64;
     }
-    if (off != n_total) return fail(YOLO_ERR_ARG, "decode3: n_total %d != sum of 3 g^2 = %d", n_total, off);
+    if (off != n_total) return fail(YOLO_ERR_ARG, "decode3: n_total %d != sum of 3 gh gw = %lld", n_total, off);
     if (blocks > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "decode3: too many cells");
     const size_t lds = (size_t)64 * (5 + nc) * sizeof(float);
     if (lds > 64 * 1024) return fail(YOLO_ERR_UNSUPPORTED, "decode: %d classes exceed the staging tile", nc);

@@ -9,7 +9,7 @@ Data layout in HBM (fp32 path)
     of nn.Upsample writes slice [0, Cu) with a 2x-upsampling store — no copy kernels;
   * weights: packed [Cout_pad][K_pad] (K = (kh,kw,ci)) + folded BatchNorm scale/shift, cached per
     block and refreshed when the parameter tensors change;
-  * head outputs: (B,3,g,g,5+nc) contiguous, freshly allocated per call (callers mutate them).
+  * head outputs: (B,3,H/s,W/s,5+nc) contiguous, freshly allocated per call (callers mutate them).
 """
 from __future__ import annotations
 
@@ -123,8 +123,10 @@ class Program:
         self.n_pred += 1
 
 
-def build_network_program(model, B, S, ch_align=4):
-    """Walk ``model.layers`` the way the reference forward does (model.py:172-193)."""
+def build_network_program(model, B, H, ch_align=4, W=None):
+    """Walk ``model.layers`` the way the reference forward does (model.py:172-193) for a (B, C, H, W) input; ``W`` defaults
+    to ``H`` (square input)."""
+    W = H if W is None else W
     from .model import CNNBlock, ResidualBlock, ScalePredictionBlock
     layers = list(model.layers)
     # pre-pass: pair each route (8-unit residual stage) with the nn.Upsample that pops it (LIFO)
@@ -142,7 +144,7 @@ def build_network_program(model, B, S, ch_align=4):
             c = c + cr
     prog = Program(B)
     cin_pad = (model.in_channels + ch_align - 1) // ch_align * ch_align
-    cur = TView(prog.new_buf(S, S, cin_pad), model.in_channels, S, S, cin_pad, 0)
+    cur = TView(prog.new_buf(H, W, cin_pad), model.in_channels, H, W, cin_pad, 0)
     prog.input = cur
     concat_view = {}                                  # upsample layer index -> TView of the whole concat
     for i, m in enumerate(layers):
@@ -549,7 +551,7 @@ class ModelState:
     # ------------------------------------------------------------------ inference forward
     def forward(self, model, x):
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
-            raise ValueError("expected a (B,C,S,S) tensor")
+            raise ValueError("expected a (B,C,H,W) tensor")
         if not x.is_cuda:
             raise RuntimeError("yolo_for_turbines_amd runs on MI355X only: move the model and the input to the GPU "
                                "(there is no CPU fallback)")
@@ -560,18 +562,18 @@ class ModelState:
             from . import train_engine
             return train_engine.forward_train(self, model, x)
         B, Cc, H, W = x.shape
-        if Cc != model.in_channels or H != W or H % 32:
-            raise ValueError(f"input must be (B,{model.in_channels},S,S) with S a multiple of 32, got {tuple(x.shape)}")
+        if Cc != model.in_channels or H % 32 or W % 32 or H <= 0 or W <= 0:
+            raise ValueError(f"input must be (B,{model.in_channels},H,W) with H and W multiples of 32, got {tuple(x.shape)}")
         if model.training:
             raise NotImplementedError("train-mode forward without autograd (batch statistics) is not supported; "
                                       "call model.eval() for inference")
         with torch.cuda.device(x.device):
             stream = L.current_stream()
             dt = resolve_dtype(self.compute_dtype)
-            key = ("eval", B, H, x.device.index, self.tile_override, dt)
+            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt)
             plan = self._plans.get(key)
             if plan is None:
-                prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4)
+                prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4, W=W)
                 plan = Plan(prog, self, x.device, self.tile_override, dtype=dt)
                 if dt != "fp32" and plan.stem is None:
                     raise NotImplementedError("the 16-bit path needs the 3->32 stem block as the first layer")
@@ -591,8 +593,9 @@ class ModelState:
                 plan.load_input(xin, stream)
             preds = []
             for k in range(plan.prog.n_pred):
-                i, g, c3 = plan.pred_ops[k]
-                out = torch.empty((B, 3, g, g, c3), dtype=torch.float32, device=x.device)
+                i, gh, c3 = plan.pred_ops[k]
+                gw = plan.prog.ops[i]["Wo"]
+                out = torch.empty((B, 3, gh, gw, c3), dtype=torch.float32, device=x.device)
                 plan.table[i].y = out.data_ptr()
                 preds.append(out)
             plan.launch(stream)
@@ -721,8 +724,9 @@ def _run_module_plan(st, module, x, prog, cur, out, stream, dt="fp32"):
     plan.load_input(xin, stream)
     result = None
     if out is None:
-        i, g, c3 = plan.pred_ops[0]
-        result = torch.empty((B, 3, g, g, c3), dtype=torch.float32, device=x.device)
+        i, gh, c3 = plan.pred_ops[0]
+        gw = plan.prog.ops[i]["Wo"]
+        result = torch.empty((B, 3, gh, gw, c3), dtype=torch.float32, device=x.device)
         plan.table[i].y = result.data_ptr()
     plan.launch(stream)
     if out is not None:

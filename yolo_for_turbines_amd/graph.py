@@ -19,7 +19,7 @@ from .loss import FusedYOLOLoss
 class GraphedTrainStep:
     """``step = GraphedTrainStep(model, optimizer, scaled_anchors, x, targets)`` then ``loss = step(x, targets)``.
 
-    ``x``: (B,3,S,S) batch, ``targets``: the three (B,3,g,g,6) tensors of the loader, ``scaled_anchors``: (3,3,2) anchors
+    ``x``: (B,3,H,W) batch, ``targets``: the three (B,3,gh,gw,6) tensors of the loader, ``scaled_anchors``: (3,3,2) anchors
     in grid units (`train.py:195-197`). The example batch passed to the constructor fixes the shapes and is used for
     the warm-up steps on a side stream (so they DO update the model, like three ordinary steps). ``autocast_dtype``
     (``torch.bfloat16`` / ``torch.float16`` / None) selects what `train.py:53` selects. Returns the summed loss as a
@@ -56,7 +56,7 @@ class GraphedTrainStep:
             # The graph bakes in raw pointers to the train plan's buffers (activations, statistics, workspaces, packed
             # gradient weights). Own the plan: a strong reference keeps its memory alive, `pinned` exempts it from the
             # model's LRU of plans (multi-scale training builds other sizes in between replays).
-            plans = [pl for k, pl in model._engine._plans.items() if k[0] == "train" and k[1] == x.shape[0] and k[2] == x.shape[2]]
+            plans = [pl for k, pl in model._engine._plans.items() if k[0] == "train" and k[1] == x.shape[0] and k[2] == tuple(x.shape[2:4])]
             if not plans:
                 raise RuntimeError("GraphedTrainStep: the warm-up steps left no train plan for this shape")
             self._plan = plans[-1]

@@ -45,15 +45,15 @@ class _FusedLossFn(torch.autograd.Function):
         import ctypes as C
         from . import _lib as L
         lib = L.lib()
-        B, A, g, _, D = pred.shape
+        B, A, gh, gw, D = pred.shape
         dev = pred.device
         with torch.cuda.device(dev):
             out = torch.empty(4, dtype=torch.float32, device=dev)
             counts = torch.empty(2, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.yolo_loss_workspace_bytes(B, g), dtype=torch.uint8, device=dev)
+            ws = torch.empty(lib.yolo_loss_workspace_bytes_hw(B, gh, gw), dtype=torch.uint8, device=dev)
             strides = (C.c_int64 * 5)(*pred.stride())
-            L.check(lib.yolo_loss_fwd(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, g, D - 5, out.data_ptr(),
-                                      counts.data_ptr(), ws.data_ptr(), ws.numel(), L.current_stream()), "yolo_loss_fwd")
+            L.check(lib.yolo_loss_fwd_hw(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, gh, gw, D - 5, out.data_ptr(),
+                                         counts.data_ptr(), ws.data_ptr(), ws.numel(), L.current_stream()), "yolo_loss_fwd")
         ctx.save_for_backward(pred, target, anchors, counts)
         return out
 
@@ -62,13 +62,13 @@ class _FusedLossFn(torch.autograd.Function):
         import ctypes as C
         from . import _lib as L
         pred, target, anchors, counts = ctx.saved_tensors
-        B, A, g, _, D = pred.shape
+        B, A, gh, gw, D = pred.shape
         with torch.cuda.device(pred.device):
-            dpred = torch.empty((B, A, g, g, D), dtype=torch.float32, device=pred.device)
+            dpred = torch.empty((B, A, gh, gw, D), dtype=torch.float32, device=pred.device)
             gout = gout.float().contiguous()
             strides = (C.c_int64 * 5)(*pred.stride())
-            L.check(L.lib().yolo_loss_bwd(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, g, D - 5,
-                                          counts.data_ptr(), gout.data_ptr(), dpred.data_ptr(), L.current_stream()), "yolo_loss_bwd")
+            L.check(L.lib().yolo_loss_bwd_hw(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, gh, gw, D - 5,
+                                             counts.data_ptr(), gout.data_ptr(), dpred.data_ptr(), L.current_stream()), "yolo_loss_bwd")
         return dpred, None, None
 
 
@@ -83,11 +83,11 @@ class FusedYOLOLoss(nn.Module):
         if not predictions.is_cuda:
             raise RuntimeError("FusedYOLOLoss runs on MI355X only (no CPU fallback); use YOLOLoss on the CPU")
         if predictions.dim() != 5 or predictions.shape[1] != 3:
-            raise ValueError("predictions must be a (B,3,g,g,5+nc) tensor")
+            raise ValueError("predictions must be a (B,3,gh,gw,5+nc) tensor")
         if predictions.dtype in (torch.float16, torch.bfloat16):
             predictions = predictions.float()          # autocast heads (train.py:53): the loss terms are evaluated in fp32, as autocast does
         elif predictions.dtype != torch.float32:
-            raise ValueError("predictions must be a floating-point (B,3,g,g,5+nc) tensor")
+            raise ValueError("predictions must be a floating-point (B,3,gh,gw,5+nc) tensor")
         t = targets.detach()
         if t.dtype != torch.float32 or not t.is_contiguous():
             t = t.float().contiguous()

@@ -139,8 +139,8 @@ def _forward(state, model, plan: TrainPlan, x, use_tape=False):
     preds = [None] * prog.n_pred
     for op in prog.ops:
         if op["pred"] is not None:
-            g = op["Ho"]
-            preds[op["pred"]] = torch.empty((B, 3, g, g, op["block"].conv.out_channels // 3), dtype=torch.float32, device=dev)
+            preds[op["pred"]] = torch.empty((B, 3, op["Ho"], op["Wo"], op["block"].conv.out_channels // 3), dtype=torch.float32,
+                                            device=dev)
     tape = plan.fwd_tape if use_tape else None
     if tape is not None and tape.fresh():
         slots = {"x": xin.data_ptr()}
@@ -461,8 +461,12 @@ def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_inpu
             else:
                 dp = dp.float()
                 strides = (C.c_int64 * 5)(*dp.stride())
-                L.check(lib.yolo_head_grad_to_nhwc(dp.data_ptr(), strides, dz.data_ptr(), B, Ho, cout // 3, coutp, code, stream),
-                        "yolo_head_grad_to_nhwc")
+                if Ho == Wo:
+                    L.check(lib.yolo_head_grad_to_nhwc(dp.data_ptr(), strides, dz.data_ptr(), B, Ho, cout // 3, coutp, code, stream),
+                            "yolo_head_grad_to_nhwc")
+                else:
+                    L.check(lib.yolo_head_grad_to_nhwc_hw(dp.data_ptr(), strides, dz.data_ptr(), B, Ho, Wo, cout // 3, coutp, code,
+                                                          stream), "yolo_head_grad_to_nhwc_hw")
             if need.get(id(cv.bias), False):
                 db = keep(torch.empty(coutp, dtype=torch.float32, device=dev))
                 L.check(lib.yolo_bn_act_bwd(dz.data_ptr(), coutp, 0, 0, 0, 0, 0, 0, 0, 0, 0, m, coutp, L.ACT_NONE, 0, db.data_ptr(),
@@ -696,16 +700,16 @@ def _same_params(plan, plist):
 
 def forward_train(state, model, x):
     B, Cc, H, W = x.shape
-    if Cc != model.in_channels or H != W or H % 32:
-        raise ValueError(f"input must be (B,{model.in_channels},S,S) with S a multiple of 32, got {tuple(x.shape)}")
+    if Cc != model.in_channels or H % 32 or W % 32 or H <= 0 or W <= 0:
+        raise ValueError(f"input must be (B,{model.in_channels},H,W) with H and W multiples of 32, got {tuple(x.shape)}")
     with torch.cuda.device(x.device):
         if state._train_nan_pending is not None:
             state.poll_nan()                              # guards left by earlier train-mode forwards (nan_check = "deferred"): never waits
         dt = resolve_dtype(state.compute_dtype)           # autocast (train.py:53) selects the 16-bit kernels
-        key = ("train", B, H, x.device.index, dt)
+        key = ("train", B, (H, W), x.device.index, dt)
         plan = state._plans.get(key)
         if plan is None:
-            prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4)   # 16-bit kernels read 8-channel pieces
+            prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4, W=W)   # 16-bit kernels read 8-channel pieces
             plan = TrainPlan(prog, x.device, dt)
             if dt != "fp32" and not plan.stem:
                 raise NotImplementedError("the 16-bit path needs the 3->32 stem block as the first layer")

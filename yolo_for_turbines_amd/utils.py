@@ -18,7 +18,7 @@ from . import _lib as L
 
 __all__ = ["iou_aligned", "calc_iou", "cells_to_boxes", "non_max_suppression", "decode_boxes", "nms_indices",
            "detect", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
-           "save_checkpoint", "load_checkpoint"]
+           "save_checkpoint", "load_checkpoint", "scaled_anchors"]
 
 
 # -------------------------------------------------------------------------------- IoU
@@ -49,12 +49,39 @@ def calc_iou(boxes1, boxes2, box_format="center"):
     return inter / (w1 * h1 + w2 * h2 - inter + 1e-6)
 
 
+# ------------------------------------------------------------------------------ anchors
+STRIDES = (32, 16, 8)
+
+
+def scaled_anchors(anchors, H, W=None):
+    """Anchors in grid cells for an H x W input, (3, 3, 2) fp32: ``anchors[k] * (L / stride_k)`` with L = max(H, W) - an
+    H x W canvas behaves like the square canvas of side L with its padding cropped away. For H == W this is
+    the reference's ``torch.tensor(config.ANCHORS) * S`` (train.py:195-197) bit for bit."""
+    W = H if W is None else W
+    L_ = max(int(H), int(W))
+    if L_ % 32:
+        raise ValueError(f"H and W must be multiples of 32, got {H} x {W}")
+    grids = torch.tensor([L_ // s for s in STRIDES]).view(3, 1, 1)
+    return torch.as_tensor(anchors, dtype=torch.float32).reshape(3, 3, 2) * grids
+
+
+def _grid_hw(grid_size):
+    """None | g | (gh, gw) -> None | (gh, gw)."""
+    if grid_size is None:
+        return None
+    if isinstance(grid_size, (tuple, list)):
+        gh, gw = grid_size
+        return int(gh), int(gw)
+    return int(grid_size), int(grid_size)
+
+
 # ------------------------------------------------------------------------------ decode
 def decode_boxes(predictions, anchors, grid_size=None, is_pred=True, out=None, box_offset=0, mutate=True):
-    """Device decode of one scale: (B,3,g,g,5+nc) -> (B, 3*g*g, 6) fp32 tensor
+    """Device decode of one scale: (B,3,gh,gw,5+nc) -> (B, 3*gh*gw, 6) fp32 tensor
     [cx,cy,w,h,obj,cls] normalised to [0,1]; mutates ``predictions[...,0:4]`` in place when
     ``is_pred`` exactly like the reference (utils.py:106-110) unless ``mutate=False``. ``out`` / ``box_offset`` let
-    several scales share one (B, N_total, 6) buffer."""
+    several scales share one (B, N_total, 6) buffer. ``grid_size``: None (taken from the tensor), g or (gh, gw); x and w
+    are normalised by gw, y and h by gh."""
     if not predictions.is_cuda:
         raise RuntimeError("decode_boxes runs on MI355X only (no CPU fallback)")
     if predictions.dtype in (torch.float16, torch.bfloat16):
@@ -66,10 +93,10 @@ def decode_boxes(predictions, anchors, grid_size=None, is_pred=True, out=None, b
         return res
     if predictions.dtype != torch.float32:
         raise NotImplementedError("decode_boxes: floating-point predictions only")
-    B, A, g, g2, D = predictions.shape
-    if A != 3 or g != g2 or (grid_size is not None and int(grid_size) != g):
+    B, A, gh, gw, D = predictions.shape
+    if A != 3 or (grid_size is not None and _grid_hw(grid_size) != (gh, gw)):
         raise ValueError(f"bad prediction shape {tuple(predictions.shape)} for grid {grid_size}")
-    n = 3 * g * g
+    n = 3 * gh * gw
     if out is None:
         out = torch.empty((B, n, 6), dtype=torch.float32, device=predictions.device)
         box_offset = 0
@@ -79,13 +106,14 @@ def decode_boxes(predictions, anchors, grid_size=None, is_pred=True, out=None, b
         if is_pred else None
     strides = (C.c_int64 * 5)(*predictions.stride())
     with torch.cuda.device(predictions.device):
-        L.check(L.lib().yolo_decode(predictions.data_ptr(), strides, L.ptr(anc), B, g, D - 5, (1 if mutate else 2) if is_pred else 0,
-                                    out.data_ptr(), out.shape[1], int(box_offset), L.current_stream()), "yolo_decode")
+        L.check(L.lib().yolo_decode_hw(predictions.data_ptr(), strides, L.ptr(anc), B, gh, gw, D - 5,
+                                       (1 if mutate else 2) if is_pred else 0, out.data_ptr(), out.shape[1], int(box_offset),
+                                       L.current_stream()), "yolo_decode")
     return out
 
 
 def cells_to_boxes(predictions, anchors, grid_size, is_pred=True):
-    """Reference signature (utils.py:86-148): returns ``list[B][3*g*g][6]``."""
+    """Reference signature (utils.py:86-148): returns ``list[B][3*gh*gw][6]``; ``grid_size`` is g or (gh, gw)."""
     return decode_boxes(predictions, anchors, grid_size, is_pred).tolist()
 
 
@@ -149,7 +177,7 @@ def detect(predictions, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, b
     ``mutate=True`` also performs the in-place sigmoid / exp write-back ``cells_to_boxes`` does to the prediction tensors
     (utils.py:106-110); the reference's callers of this sequence never read them again, so the default leaves them alone."""
     B = predictions[0].shape[0]
-    n_per = [3 * p.shape[2] * p.shape[2] for p in predictions]
+    n_per = [3 * p.shape[2] * p.shape[3] for p in predictions]
     total = sum(n_per)
     dev = predictions[0].device
     boxes = torch.empty((B, total, 6), dtype=torch.float32, device=dev)
@@ -160,13 +188,13 @@ def detect(predictions, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, b
             pp = (C.c_void_p * 3)(*[p.data_ptr() for p in predictions])
             st = (C.c_int64 * 15)(*[v for p in predictions for v in p.stride()])
             ap = (C.c_void_p * 3)(*[a.data_ptr() for a in anc])
-            gg = (C.c_int * 3)(*[p.shape[2] for p in predictions])
-            L.check(L.lib().yolo_decode3_ex(pp, st, ap, gg, B, predictions[0].shape[4] - 5, int(bool(mutate)), boxes.data_ptr(), total,
+            gg = (C.c_int * 6)(*[v for p in predictions for v in (p.shape[2], p.shape[3])])      # (gh, gw) per scale
+            L.check(L.lib().yolo_decode3_hw(pp, st, ap, gg, B, predictions[0].shape[4] - 5, int(bool(mutate)), boxes.data_ptr(), total,
                                             L.current_stream()), "yolo_decode3")
     else:
         off = 0
         for p, a, n in zip(predictions, scaled_anchors, n_per):
-            decode_boxes(p, a, p.shape[2], True, out=boxes, box_offset=off, mutate=mutate)
+            decode_boxes(p, a, (p.shape[2], p.shape[3]), True, out=boxes, box_offset=off, mutate=mutate)
             off += n
     keep, count = nms_indices(boxes, iou_threshold, obj_threshold, box_format)
     return boxes, keep, count
@@ -197,7 +225,8 @@ def build_targets(boxes, anchors, image_size, counts=None, ignore_iou_threshold=
 
     ``boxes``: per-image lists ``[[x, y, w, h, class], ...]`` (normalised, the dataset's order) or a padded
     ``(B, max_boxes, 5)`` tensor with ``counts`` (B). ``anchors``: the 3x3x2 normalised anchor table
-    (``config.ANCHORS``). Returns the tuple of three ``(B, 3, g, g, 6)`` fp32 tensors the loss consumes."""
+    (``config.ANCHORS``). ``image_size``: S or (H, W) (multiples of 32; per-axis grids, see ``yolo_build_targets_hw``).
+    Returns the tuple of three ``(B, 3, gh, gw, 6)`` fp32 tensors the loss consumes."""
     if isinstance(boxes, torch.Tensor):
         if counts is None:
             raise ValueError("a padded box tensor needs `counts`")
@@ -220,11 +249,11 @@ def build_targets(boxes, anchors, image_size, counts=None, ignore_iou_threshold=
     ct = ct.to(dev).contiguous()
     anc = torch.as_tensor(anchors, dtype=torch.float32).reshape(9, 2).to(dev).contiguous()
     B, mb = bt.shape[0], bt.shape[1]
-    S = int(image_size)
+    H, W = _grid_hw(image_size)
     with torch.cuda.device(dev):
-        outs = [torch.empty((B, 3, g, g, 6), dtype=torch.float32, device=dev) for g in (S // 32, S // 16, S // 8)]
-        L.check(L.lib().yolo_build_targets(bt.data_ptr(), ct.data_ptr(), mb, anc.data_ptr(), B, S, float(ignore_iou_threshold),
-                                           outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), L.current_stream()),
+        outs = [torch.empty((B, 3, H // s, W // s, 6), dtype=torch.float32, device=dev) for s in STRIDES]
+        L.check(L.lib().yolo_build_targets_hw(bt.data_ptr(), ct.data_ptr(), mb, anc.data_ptr(), B, H, W, float(ignore_iou_threshold),
+                                              outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), L.current_stream()),
                 "yolo_build_targets")
     return tuple(outs)
 
@@ -306,10 +335,12 @@ def accuracy_counts(predictions, targets, object_threshold, counts=None):
             if p.dtype != torch.float32:
                 raise ValueError("fp32 predictions expected")
             t = t.to(dev, torch.float32).contiguous()
-            B, _, g, _, D = p.shape
+            B, _, gh, gw, D = p.shape
+            if tuple(t.shape[:4]) != (B, 3, gh, gw):
+                raise ValueError(f"target shape {tuple(t.shape)} does not match predictions {tuple(p.shape)}")
             strides = (C.c_int64 * 5)(*p.stride())
-            L.check(L.lib().yolo_accuracy_counts(p.data_ptr(), strides, t.data_ptr(), B, g, D - 5, float(object_threshold),
-                                                 counts.data_ptr(), L.current_stream()), "yolo_accuracy_counts")
+            L.check(L.lib().yolo_accuracy_counts_hw(p.data_ptr(), strides, t.data_ptr(), B, gh, gw, D - 5, float(object_threshold),
+                                                    counts.data_ptr(), L.current_stream()), "yolo_accuracy_counts")
     return counts
 
 
@@ -353,10 +384,12 @@ def eval_boxes(loader, model, iou_threshold, anchors, obj_threshold, box_format=
         with torch.no_grad():
             predictions = model(x.to(dev))
         B = x.shape[0]
-        sa = [torch.as_tensor(anchors[i], dtype=torch.float32, device=dev).reshape(3, 2) * predictions[i].shape[2] for i in range(3)]
+        # anchors in grid cells: * S / stride (utils.py:300-309); an H x W batch uses L = max(H, W) (see scaled_anchors)
+        sa = [torch.as_tensor(anchors[i], dtype=torch.float32, device=dev).reshape(3, 2) * max(predictions[i].shape[2:4])
+              for i in range(3)]
         boxes, keep, count = detect(predictions, sa, iou_threshold, obj_threshold, box_format)
-        g = predictions[2].shape[2]
-        true_boxes = decode_boxes(targets[2].to(dev, torch.float32).contiguous(), sa[2], g, is_pred=False)     # (B, 3 g^2, 6)
+        ghw = tuple(predictions[2].shape[2:4])
+        true_boxes = decode_boxes(targets[2].to(dev, torch.float32).contiguous(), sa[2], ghw, is_pred=False)     # (B, 3 gh gw, 6)
         cnt = count.tolist()
         for b in range(B):
             kb = boxes[b, keep[b, :cnt[b]].long()]
@@ -381,41 +414,59 @@ def get_eval_boxes(loader, model, iou_threshold, anchors, obj_threshold, box_for
 
 
 # ------------------------------------------------------------------------------ letterbox
-def letterbox(images, image_size=416, device=None):
+def letterbox(images, image_size=416, device=None, rect=False):
     """``config.set_only_image_transforms`` (config.py:101-113) on the device: each uint8 (H, W, 3) image (tensor or
     array) is resized so that its longer side is ``image_size`` (bilinear), centred on a zero canvas, scaled to [0,1]
-    and laid out CHW. Returns ``(batch (B,3,S,S) fp32, meta)`` with ``meta[i] = (orig_h, orig_w, new_h, new_w,
-    pad_top, pad_left)`` for :func:`unletterbox_boxes`. Parity with cv2 is unpinned (see csrc/preprocess.hip)."""
+    and laid out CHW. Returns ``(batch (B,3,Hc,Wc) fp32, meta)`` with ``meta[i] = (orig_h, orig_w, new_h, new_w,
+    pad_top, pad_left)`` for :func:`unletterbox_boxes`. Parity with cv2 is unpinned (see csrc/preprocess.hip).
+    ``rect=False``: the canvas is ``image_size`` square. ``rect=True``: (Hc, Wc) are the smallest multiples of 32 that hold
+    every resized image of the batch (``yolo_letterbox_canvas``); resize arithmetic and the centring rule are the square
+    path's, so the resized pixels are the same bits as the interior of the square letterbox."""
     if isinstance(images, (torch.Tensor,)) and images.dim() == 3 or not isinstance(images, (list, tuple)):
         images = [images]
     dev = torch.device("cuda" if device is None else device)
     if dev.type != "cuda":
         raise RuntimeError("letterbox runs on MI355X only (no CPU fallback)")
     S = int(image_size)
+    ts = []
+    for im in images:
+        t = torch.as_tensor(im)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("images must be uint8 (H, W, 3)")
+        ts.append(t)
+    hw = (C.c_int32 * max(2 * len(ts), 2))(*[int(v) for t in ts for v in t.shape[:2]])
+    canvas = (C.c_int32 * 2)()
+    L.check(L.lib().yolo_letterbox_canvas(hw, len(ts), S, int(bool(rect)), canvas), "yolo_letterbox_canvas")
+    Hc, Wc = int(canvas[0]), int(canvas[1])
     with torch.cuda.device(dev):
-        out = torch.empty((len(images), 3, S, S), dtype=torch.float32, device=dev)
+        out = torch.empty((len(ts), 3, Hc, Wc), dtype=torch.float32, device=dev)
         meta = []
-        for i, im in enumerate(images):
-            t = torch.as_tensor(im)
-            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-                raise ValueError("images must be uint8 (H, W, 3)")
+        for i, t in enumerate(ts):
             t = t.to(dev).contiguous()
             nhw, pad = (C.c_int * 2)(), (C.c_int * 2)()
-            L.check(L.lib().yolo_letterbox(t.data_ptr(), t.shape[0], t.shape[1], S, out[i].data_ptr(), nhw, pad, L.current_stream()),
-                    "yolo_letterbox")
+            L.check(L.lib().yolo_letterbox_hw(t.data_ptr(), t.shape[0], t.shape[1], S, Hc, Wc, out[i].data_ptr(), nhw, pad,
+                                              L.current_stream()), "yolo_letterbox")
             t.record_stream(torch.cuda.current_stream())
             meta.append((int(t.shape[0]), int(t.shape[1]), nhw[0], nhw[1], pad[0], pad[1]))
     return out, meta
 
 
-def unletterbox_boxes(boxes, original_hw, resized_hw):
+def unletterbox_boxes(boxes, original_hw, resized_hw, meta=None):
     """Box mapping of ``plot_original`` (utils.py:475-501): normalised letterboxed ``[cx, cy, w, h, obj, cls]`` rows ->
-    coordinates normalised to the ORIGINAL image. Same arithmetic (incl. its ``int(o * scale)`` size and ``// 2`` padding)."""
-    o_h, o_w = original_hw
+    coordinates normalised to the ORIGINAL image. Same arithmetic (incl. its ``int(o * scale)`` size and ``// 2`` padding).
+    ``resized_hw`` is the canvas (H, W). The reference's formula re-derives the resize from the canvas, which is only exact
+    for a square canvas: on a rectangular one the short side can hold padding of its own (another image of the batch set the
+    canvas, or the resized side was rounded up to 32), and ``min(r_w / o_w, r_h / o_h)`` then picks the wrong axis or is
+    off by a rounding. ``meta`` (the tuple :func:`letterbox` returned for this image) uses the letterbox's own resized size
+    and padding instead."""
     r_h, r_w = resized_hw
-    scale = min(r_w / o_w, r_h / o_h)
-    new_width, new_height = int(o_w * scale), int(o_h * scale)
-    pad_width, pad_height = (r_w - new_width) // 2, (r_h - new_height) // 2
+    if meta is not None:
+        _, _, new_height, new_width, pad_height, pad_width = meta
+    else:
+        o_h, o_w = original_hw
+        scale = min(r_w / o_w, r_h / o_h)
+        new_width, new_height = int(o_w * scale), int(o_h * scale)
+        pad_width, pad_height = (r_w - new_width) // 2, (r_h - new_height) // 2
     return [[(b[0] * r_w - pad_width) / new_width, (b[1] * r_h - pad_height) / new_height, (b[2] * r_w) / new_width,
              (b[3] * r_h) / new_height, b[4], b[5]] for b in boxes]
 
