@@ -273,6 +273,39 @@ int yolo_build_targets(const float* boxes, const int32_t* counts, int max_boxes,
 int yolo_build_targets_hw(const float* boxes, const int32_t* counts, int max_boxes, const float* anchors_9x2, int b, int image_h,
                           int image_w, float ignore_iou, float* t0, float* t1, float* t2, void* stream);
 
+/* ---- training augmentation (config.py:60-87 set_train_transforms, utils.py:503-662 mosaic_augmentation); parity with
+ * cv2 / albumentations UNPINNED (see csrc/augment.hip) ------------------------------------------------------------------ */
+/* Per-image parameter row, float64 (the draws of the transforms; the kernels hold no randomness). A switch is on when != 0.
+ * mosaic: YOLO_AUG_MOSAIC + 2k, + 2k + 1 = (x, y) of cutout draw k, k < 10 (each in [0.2, 0.3]). */
+#define YOLO_AUG_DO_HSV 0
+#define YOLO_AUG_HUE 1
+#define YOLO_AUG_SAT 2
+#define YOLO_AUG_VAL 3
+#define YOLO_AUG_DO_SSR 4
+#define YOLO_AUG_SCALE 5
+#define YOLO_AUG_DX 6
+#define YOLO_AUG_DY 7
+#define YOLO_AUG_DO_FLIP 8
+#define YOLO_AUG_MOSAIC 9
+#define YOLO_AUG_NPARAM 29
+/* Tables. Host (read here, validated): hw [n_pool][2] source sizes, src [b][4] pool indices per output image: {i, -1, -1, -1}
+ * = the standard transform of image i, four images = mosaic (square canvas only; all four must resize to the same size).
+ * Device: the same hw / src (hw_dev, src_dev), params [b][YOLO_AUG_NPARAM], boxes [n_pool][max_in][5] yolo
+ * (x, y, w, h, class) float64, nbox [n_pool] (-1 = no label file: letterbox only, count 0). Canvas (out_h, out_w):
+ * multiples of 32; images are resized so that their longer side is max(out_h, out_w). */
+size_t yolo_augment_workspace_bytes(int b, int out_h, int out_w);   /* the uint8 HWC staging canvas of yolo_augment_images */
+/* out_boxes (B, max_out, 5) fp32 yolo, rows past counts[b] zeroed; counts (B) int32: the input of yolo_build_targets_hw.
+ * max_out must be >= the sum of nbox over the row's images (extra boxes are not written). sel (B) int32 receives the
+ * path each image takes and is read by yolo_augment_images: run this first, on the same stream. */
+int yolo_augment_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, const int32_t* src_dev,
+                       const int32_t* hw, int n_pool, const int32_t* src, const double* params, int b, int out_h, int out_w,
+                       float* out_boxes, int32_t* counts, int max_out, int32_t* sel, void* stream);
+/* pool: uint8 HWC images at byte offsets offsets (device, int64 [n_pool]); staging: yolo_augment_workspace_bytes;
+ * out_chw: fp32 (B, 3, out_h, out_w) in [0, 1]. */
+int yolo_augment_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, const int32_t* src_dev,
+                        const int32_t* hw, int n_pool, const int32_t* src, const double* params, const int32_t* sel, int b, int out_h,
+                        int out_w, void* staging, float* out_chw, void* stream);
+
 /* ---- evaluation: average precision per class (utils.py:193-274) ----------------------------- */
 /* rows are [image, x, y, w, h, objectness, class] fp32. dets_sorted: class ascending, objectness descending (stable);
  * gts_sorted: class ascending, image ascending (stable); *_class_offsets: [num_classes + 1] row ranges.

@@ -10,26 +10,9 @@
 // albumentations' size / padding rules (banker's rounding of dim * scale, top/left pad = floor(diff / 2)); it is tested
 // bit for bit against oracle/preprocess.py, which restates the same published rules — not against cv2 itself.
 #include "common.h"
+#include "resample.h"
 
 namespace yolo {
-
-__device__ __forceinline__ int cv_round(double v) { return (int)rint(v); }          // round half to even, like cvRound
-
-__device__ __forceinline__ void lin_coef(int d, double scale, int src_n, int* s0, int* s1, int* c0, int* c1) {
-    double f = (d + 0.5) * scale - 0.5;
-    int s = (int)floor(f);
-    f -= s;
-    if (s < 0) { s = 0; f = 0; }
-    if (s >= src_n - 1) { s = src_n - 1; f = 0; }
-    *s0 = s;
-    *s1 = s + 1 < src_n ? s + 1 : s;
-    const float ff = (float)f;
-    int a1 = cv_round((double)(ff * 2048.f));
-    int a0 = cv_round((double)((1.f - ff) * 2048.f));
-    a0 = a0 > 32767 ? 32767 : a0;
-    a1 = a1 > 32767 ? 32767 : a1;
-    *c0 = a0; *c1 = a1;
-}
 
 // out: (3, SH, SW) fp32; one thread per output pixel
 __global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* __restrict__ img, int h, int w, int nh, int nw,
@@ -41,20 +24,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* __r
     float v[3] = {0.f, 0.f, 0.f};
     if ((unsigned)y < (unsigned)nh && (unsigned)x < (unsigned)nw) {
         unsigned char px[3];
-        if (nh == h && nw == w) {
-            for (int c = 0; c < 3; ++c) px[c] = img[((size_t)y * w + x) * 3 + c];
-        } else {
-            const double sx = (double)w / nw, sy = (double)h / nh;
-            int x0, x1, a0, a1, y0, y1, b0, b1;
-            lin_coef(x, sx, w, &x0, &x1, &a0, &a1);
-            lin_coef(y, sy, h, &y0, &y1, &b0, &b1);
-            for (int c = 0; c < 3; ++c) {
-                const int r0 = img[((size_t)y0 * w + x0) * 3 + c] * a0 + img[((size_t)y0 * w + x1) * 3 + c] * a1;
-                const int r1 = img[((size_t)y1 * w + x0) * 3 + c] * a0 + img[((size_t)y1 * w + x1) * 3 + c] * a1;
-                const int t = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-                px[c] = (unsigned char)(t < 0 ? 0 : (t > 255 ? 255 : t));
-            }
-        }
+        resize_px(img, h, w, nh, nw, y, x, px);
         const float inv = 1.0f / 255.0f;                     // albumentations multiplies by the fp32 reciprocal
         for (int c = 0; c < 3; ++c) v[c] = (float)px[c] * inv;
     }
@@ -66,19 +36,6 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* __r
 using namespace yolo;
 
 extern "C" {
-
-/* albumentations LongestMaxSize: the size an (h, w) image is resized to (banker's rounding of dim * scale) */
-static void resized_hw(int h, int w, int size, int* nh_out, int* nw_out) {
-    const double scale = (double)size / (double)(h > w ? h : w);
-    auto py3round = [](double v) {                         // albumentations.py3round: banker's rounding
-        const double r = nearbyint(v);                      // FE_TONEAREST: half to even
-        return (int)r;
-    };
-    int nh = h, nw = w;
-    if (scale != 1.0) { nh = py3round(h * scale); nw = py3round(w * scale); }
-    *nh_out = nh < 1 ? 1 : nh;
-    *nw_out = nw < 1 ? 1 : nw;
-}
 
 int yolo_letterbox_canvas(const int32_t* hw, int n, int size, int rect, int32_t* canvas_hw) {
     if (!canvas_hw || size <= 0 || n < 0 || (rect && (n == 0 || !hw))) return fail(YOLO_ERR_ARG, "letterbox_canvas: bad arguments");
