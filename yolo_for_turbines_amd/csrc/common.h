@@ -206,6 +206,13 @@ bool wino_eligible(const yolo_conv_desc* d);
 size_t wino_workspace_bytes(const yolo_conv_desc* d);
 int conv_wino_launch(const yolo_conv_desc* d, const void* x, const float* U, const float* scale, const float* shift,
                      const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
+// conv_wino4_f32.hip (fp32 3x3 stride 1 by Winograd F(4x4, 3x3), tile 15: transform pass (input and filters, from the row-major
+// section of the packed weights) into a caller-owned workspace + 36 GEMMs in six passes)
+bool wino4_supported(const yolo_conv_desc* d);
+bool wino4_eligible(const yolo_conv_desc* d);
+size_t wino4_workspace_bytes(const yolo_conv_desc* d);
+int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* scale, const float* shift,
+                      const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // conv_h16.hip (bf16 / fp16 patch kernel)
 size_t h16_frag_elems(int cout, int cin, int ks);
 int h16_pack(const float* w_oihw, void* wf, int cout, int cin, int ks, int dtype, hipStream_t s);

@@ -269,6 +269,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvArgs p) {
 constexpr int kNumTiles = 10;     // 1-4: register-staged tiles above; 5/6: conv_f32_v2.hip with BN = 64/128; 7: BN = 64, one patch buffer (3 blocks/CU); 8-10: 16-bit only (conv3_dma_h16)
 constexpr int kTileRs = 12;       // conv1_rs_f32.hip (fp32 1x1, weights in registers)
 constexpr int kTileWino = 13;     // conv_wino_f32.hip (fp32 3x3 stride 1, Winograd F(2x2, 3x3); needs the caller's workspace)
+constexpr int kTileWino4 = 15;    // conv_wino4_f32.hip (fp32 3x3 stride 1, Winograd F(4x4, 3x3); needs the caller's workspace)
 constexpr int kMaxTileId = 31;    // ids above kNumTiles select timing probes of the diagnostic library (make probes); the product library runs tile 8 for them
 
 static size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * LDS_LD * sizeof(float); }
@@ -292,7 +293,8 @@ static int launch_tile(const ConvArgs& a, bool smallc, hipStream_t s) {
 // stride-1 layers with cin % 32 == 0 go to the patch/fragment-stream kernel (ids 5, 6).
 static int pick_direct_tile(const yolo_conv_desc* d);
 static int pick_tile(const yolo_conv_desc* d) {
-    if (wino_eligible(d)) return kTileWino;         // with a workspace (yolo_conv_fwd_ws / the launch table); without one: the ids below
+    if (wino4_eligible(d)) return kTileWino4;       // with a workspace (yolo_conv_fwd_ws / the launch table); without one: the ids below
+    if (wino_eligible(d)) return kTileWino;
     return pick_direct_tile(d);
 }
 
@@ -353,8 +355,13 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     // heuristic, or tile 12 explicitly; tiles 1-4 keep the register-staged kernel for A/B)
     if ((d->tile == 0 || d->tile == kTileRs) && conv1_rs_eligible(d, residual)) return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     if (d->tile == kTileRs) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 12 needs a 1x1 with 256 / 384 / 512 input channels and cout %% 128 == 0");
-    // 3x3 stride 1 by Winograd F(2x2, 3x3): tile 13 explicitly, or the heuristic when the caller brought a large enough workspace
-    // (yolo_conv_fwd itself has none: the library allocates nothing)
+    // 3x3 stride 1 by Winograd F(4x4, 3x3): tile 15 explicitly, or the heuristic when the caller brought a large enough workspace
+    // (yolo_conv_fwd itself has none: the library allocates nothing); the filters are transformed per launch from the row-major section
+    if (d->tile == kTileWino4 || (d->tile == 0 && wino4_eligible(d) && ws && ws_bytes >= wino4_workspace_bytes(d))) {
+        if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
+        return conv_wino4_launch(d, x, (const float*)w, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
+    }
+    // ... by F(2x2, 3x3): tile 13 explicitly, or the heuristic as above
     if (d->tile == kTileWino || d->tile == kTileWino + 1 || (d->tile >= 16 && d->ksize == 3 && wino_supported(d)) ||      // 16+: timing probes of the diagnostic library (make wstamps)
         (d->tile == 0 && wino_eligible(d) && ws && ws_bytes >= wino_workspace_bytes(d))) {
         if (!wino_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 13 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
@@ -395,6 +402,7 @@ int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, 
 
 size_t yolo_conv_workspace_bytes(const yolo_conv_desc* d) {
     if (yolo::validate(d)) return 0;
+    if (d->tile == yolo::kTileWino4 || (d->tile == 0 && yolo::wino4_eligible(d))) return yolo::wino4_workspace_bytes(d);
     if (d->tile == yolo::kTileWino || d->tile == yolo::kTileWino + 1 || d->tile >= 16 || (d->tile == 0 && yolo::wino_eligible(d))) return yolo::wino_workspace_bytes(d);
     return 0;
 }

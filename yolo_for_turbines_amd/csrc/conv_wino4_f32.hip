@@ -1,0 +1,481 @@
+// conv_wino4_f32.hip — the fp32 3x3 stride-1 blocks on large maps by Winograd F(4x4, 3x3):
+//
+//     Y = A^T [ (G g G^T) .* (B^T d B) ] A            per 6x6 input tile d (stride 4), 3x3 filter g, 4x4 output tile Y
+//
+// 36 multiplications per 16 outputs and (ci, co) pair instead of F(2x2)'s 16 per 4: the matrix cores execute 0.5625x the
+// work of conv_wino_f32.hip, and the transformed input V4 is 2.25x the activation instead of 4x. Interpolation points
+// (0, 1, -1, 2, -1/2, inf) instead of the textbook (0, +-1, +-2, inf): the fp32 error of the transforms is ~4x smaller
+// (max|err| / max|y| ~3e-6 against an fp64 convolution at K = 128 .. 256). From the points:
+//   A^T[i][j] = p_j^i (the column of inf is e_3), G[j][k] = p_j^k / prod_{l != j} (p_j - p_l) (the row of inf is e_2), and
+//   B^T solves sum_j A^T[i][j] G[j][k] B^T[j][l] = delta(l, i + k). A^T and B^T hold dyadic fractions only (exact in fp32);
+//   G holds thirds and fifteenths: the filter transform runs in fp64 and rounds once.
+//
+// Two kernels per launch:
+//   wino4_xform_f32  V4[xi][c4][tile_pad64][4] = (B^T d B)[xi] for every 6x6 input tile, xi = 6a + b, c4 running to C4p (= C4
+//                    rounded up to even, the padding plane zero); the blocks behind the input transform write
+//                    U4[xi][c4][co_pad64][4] = (G g G^T)[xi] from the row-major section at the start of the packed weights
+//                    (yolo_pack_weights, and yolo_pack_weights_dgrad with flip = 1 for the stride-1 input gradient). U4 is
+//                    computed per launch and lives in the workspace behind V4: the packed weight format stays as it is.
+//   conv_wino4_f32   per workgroup 64 tiles x 64 output channels (the block of conv_wino_f32: the same operand bytes per MFMA, so
+//                    the same LDS-DMA price per matrix cycle): 36 GEMMs D_xi[co][tile] = sum_ci U4_xi[co][ci] V4_xi[tile][ci] in SIX
+//                    passes over K, one row a of the 6x6 product matrix M per pass (xi = 6a .. 6a + 5). Y = A^T M A is linear in the
+//                    rows of M, so each pass folds its row into the 4x4 output tiles right away (t = M[a][.] A, Y += A^T[.][a] t^T)
+//                    and only those partial tiles survive a pass. 8 waves, two per SIMD; a wave owns 32 tiles x 16 channels as two
+//                    16 x 16 blocks of v_mfma_f32_16x16x4_f32 per xi: 48 accumulators per pass (VGPRs), 128 partial-tile registers
+//                    (parked in the AGPR half between passes). A stage is 8 channels = two planes x 6 xi x (V, U) = 24 KiB.
+//                    Epilogue: BN scale / shift, activation, residual, ld / off views and the NaN flag as in conv_wino_f32,
+//                    staged through LDS one output row of the tile at a time.
+#include "wino_dma.h"
+
+namespace yolo {
+
+// points (0, 1, -1, 2, -1/2, inf)
+__device__ constexpr float W4_BT[6][6] = {
+    {1.f, 1.5f, -2.f, -1.5f, 1.f, 0.f},
+    {0.f, -1.f, -2.5f, -0.5f, 1.f, 0.f},
+    {0.f, 1.f, 0.5f, -2.5f, 1.f, 0.f},
+    {0.f, -0.5f, -1.f, 0.5f, 1.f, 0.f},
+    {0.f, 2.f, -1.f, -2.f, 1.f, 0.f},
+    {0.f, 1.f, 1.5f, -2.f, -1.5f, 1.f},
+};
+__device__ constexpr float W4_AT[4][6] = {
+    {1.f, 1.f, 1.f, 1.f, 1.f, 0.f},
+    {0.f, 1.f, -1.f, 2.f, -0.5f, 0.f},
+    {0.f, 1.f, 1.f, 4.f, 0.25f, 0.f},
+    {0.f, 1.f, -1.f, 8.f, -0.125f, 1.f},
+};
+__device__ constexpr double W4_G[6][3] = {
+    {1.0, 0.0, 0.0},
+    {-1.0 / 3, -1.0 / 3, -1.0 / 3},
+    {1.0 / 3, -1.0 / 3, 1.0 / 3},
+    {1.0 / 15, 2.0 / 15, 4.0 / 15},
+    {-16.0 / 15, 8.0 / 15, -4.0 / 15},
+    {0.0, 0.0, 1.0},
+};
+
+// ------------------------------------------------------------------------------ transform pass: V4 = B^T d B, U4 = G g G^T
+struct Wino4XArgs {
+    const float* x;
+    float* V;
+    int H, W, C4, C4p;
+    int x_ld, x_off;
+    int th, tw, T, Tpad;
+    int ncg;                 // channel groups of 32 (over C4p): the fastest-running part of blockIdx.x
+    int nxb;                 // blocks of the input transform; the blocks behind them transform the filters
+    const float* w;          // row-major section of the packed weights: [row co][(3 kh + kw) * cinp + ci], rows kpad apart
+    float* U;
+    int cout, cin, coutp, cinp, kpad;
+    long long utotal;        // C4p * coutp * 4: one thread per (ci, co) pair computes all 36 xi
+};
+
+__global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
+    if ((int)blockIdx.x >= p.nxb) {
+        const long long stride = (long long)(gridDim.x - p.nxb) * blockDim.x;
+        for (long long i = (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x; i < p.utotal; i += stride) {
+            const int e = (int)(i & 3);
+            const long long r = i >> 2;
+            const int co = (int)(r % p.coutp), c4 = (int)(r / p.coutp);
+            const int ci = 4 * c4 + e;
+            double g[3][3];
+            const bool ok = co < p.cout && ci < p.cin;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = ok ? (double)p.w[(size_t)co * p.kpad + k * p.cinp + ci] : 0.0;
+            double t[6][3];                                  // G g
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) t[j][q] = W4_G[j][0] * g[0][q] + W4_G[j][1] * g[1][q] + W4_G[j][2] * g[2][q];
+            float* dst = p.U + i;
+            const size_t xs = (size_t)p.C4p * p.coutp * 4;
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+#pragma unroll
+                for (int l = 0; l < 6; ++l)
+                    dst[(6 * j + l) * xs] = (float)(t[j][0] * W4_G[l][0] + t[j][1] * W4_G[l][1] + t[j][2] * W4_G[l][2]);
+        }
+        return;
+    }
+    // 8 lanes = the 8 channel quads of one pixel's 128-byte line, 8 tiles per wave (the access pattern of wino_xform_f32)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cg = blockIdx.x % p.ncg, tb = blockIdx.x / p.ncg;
+    const int c4 = cg * 8 + (lane & 7);
+    const int t = tb * 32 + wave * 8 + (lane >> 3);
+    if (c4 >= p.C4p) return;
+    const bool tv = t < p.T && c4 < p.C4;                // the padding plane c4 = C4 (odd C4) and the padding tiles are zero
+    const int tt = t < p.T ? t : 0;
+    const int per = p.th * p.tw;
+    const int n = tt / per, rem = tt - n * per;
+    const int ty = rem / p.tw, tx = rem - ty * p.tw;
+    const int r0 = 4 * ty - 1, c0 = 4 * tx - 1;
+    const float* base = p.x + p.x_off + 4 * (c4 < p.C4 ? c4 : 0);
+    // v = B^T d B, row by row of d: e = d[k][.] B (6 -> 6), v[i][.] += B^T[i][k] e
+    f32x4 v[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int l = 0; l < 6; ++l) v[i][l] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int r = r0 + k;
+        const bool rv = tv && r >= 0 && r < p.H;
+        f32x4 d[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int c = c0 + j;
+            const bool ok = rv && c >= 0 && c < p.W;
+            const size_t pix = ok ? ((size_t)n * p.H + r) * p.W + c : 0;
+            const f32x4 ld = *reinterpret_cast<const f32x4*>(base + pix * p.x_ld);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            d[j] = ok ? ld : z;
+        }
+        f32x4 e[6];
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+            e[l] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                if (W4_BT[l][j] != 0.f) e[l] += W4_BT[l][j] * d[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+            if (W4_BT[i][k] != 0.f)
+#pragma unroll
+                for (int l = 0; l < 6; ++l) v[i][l] += W4_BT[i][k] * e[l];
+    }
+    float* dst = p.V + ((size_t)c4 * p.Tpad + t) * 4;
+    const size_t xs = (size_t)p.C4p * p.Tpad * 4;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int l = 0; l < 6; ++l) *reinterpret_cast<f32x4*>(dst + (6 * i + l) * xs) = v[i][l];
+}
+
+// ------------------------------------------------------------------------------ 36 GEMMs in six passes + output transform + epilogue
+struct Wino4Args {
+    const float* V;
+    const float* U;
+    const float* scale;
+    const float* shift;
+    const float* res;
+    float* y;
+    int* nan_flag;
+    int T, Tpad, C4p, Cout, CoutPad;
+    int th, tw, H, W;
+    int y_ld, y_off, r_ld, r_off;
+    int flags;
+    int n_mt, n_nt;
+};
+
+constexpr int W4_STAGE = 24576;          // bytes per ring stage: V [2 planes][6 xi][64][4] floats, then U the same
+constexpr int W4_SLOTS = 4;              // (a power of two: slot arithmetic by mask)
+constexpr int W4_DMA = 3;                // DMA wave-instructions per wave and stage
+
+// fragments of one sub-step: the U row (A operand) and the V rows of the wave's two tile blocks (B operands)
+template <int OFF>
+__device__ __forceinline__ void w4_read3(float& a, float& b0, float& b1, unsigned ua, unsigned va) {
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(a) : "v"(ua), "n"(OFF));
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(b0) : "v"(va), "n"(OFF));
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(b1) : "v"(va), "n"(OFF + 256));
+}
+
+// 512 threads = 8 waves, two per SIMD: wave (wm, wn) owns tiles 32 wm .. + 31 and channels 16 wn .. + 15 of the 64 x 64 block, as
+// two 16 x 16 blocks of v_mfma_f32_16x16x4_f32 per xi (D[channel][tile]: a lane holds one tile and 4 consecutive channels)
+template <int ACT, bool RES>
+__global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15, kq = lane >> 4;
+    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+    const int nt = q % p.n_nt, mt = (q / p.n_nt) * 8 + xcd;
+    if (mt >= p.n_mt) return;
+    const int wm = wave & 1, wn = wave >> 1;
+
+    // ---- DMA roles: waves 2 grp, 2 grp + 1 move part grp of a stage (0 / 1: plane 0 / 1 of V, 2 / 3: the same planes of U),
+    // three xi each; lane = row
+    const size_t v_xi = (size_t)p.C4p * p.Tpad * 4, v_c4 = (size_t)p.Tpad * 4;
+    const size_t u_xi = (size_t)p.C4p * p.CoutPad * 4, u_c4 = (size_t)p.CoutPad * 4;
+    const int grp = wave >> 1, x0 = 3 * (wave & 1);
+    const int plane = grp & 1;
+    const char* src = grp < 2 ? reinterpret_cast<const char*>(p.V + plane * v_c4 + (size_t)mt * 256)
+                              : reinterpret_cast<const char*>(p.U + plane * u_c4 + (size_t)nt * 256);
+    const size_t s_xi = (grp < 2 ? v_xi : u_xi) * 4, s_c4 = (grp < 2 ? v_c4 : u_c4) * 4;       // bytes
+    const unsigned lane16 = lane * 16;
+    const unsigned lds0 = (unsigned)(size_t)(wn_lptr)smem;
+    auto issue_piece = [&](int k, int pass, int st, int slot) {
+        const int x = x0 + k;
+        wn_glds16_s(src + (size_t)(6 * pass + x) * s_xi + (size_t)(2 * st) * s_c4, lane16, lds0 + slot * W4_STAGE + (6 * grp + x) * 1024);
+    };
+    auto issue = [&](int pass, int st, int slot) { wn_for<0, W4_DMA>([&](auto K) { issue_piece(decltype(K)::value, pass, st, slot); }); };
+
+    // ---- fragment addresses: sub-step s = 6 plane + x of a stage sits at s KiB in both halves; channel kq of the plane,
+    // rows 32 wm + l16 (+ 16) of V, row 16 wn + l16 of U
+    const unsigned vb = lds0 + (32 * wm + l16) * 16 + kq * 4;
+    const unsigned ub = lds0 + 12288 + (16 * wn + l16) * 16 + kq * 4;
+
+    const int nst = p.C4p / 2;
+    // the partial output tiles: [tile block bb][output row i][output column j] of this lane's tile 32 wm + 16 bb + l16, its
+    // channels 16 wn + 4 kq .. + 3
+    f32x4 py[2][4][4];
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) py[bb][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto run_pass = [&](auto PASS) {
+        constexpr int a = decltype(PASS)::value;
+        float fa[12], fb0[12], fb1[12];
+        if constexpr (a == 0) {              // (the first stages of passes 1 .. 5 are requested before the previous pass's transform)
+            issue(0, 0, 0);
+            if (nst > 1) issue(0, 1, 1);
+            if (nst > 2) issue(0, 2, 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 acc[6][2];
+#pragma unroll
+        for (int x = 0; x < 6; ++x)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) acc[x][bb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int x = 0; x < 6; ++x) asm volatile("" : "+v"(acc[x][0]), "+v"(acc[x][1]));
+        __builtin_amdgcn_sched_barrier(0);
+        if (nst > 2) wn_wait_vmcnt<2 * W4_DMA>();
+        else if (nst > 1) wn_wait_vmcnt<W4_DMA>();
+        else wn_wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        w4_read3<0>(fa[0], fb0[0], fb1[0], ub, vb);
+        w4_read3<1024>(fa[1], fb0[1], fb1[1], ub, vb);
+
+        int slot = 0;
+        for (int st = 0; st < nst; ++st) {
+            const unsigned sb = (unsigned)slot * W4_STAGE;
+            const int ns = (slot + 1) & (W4_SLOTS - 1);
+            const unsigned nb = (unsigned)ns * W4_STAGE;
+            wn_for<0, 12>([&](auto S) {
+                constexpr int s = decltype(S)::value, x = s % 6;
+                if constexpr (s == 10) {
+                    // stage st + 1 has to be in LDS for everybody before its first fragments are read (the only requests younger
+                    // than its pieces are those of stage st + 2); the slot of stage st - 1 is free once everybody is here
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (st + 2 < nst) wn_wait_vmcnt<W4_DMA>();
+                    else wn_wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (s + 2 < 12) w4_read3<(s + 2) * 1024>(fa[s + 2], fb0[s + 2], fb1[s + 2], ub + sb, vb + sb);
+                // reads issued after those of sub-step s and still in flight: s < 10 -> s + 1, s + 2; 10 -> 11; 11 -> the next stage's 0
+                constexpr int after = s < 10 ? 6 : 3;
+                asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(fa[s]), "+v"(fb0[s]), "+v"(fb1[s]) : "n"(after));
+                acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[s], fb0[s], acc[x][0], 0, 0, 0);
+                acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[s], fb1[s], acc[x][1], 0, 0, 0);
+                if constexpr (s < W4_DMA) {
+                    // one piece of stage st + 2 behind each of the first sub-steps: its slot (= stage st - 2's) is free since the
+                    // barrier of stage st - 1; stages 0 .. 2 come from the prologue
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (st >= 1 && st + 2 < nst) issue_piece(s, a, st + 2, (slot + 2) & (W4_SLOTS - 1));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (s >= 10) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    w4_read3<(s - 10) * 1024>(fa[s - 10], fb0[s - 10], fb1[s - 10], ub + nb, vb + nb);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+            slot = ns;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the look-ahead reads of the stage after the last
+        __syncthreads();                                     // everybody is done with the ring: the next pass's first stages / the staging may overwrite it
+        if constexpr (a < 5) {                               // ... and they are requested now: in flight during the transform below
+            issue(a + 1, 0, 0);
+            if (nst > 1) issue(a + 1, 1, 1);
+            if (nst > 2) issue(a + 1, 2, 2);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // row a of M into the output tiles: t[j] = sum_b M[a][b] A^T[j][b], Y[i][j] += A^T[i][a] t[j]
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) {
+            f32x4 mb[6];
+#pragma unroll
+            for (int b = 0; b < 6; ++b) mb[b] = acc[b][bb];
+            f32x4 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                t[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int b = 0; b < 6; ++b)
+                    if (W4_AT[j][b] != 0.f) t[j] += W4_AT[j][b] * mb[b];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (W4_AT[i][a] != 0.f)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) py[bb][i][j] += W4_AT[i][a] * t[j];
+        }
+        // the partial tiles wait out the next pass in the AGPR half of the register file (the accumulators and everything else
+        // of the K loop use the VGPR half: 2 waves per SIMD leave 256 registers per lane in all)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(py[bb][i][j]));
+    };
+    run_pass(std::integral_constant<int, 0>{});
+    run_pass(std::integral_constant<int, 1>{});
+    run_pass(std::integral_constant<int, 2>{});
+    run_pass(std::integral_constant<int, 3>{});
+    run_pass(std::integral_constant<int, 4>{});
+    run_pass(std::integral_constant<int, 5>{});
+
+    // ------------------------------------------------------------------ epilogue through LDS, one output row i of the tiles at a time
+    // ([pixel j][tile][64 + 4] over the idle ring, 16 lanes per pixel row: stores and residual loads are 256-byte runs)
+    constexpr int OLD = 68;
+    float* ost = reinterpret_cast<float*>(smem);
+    int* tab = reinterpret_cast<int*>(smem + 256 * OLD * 4);        // [64] first output pixel of the tile, [64] valid rows << 4 | columns
+    if (tid < 64) {
+        const int t = mt * 64 + tid;
+        const bool tv = t < p.T;
+        const int tt = tv ? t : 0;
+        const int per = p.th * p.tw;
+        const int n = tt / per, rem = tt - n * per;
+        const int ty = rem / p.tw, tx = rem - ty * p.tw;
+        const int nr = p.H - 4 * ty < 4 ? p.H - 4 * ty : 4, nc = p.W - 4 * tx < 4 ? p.W - 4 * tx : 4;
+        tab[tid] = (n * p.H + 4 * ty) * p.W + 4 * tx;
+        tab[64 + tid] = tv ? (nr << 4 | nc) : 0;
+    }
+    // scale / shift of the 4 channels this thread STORES (4 (tid % 16) .. of the block); requested here, not at kernel start:
+    // eight registers less through the K loops
+    const int c16 = tid & 15;
+    const int co_t = nt * 64 + 4 * c16;
+    const bool cv = co_t < p.Cout;
+    const f32x4 sc_t = *reinterpret_cast<const f32x4*>(p.scale + (cv ? co_t : 0));
+    const f32x4 sh_t = *reinterpret_cast<const f32x4*>(p.shift + (cv ? co_t : 0));
+    bool saw_nan = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i > 0) __syncthreads();                                  // the previous row's staging has been read back
+        {
+            float* dst = ost + (32 * wm + l16) * OLD + 16 * wn + 4 * kq;
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(dst + (j * 64 + 16 * bb) * OLD) = py[bb][i][j];
+        }
+        __syncthreads();
+        // this thread's 8 rows of the staged row: pixel j = it / 2 of tile (tid / 16) + 32 (it % 2), channels 4 (tid % 16) ..
+        int pix[8];
+        bool pv[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int tl = (tid >> 4) + 32 * (it & 1), j = it >> 1;
+            const int fl = tab[64 + tl];
+            pv[it] = cv && j < (fl & 15) && i < (fl >> 4);
+            pix[it] = pv[it] ? tab[tl] + i * p.W + j : 0;
+        }
+        f32x4 rr[8];
+        if (RES) {
+#pragma unroll
+            for (int it = 0; it < 8; ++it)
+                rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 va[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it)
+            va[it] = *reinterpret_cast<const f32x4*>(ost + ((it >> 1) * 64 + (tid >> 4) + 32 * (it & 1)) * OLD + 4 * c16);
+        // all eight values first, then the eight predicated stores (inside a predicated block the compiler waits for
+        // everything in flight)
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) va[it][e] = act_c<ACT>(va[it][e] * sc_t[e] + sh_t[e]);
+            if (RES) va[it] += rr[it];
+            saw_nan |= pv[it] & ((va[it][0] != va[it][0]) | (va[it][1] != va[it][1]) | (va[it][2] != va[it][2]) | (va[it][3] != va[it][3]));
+        }
+#pragma unroll
+        for (int it = 0; it < 8; ++it) asm volatile("" : "+v"(va[it]));
+#pragma unroll
+        for (int it = 0; it < 8; ++it)
+            if (pv[it]) *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = va[it];
+    }
+    if ((p.flags & YOLO_FLAG_NANCHECK) && saw_nan) atomicOr(p.nan_flag, 2);
+}
+
+// ------------------------------------------------------------------------------ host side
+static const bool g_wino4_off = getenv("YOLO_NO_WINOGRAD") != nullptr;     // A/B switch: the direct kernels (F(2x2) is off as well)
+
+static long long wino4_tiles(const yolo_conv_desc* d) { return (long long)d->n * ((d->h + 3) / 4) * ((d->w + 3) / 4); }
+
+bool wino4_supported(const yolo_conv_desc* d) {
+    if (!wino_supported(d)) return false;
+    const long long T = wino4_tiles(d);
+    if (T + 64 > 0x7fffffffLL / 4) return false;
+    const long long C4p = (d->cin / 4 + 1) / 2 * 2, ncg = (C4p + 7) / 8;
+    return (T + 63) / 32 * ncg + 1024 <= 0x7fffffffLL;                  // the transform pass's one-dimensional grid
+}
+
+// Looks at the layer's shape only, never at the batch size. Measured at batch 32 (tools/conv_bench.py --tile 13,14,15):
+// F(4x4) 252 / 222 / 196 us against F(2x2)'s best 415 / 330 / 270 at 104 x 104, 52 x 52, 26 x 26 (which pads to 28 x 28: 16 % of
+// the tiles' pixels wasted), 351 against 297 at 13 x 13 (padded to 16 x 16: 51 % wasted). So: maps of at least 26 x 26 pixels whose
+// padding to whole 4 x 4 tiles adds at most a fifth.
+bool wino4_eligible(const yolo_conv_desc* d) {
+    if (g_wino4_off || !wino_eligible(d) || !wino4_supported(d)) return false;
+    const long long area = (long long)d->h * d->w, padded = 16LL * ((d->h + 3) / 4) * ((d->w + 3) / 4);
+    return area >= 26 * 26 && 5 * padded <= 6 * area;
+}
+
+size_t wino4_workspace_bytes(const yolo_conv_desc* d) {
+    if (!wino4_supported(d)) return 0;
+    const size_t C4p = (size_t)(d->cin / 4 + 1) / 2 * 2;
+    const size_t Tpad = (size_t)(wino4_tiles(d) + 63) / 64 * 64;
+    const size_t CoutPad = (size_t)round_up(d->cout, 64);
+    return 36 * C4p * (Tpad + CoutPad) * 4 * sizeof(float);
+}
+
+// w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad)
+int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* scale, const float* shift,
+                      const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
+    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4): needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    const size_t need = wino4_workspace_bytes(d);
+    if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4): workspace %zu < %zu bytes", workspace_bytes, need);
+    if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4): workspace must be 16-byte aligned");
+    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
+    const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4, C4p = round_up(C4, 2);
+    const int CoutPad = round_up(d->cout, 64);
+    float* V = (float*)workspace;
+    float* U = V + (size_t)36 * C4p * Tpad * 4;
+    Wino4XArgs xa;
+    xa.x = (const float*)x; xa.V = V; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.C4p = C4p; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
+    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = ceil_div(C4p, 8);
+    xa.nxb = (Tpad / 32) * xa.ncg;
+    xa.w = w_rm; xa.U = U; xa.cout = d->cout; xa.cin = d->cin; xa.coutp = CoutPad; xa.cinp = cin_pad_of(d->cin); xa.kpad = kpad_of(d->cin, 3);
+    xa.utotal = (long long)C4p * CoutPad * 4;
+    const long long ub = (xa.utotal + 255) / 256;
+    const int nub = (int)(ub < 1024 ? ub : 1024);
+    hipLaunchKernelGGL(wino4_xform_f32, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
+    if (int rc = check_launch("wino4_xform_f32")) return rc;
+
+    Wino4Args a;
+    a.V = V; a.U = U; a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y;
+    a.nan_flag = nan_flag;
+    a.T = T; a.Tpad = Tpad; a.C4p = C4p; a.Cout = d->cout; a.CoutPad = CoutPad;
+    a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
+    a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
+    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64;
+    const int grid = 8 * a.n_nt * ceil_div(a.n_mt, 8);
+    const bool res = d->flags & YOLO_FLAG_RESIDUAL;
+    const size_t lds = (size_t)W4_SLOTS * W4_STAGE;                  // (> the epilogue's staging, 256 x 68 x 4 + 512)
+    auto go = [&](auto kern) -> int {
+        static LdsOnce once;
+        if (int rc = reserve_lds(once, reinterpret_cast<const void*>(kern), lds, "conv_wino4_f32")) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
+        return check_launch("conv_wino4_f32");
+    };
+    YOLO_SWITCH_ACT(d->act, return res ? go(&conv_wino4_f32<ACT, true>) : go(&conv_wino4_f32<ACT, false>));
+    return fail(YOLO_ERR_ARG, "conv winograd F(4x4): activation");
+}
+
+}  // namespace yolo

@@ -39,40 +39,9 @@
 // Arithmetic: an f32 MFMA chain is a k-ordered fmaf chain per xi; results differ from the direct kernel's by the
 // transforms' roundings only. An image's result does not depend on its batch (tiles are independent, the choice of
 // kernel looks at cin / h / w only).
-#include <type_traits>
-#include "common.h"
+#include "wino_dma.h"
 
 namespace yolo {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-typedef const __attribute__((address_space(1))) void* wn_gptr;
-typedef __attribute__((address_space(3))) void* wn_lptr;
-__device__ __forceinline__ void wn_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((wn_gptr)g, (wn_lptr)l, 16, 0, 0); }
-// the same request with the source as wave-uniform base (SGPR pair) + 32-bit lane offset, the LDS destination (wave-uniform byte
-// address) through M0. Written out because inside the stage loop the compiler's strength reduction turns base + offset back
-// into one 64-bit vector add per request.
-__device__ __forceinline__ void wn_glds16_s(const void* base_uniform, unsigned lane_off, unsigned lds_addr_uniform) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(lane_off), "s"(base_uniform), "s"(lds_addr_uniform) : "memory");      // (M0 is written here; the compiler re-loads it before every use of its own)
-}
-template <int N> __device__ __forceinline__ void wn_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// fragments of one xi: the U row (A operand) and the V row (B operand), channels 2h and 2h + 1 of the stage
-template <int OFF>
-__device__ __forceinline__ void wn_read2(f32x2& a, f32x2& b, unsigned ua, unsigned va) {
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=&v"(a) : "v"(ua), "n"(OFF));
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=&v"(b) : "v"(va), "n"(OFF));
-}
-
-template <int I, int N, class Fn>
-__device__ __forceinline__ void wn_for(Fn&& fn) {
-    if constexpr (I < N) {
-        fn(std::integral_constant<int, I>{});
-        wn_for<I + 1, N>(fn);
-    }
-}
 
 // ------------------------------------------------------------------------------ weights: U = G g G^T
 // G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
@@ -114,6 +83,7 @@ struct WinoXArgs {
     int H, W, C4;
     int x_ld, x_off;
     int th, tw, T, Tpad;
+    int ncg;                         // channel groups of 32 = the fastest-running part of blockIdx.x
 };
 
 // B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
@@ -122,8 +92,11 @@ __global__ __launch_bounds__(256) void wino_xform_f32(const WinoXArgs p) {
     // lines (16 bytes per lane from 64 different pixels - one tile per lane - measured 66 us at 52 x 52 for 221 MB), every
     // store instruction writes 8 runs of 128 bytes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c4 = blockIdx.x * 8 + (lane & 7);
-    const int t = blockIdx.y * 32 + wave * 8 + (lane >> 3);
+    // one grid dimension (blockIdx.x = tile block * ncg + channel group, the order of the former 2-D grid): grid.y would cap
+    // the tile count at 65,535 blocks of 32
+    const int cg = blockIdx.x % p.ncg, tb = blockIdx.x / p.ncg;
+    const int c4 = cg * 8 + (lane & 7);
+    const int t = tb * 32 + wave * 8 + (lane >> 3);
     if (c4 >= p.C4) return;
     const bool tv = t < p.T;
     const int tt = tv ? t : 0;
@@ -736,6 +709,7 @@ bool wino_supported(const yolo_conv_desc* d) {
     if ((d->flags & YOLO_FLAG_RESIDUAL) && ((d->r_ld & 3) || (d->r_off & 3))) return false;
     const long long T = (long long)d->n * ((d->h + 1) / 2) * ((d->w + 1) / 2);
     if (T + 64 > 0x7fffffffLL / 4 || (long long)d->n * d->h * d->w > 0x7fffffffLL) return false;
+    if ((T + 63) / 32 * ((d->cin / 4 + 7) / 8) > 0x7fffffffLL) return false;        // the transform pass's one-dimensional grid
     return true;
 }
 
@@ -765,8 +739,8 @@ int conv_wino_launch(const yolo_conv_desc* d, const void* x, const float* U, con
     const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4;
     WinoXArgs xa;
     xa.x = (const float*)x; xa.V = (float*)workspace; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
-    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad;
-    hipLaunchKernelGGL(wino_xform_f32, dim3(ceil_div(C4, 8), Tpad / 32), dim3(256), 0, s, xa);
+    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = ceil_div(C4, 8);
+    hipLaunchKernelGGL(wino_xform_f32, dim3((unsigned)(Tpad / 32) * xa.ncg), dim3(256), 0, s, xa);
     if (int rc = check_launch("wino_xform_f32")) return rc;
 
     WinoArgs a;
