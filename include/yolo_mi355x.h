@@ -357,6 +357,19 @@ int yolo_sgd_step(const void* items_dev, const int32_t* chunks_dev, int n_chunks
  * responsibility here: the values are not on the host). */
 int yolo_sgd_step_hp(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, int nesterov, int maximize,
                      void* stream);
+/* fp16 loss scaling without a host wait (torch.amp.GradScaler, train.py:39,67-69).
+ * yolo_sgd_check_finite: one launch over the same tables; *found_inf_dev (float) becomes 1.0f when any gradient holds an inf
+ * or a NaN (exponent bits all ones). clear != 0: a one-thread launch sets the word to 0.0f first (stream-ordered,
+ * capturable); clear == 0 adds to what an earlier call (another parameter group) found. Nothing else is written.
+ * yolo_sgd_step_amp: the update of yolo_sgd_step_hp with g * (float)(1.0 / (double)*grad_scale_dev) in front of it as a
+ * rounding of its own (grad_scale_dev == NULL, or a scale of 1: no unscale); the gradient is not written back.
+ * *found_inf_dev != 0: nothing is touched. "First step" is a device fact here: written_dev[i] == 0 means item i's momentum
+ * buffer was never written (buf = g + wd * p); a second small launch sets it to 1 for every item with a gradient after a
+ * step that was applied. n of an item may be given with either sign. */
+int yolo_sgd_check_finite(const void* items_dev, const int32_t* chunks_dev, int n_chunks, float* found_inf_dev, int clear, void* stream);
+int yolo_sgd_step_amp(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                      const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, int nesterov, int maximize,
+                      void* stream);
 
 /* ---- post-processing ------------------------------------------------------------------- */
 /* Replaces cells_to_boxes (utils.py:86-148) for one scale.

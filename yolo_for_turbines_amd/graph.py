@@ -24,12 +24,28 @@ class GraphedTrainStep:
     the warm-up steps on a side stream (so they DO update the model, like three ordinary steps). ``autocast_dtype``
     (``torch.bfloat16`` / ``torch.float16`` / None) selects what `train.py:53` selects. Returns the summed loss as a
     0-dim tensor that is overwritten by the next call.
+
+    ``grad_scaler`` (a :class:`yolo_for_turbines_amd.GradScaler`, with a :class:`yolo_for_turbines_amd.SGD`): the step is
+    `train.py:67-69`, ``scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update()``, all of it captured - the
+    scale, the growth tracker and the skip decision are device memory read at replay time, so a replay whose gradients
+    overflow skips its update and halves the scale like an eager step. The warm-up steps go through the scaler too. The
+    returned loss is the unscaled one; ``grad_scaler.get_scale()`` reads the live value (and waits for the device).
     """
 
     def __init__(self, model, optimizer, scaled_anchors, x, targets, autocast_dtype=None, loss_fn=None, warmup=3,
-                 zero_grad=True, allow_data_parallel=None):
+                 zero_grad=True, allow_data_parallel=None, grad_scaler=None):
         if not x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors (no CPU fallback)")
+        if grad_scaler is not None:
+            from .amp import GradScaler
+            from .optim import SGD
+            if not isinstance(grad_scaler, GradScaler) or not isinstance(optimizer, SGD):
+                raise TypeError("GraphedTrainStep: grad_scaler must be a yolo_for_turbines_amd.GradScaler stepping a "
+                                "yolo_for_turbines_amd.SGD (torch.amp.GradScaler.step reads its inf flag on the host, which "
+                                "cannot be captured)")
+            if not grad_scaler.is_enabled():
+                raise ValueError("GraphedTrainStep: grad_scaler is disabled; pass grad_scaler=None instead")
+        self.scaler = grad_scaler
         if allow_data_parallel is None:
             allow_data_parallel = os.environ.get("YOLO_DP_GRAPH", "0") == "1"
         self._dp = getattr(model._engine, "ddp", None) is not None and model._engine.ddp[0] is not None
@@ -84,8 +100,13 @@ class GraphedTrainStep:
         with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
             preds = self.model(self.x)
             loss = sum(sum(self.loss_fn(preds[i], self.targets[i], self.anchors[i])) for i in range(3))
-        loss.backward()
-        self.opt.step()
+        if self.scaler is not None:
+            self.scaler.scale(loss).backward()
+            self.scaler.step(self.opt)
+            self.scaler.update()
+        else:
+            loss.backward()
+            self.opt.step()
         return loss.detach()
 
     def _hyper_snapshot(self):

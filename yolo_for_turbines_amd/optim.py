@@ -5,6 +5,11 @@ Drop-in for `torch.optim.SGD` as the reference constructs it (`code/train.py:171
 same `state` / `state_dict()` layout (`momentum_buffer` per parameter, so `utils.py:383-416` checkpoints load
 either way), same bits after every step. Only fp32 parameters on the GPU (what the model holds); anything
 else raises instead of falling back.
+
+Under a loss scale (`yolo_for_turbines_amd.GradScaler`, or anything that sets the two tensor attributes PyTorch's fused
+optimizers use, `optimizer.grad_scale` and `optimizer.found_inf`) the step unscales in registers and is skipped on the device
+when `found_inf` is set: no host wait, capturable. Whether a momentum buffer has been written yet is then a device fact
+(a skipped first step leaves it unwritten), kept as one int32 word per parameter next to the tables.
 """
 import torch
 
@@ -43,6 +48,13 @@ class _GroupTable:
         self.hyper_host = None                              # the values last pushed
         self.hyper_ring = [[torch.zeros(4, dtype=torch.float32).pin_memory(), None] for _ in range(4)]
         self.hyper_slot = 0
+        # loss-scaled steps: written[i] != 0 once parameter i's momentum buffer holds a value (set on the device after an
+        # applied step; SGD._table fills it in for buffers the host knows about). device_first: some buffer of this group was
+        # allocated by a loss-scaled step, so only the device knows whether it was written - every later step of the group
+        # then goes through the kernel that reads the words.
+        self.written = torch.zeros(len(params), dtype=torch.int32, device=dev)
+        self.device_first = False
+        self.no_inf = torch.zeros(1, dtype=torch.float32, device=dev)
 
     def _pinned(self):
         return torch.zeros((len(self.params), 4), dtype=torch.int64).pin_memory()
@@ -94,12 +106,62 @@ class SGD(torch.optim.SGD):
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                          maximize=maximize)
         self._tables = {}                                   # group index -> _GroupTable
+        self._word = {}                                     # parameter -> its 1-element view of a table's `written`
 
     def _table(self, gi, params):
         t = self._tables.get(gi)
         if t is None or not t.matches(params):
+            old = t
             t = self._tables[gi] = _GroupTable(params)
+            # A buffer this optimizer has no word for came from a plain step or from load_state_dict: it is written. One the
+            # device decides about (allocated by a loss-scaled step) keeps its word across a rebuild of the table.
+            known = [int(p not in self._word and self.state.get(p, {}).get("momentum_buffer") is not None) for p in params]
+            t.written.copy_(torch.tensor(known, dtype=torch.int32))
+            for i, p in enumerate(params):
+                if p in self._word:
+                    t.written[i:i + 1].copy_(self._word[p])
+                self._word[p] = t.written[i:i + 1]
+            t.device_first = old is not None and old.device_first
         return t
+
+    def _unwritten(self):
+        """Parameters whose momentum buffer exists but has never been written (every loss-scaled step so far was skipped).
+        Reads device memory, so it waits for the device: for checkpointing, not for the step."""
+        out = set()
+        for tab in self._tables.values():
+            if tab.device_first:
+                w = tab.written.cpu()
+                out.update(p for i, p in enumerate(tab.params) if not int(w[i]) and "momentum_buffer" in self.state.get(p, {}))
+        return out
+
+    def state_dict(self):
+        """`torch.optim.SGD.state_dict()`; a momentum buffer that was allocated but never written (the steps so far were all
+        skipped by the loss scaler) is left out, which is PyTorch's meaning of "no buffer yet"."""
+        sd = super().state_dict()
+        skip = self._unwritten()
+        if skip:
+            index, n = {}, 0
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if id(p) not in index:
+                        index[id(p)] = n
+                        n += 1
+            for p in skip:
+                entry = {k: v for k, v in sd["state"][index[id(p)]].items() if k != "momentum_buffer"}
+                if entry:
+                    sd["state"][index[id(p)]] = entry
+                else:
+                    del sd["state"][index[id(p)]]
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        # the "written" word of every parameter follows from whether a buffer came with the checkpoint (the tables stay: their
+        # device memory may be part of a captured graph)
+        for tab in self._tables.values():
+            known = [int(self.state.get(p, {}).get("momentum_buffer") is not None) for p in tab.params]
+            tab.written.copy_(torch.tensor(known, dtype=torch.int32))
+            tab.device_first = False
 
     @staticmethod
     def _hyper_of(group):
@@ -117,65 +179,111 @@ class SGD(torch.optim.SGD):
             if tab is not None:
                 tab.push_hyper(self._hyper_of(group))
 
+    def _prepare(self, gi, group, scaled):
+        """Fill and (if it changed) upload the row table of one group for the gradients as they are now. Returns
+        (table, indices of momentum buffers the host marked new)."""
+        tab = self._table(gi, group["params"])
+        mom = float(group["momentum"])
+        capturing = torch.cuda.is_current_stream_capturing()
+        hyper = self._hyper_of(group)
+        if capturing and tab.hyper_host is None:
+            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing")
+        if not capturing or hyper != tab.hyper_host:      # inside a capture an unchanged value needs no node at all
+            tab.push_hyper(hyper)
+        scaled = scaled or tab.device_first
+        host, slot = tab.host_buffer(capturing)
+        rows = host.numpy()                              # [p, g, momentum buffer, n] per parameter (yolo_sgd_item)
+        updated, fresh = [], []
+        for i, p in enumerate(tab.params):
+            g = p.grad
+            if g is None:
+                rows[i, 1] = 0                           # skipped by the kernel, like PyTorch
+                continue
+            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
+                raise TypeError("yolo_for_turbines_amd.optim.SGD: gradients must be dense contiguous fp32 on the parameter's GPU")
+            n = p.numel()
+            rows[i, 0] = p.data_ptr()
+            rows[i, 1] = g.data_ptr()
+            if mom != 0.0:
+                st = self.state[p]
+                buf = st.get("momentum_buffer")
+                if buf is None:
+                    if capturing:
+                        raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing (the first step "
+                                           "initialises the momentum buffers)")
+                    if scaled:                           # whether this step writes it is decided on the device
+                        buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                        tab.device_first = True
+                    else:
+                        buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                        n = -n                           # first step: the kernel writes buf = g + wd * p
+                        fresh.append(i)
+                rows[i, 2] = buf.data_ptr()
+            else:
+                rows[i, 2] = p.data_ptr()                # never touched
+            rows[i, 3] = n
+            updated.append(p)
+        # the kernel writes through raw pointers: tell PyTorch's version counters (the engine re-packs a weight when its
+        # version moves - without this the forward would keep using the weights of step 0)
+        torch.autograd.graph.increment_version(updated)
+        # With gradient buckets / a captured graph every address is the same step after step: upload the table only when it
+        # differs from the one the device already holds (an H2D copy costs the GPU ~85 us of idle queue in front of it)
+        same = (not capturing) and tab.uploaded is not None and bool((rows == tab.uploaded).all())
+        if not same:
+            tab.items.copy_(host, non_blocking=True)
+            tab.uploaded = None if capturing else rows.copy()
+            if slot is not None:
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+        return tab, fresh
+
+    @staticmethod
+    def _flag(t, dev, what):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.numel() == 1):
+            raise TypeError(f"yolo_for_turbines_amd.optim.SGD: {what} must be a one-element fp32 tensor on the parameters' GPU")
+        return t
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, check_into=None):
+        """One launch per parameter group. With the tensor attributes ``self.grad_scale`` / ``self.found_inf`` set (what
+        ``GradScaler.step`` hands PyTorch's fused optimizers) the gradients are unscaled in registers (``p.grad`` keeps the
+        scaled values) and nothing is touched when ``found_inf`` is non-zero; without them nothing changes. ``check_into``
+        (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         lib = L.lib()
-        for gi, group in enumerate(self.param_groups):
-            params = group["params"]
-            if not params:
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        scaled = grad_scale is not None or found_inf is not None
+        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
+        ready = [(g,) + self._prepare(gi, g, scaled) for gi, g in groups]
+        if check_into is not None:                           # every group is checked before any group is stepped
+            self._check(ready, check_into)
+        for group, tab, fresh in ready:
+            dev = tab.hyper.device
+            nest, maxi = int(bool(group["nesterov"])), int(bool(group["maximize"]))
+            if scaled or tab.device_first:
+                flag = self._flag(found_inf, dev, "found_inf")
+                L.check(lib.yolo_sgd_step_amp(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0],
+                                              tab.hyper.data_ptr(), L.ptr(self._flag(grad_scale, dev, "grad_scale")),
+                                              (flag if flag is not None else tab.no_inf).data_ptr(), tab.written.data_ptr(), nest, maxi,
+                                              L.current_stream()), "yolo_sgd_step_amp")
                 continue
-            tab = self._table(gi, params)
-            mom = float(group["momentum"])
-            capturing = torch.cuda.is_current_stream_capturing()
-            hyper = self._hyper_of(group)
-            if capturing and tab.hyper_host is None:
-                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing")
-            if not capturing or hyper != tab.hyper_host:      # inside a capture an unchanged value needs no node at all
-                tab.push_hyper(hyper)
-            host, slot = tab.host_buffer(capturing)
-            rows = host.numpy()                              # [p, g, momentum buffer, n] per parameter (yolo_sgd_item)
-            updated = []
-            for i, p in enumerate(tab.params):
-                g = p.grad
-                if g is None:
-                    rows[i, 1] = 0                           # skipped by the kernel, like PyTorch
-                    continue
-                if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
-                    raise TypeError("yolo_for_turbines_amd.optim.SGD: gradients must be dense contiguous fp32 on the parameter's GPU")
-                n = p.numel()
-                rows[i, 0] = p.data_ptr()
-                rows[i, 1] = g.data_ptr()
-                if mom != 0.0:
-                    st = self.state[p]
-                    buf = st.get("momentum_buffer")
-                    if buf is None:
-                        if capturing:
-                            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing (the first step "
-                                               "initialises the momentum buffers)")
-                        buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
-                        n = -n                               # first step: the kernel writes buf = g + wd * p
-                    rows[i, 2] = buf.data_ptr()
-                else:
-                    rows[i, 2] = p.data_ptr()                # never touched
-                rows[i, 3] = n
-                updated.append(p)
-            # the kernel writes through raw pointers: tell PyTorch's version counters (the engine re-packs a weight when its
-            # version moves - without this the forward would keep using the weights of step 0)
-            torch.autograd.graph.increment_version(updated)
-            # With gradient buckets / a captured graph every address is the same step after step: upload the table only when it
-            # differs from the one the device already holds (an H2D copy costs the GPU ~85 us of idle queue in front of it)
-            same = (not capturing) and tab.uploaded is not None and bool((rows == tab.uploaded).all())
-            if not same:
-                tab.items.copy_(host, non_blocking=True)
-                tab.uploaded = None if capturing else rows.copy()
-                if slot is not None:
-                    slot[1] = torch.cuda.Event()
-                    slot[1].record()
             L.check(lib.yolo_sgd_step_hp(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(),
-                                         int(bool(group["nesterov"])), int(bool(group["maximize"])), L.current_stream()),
-                    "yolo_sgd_step_hp")
+                                         nest, maxi, L.current_stream()), "yolo_sgd_step_hp")
+            if len(fresh) == len(tab.params):                # the host marked these buffers new and this step wrote them
+                tab.written.fill_(1)
+            else:
+                for i in fresh:
+                    tab.written[i:i + 1].fill_(1)
         return loss
+
+    def _check(self, ready, found_inf):
+        lib = L.lib()
+        if not ready:
+            found_inf.zero_()
+        for k, (_, tab, _) in enumerate(ready):
+            L.check(lib.yolo_sgd_check_finite(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0],
+                                              self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
+                                              L.current_stream()), "yolo_sgd_check_finite")
