@@ -3,7 +3,7 @@
 processes and devices differ by ~10 %): every round times each variant once (reps launches), rounds alternate the order;
 prints median and min per variant.
 
-  python tools/conv_ab.py --dtype bf16 --layer c52_3x3 --tiles 6,8,9 [--residual] [--rounds 7] [--reps 10]
+  python tools/conv_ab.py --dtype bf16 --layer c52_3x3 --tiles 6,8,10 [--residual] [--rounds 7] [--reps 10]
 """
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

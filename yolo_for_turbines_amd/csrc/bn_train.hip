@@ -194,7 +194,7 @@ __global__ void bn_stats_finalize(const double* __restrict__ partial, int nblk, 
     }
 }
 
-// The same finalize from the per-wave partial sums a convolution's epilogue wrote (conv_h16.hip: d_epilogue_stats):
+// The same finalize from the per-wave partial sums a convolution's epilogue wrote (h16_dma_epilogue.h: d_epilogue_stats):
 // partial[row][2][ld] fp32, row = a wave's 64 pixels; fp64 across rows in a fixed order (lane l adds rows l, l + 64, ...,
 // then the lanes in order), i.e. deterministic like the path above.
 __global__ void bn_stats_finalize_rows(const float* __restrict__ partial, int nrows, int ld, int m, int c, float momentum, float eps,
@@ -427,7 +427,7 @@ __global__ void bn_bwd_finalize(const double* __restrict__ partial, int nblk, in
     coef[2 * c + ch] = (float)(q / m);                  // mean(du * zhat)
 }
 
-// The same from the per-wave sums an input-gradient convolution's epilogue wrote (conv_h16.hip: d_epilogue_bstats):
+// The same from the per-wave sums an input-gradient convolution's epilogue wrote (h16_dma_epilogue.h: d_epilogue_bstats):
 // partial[row][2][ld] fp32 = sum(du), sum(du * (z - mean)); fp64 across rows in the fixed order of bn_stats_finalize_rows.
 __global__ void bn_bwd_finalize_rows(const float* __restrict__ partial, int nrows, int ld, int m, int c, const float* __restrict__ gamma,
                                      const float* __restrict__ invstd, float* __restrict__ dgamma, float* __restrict__ dbeta,

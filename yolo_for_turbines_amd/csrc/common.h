@@ -185,6 +185,11 @@ template <> struct Vec16<_Float16> {
     default: return fail(YOLO_ERR_ARG, "%s: unknown dtype %d", what, (int)(dtype));       \
     }
 
+// run `body` with T bound to __bf16 or _Float16, the 16-bit element type of `dtype` (for callers that have no fp32 case)
+#define YOLO_SWITCH_H16(dtype, ...)                                                       \
+    if ((dtype) == YOLO_BF16) { typedef __bf16 T; __VA_ARGS__; }                          \
+    else { typedef _Float16 T; __VA_ARGS__; }
+
 // conv_f32_v2.hip ("patch + fragment stream" kernel, stride 1, cin % 32 == 0)
 bool v2_eligible(const yolo_conv_desc* d);
 size_t v2_frag_elems(int cout, int cin, int ks);
@@ -213,7 +218,7 @@ bool wino4_eligible(const yolo_conv_desc* d);
 size_t wino4_workspace_bytes(const yolo_conv_desc* d);
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
-// conv_h16.hip (bf16 / fp16 patch kernel)
+// pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)
 size_t h16_frag_elems(int cout, int cin, int ks);
 int h16_pack(const float* w_oihw, void* wf, int cout, int cin, int ks, int dtype, hipStream_t s);
 int h16_pack_dgrad(const float* w_oihw, void* wf, int cout, int cin, int ks, int dtype, hipStream_t s);
@@ -221,6 +226,8 @@ int h16_pack_batch(const float* const* w, void* const* wf, const int* cout, cons
                    hipStream_t s);
 size_t h16_dgrad_s2_elems(int cout, int cin);
 int h16_pack_dgrad_s2(const float* w_oihw, void* wf, int cout, int cin, int dtype, hipStream_t s);
+// conv_h16.hip (host side of the bf16 / fp16 convolutions; the kernels are in conv_patch_h16.hip, conv3_dma_h16.hip,
+// conv1_dma_h16.hip and conv3_ws_h16.hip, what they share in h16.h)
 int dgrad_s2_h16_launch(const void* dz, int dz_ld, int dz_off, const void* wf, const void* residual, int r_ld, int r_off, void* dx,
                         int dx_ld, int dx_off, int n, int ho, int wo, int cin, int cout, int dtype, hipStream_t s);
 int conv_h16_launch(const yolo_conv_desc* d, const void* x, const void* wf, const float* scale, const float* shift,
@@ -235,7 +242,7 @@ struct ConvBStats { const void* z; int z_ld, z_off; const float* mean; const flo
 int conv_h16_launch_stats(const yolo_conv_desc* d, const void* x, const void* wf, const float* scale, const float* shift,
                           const void* residual, void* y, int32_t* nan_flag, float* stats, int* rows_ld, const size_t* stats_bytes,
                           hipStream_t s, const ConvBStats* bs);
-// the first block (3 -> 32 channels, 3x3) with a 16-bit output on the matrix cores; same arguments as yolo_stem_fwd
+// stem_h16.hip: the first block (3 -> 32 channels, 3x3) with a 16-bit output on the matrix cores; same arguments as yolo_stem_fwd
 int stem_h16_launch(const float* x, const float* wt, const float* scale, const float* shift, void* y, int n, int h, int w, int y_ld,
                     int y_off, int act, int dtype, int* nan_flag, hipStream_t s);
 // wgrad_h16.hip (bf16 / fp16 weight gradient, transposing LDS reads)

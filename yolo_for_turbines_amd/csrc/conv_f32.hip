@@ -270,7 +270,7 @@ constexpr int kNumTiles = 10;     // 1-4: register-staged tiles above; 5/6: conv
 constexpr int kTileRs = 12;       // conv1_rs_f32.hip (fp32 1x1, weights in registers)
 constexpr int kTileWino = 13;     // conv_wino_f32.hip (fp32 3x3 stride 1, Winograd F(2x2, 3x3); needs the caller's workspace)
 constexpr int kTileWino4 = 15;    // conv_wino4_f32.hip (fp32 3x3 stride 1, Winograd F(4x4, 3x3); needs the caller's workspace)
-constexpr int kMaxTileId = 31;    // ids above kNumTiles select timing probes of the diagnostic library (make probes); the product library runs tile 8 for them
+constexpr int kMaxTileId = 31;    // ids above kNumTiles: the named ones above; 16 + bits = timing probes of the fp32 Winograd diagnostic library (make wstamps)
 
 static size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * LDS_LD * sizeof(float); }
 

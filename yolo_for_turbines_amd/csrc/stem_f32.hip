@@ -22,7 +22,7 @@ __device__ __forceinline__ unsigned short stem_cvt(float f, int dtype) {
     return *reinterpret_cast<unsigned short*>(&h);
 }
 
-// DT: YOLO_F32 writes fp32; YOLO_F16 / YOLO_BF16 write 16-bit activations for conv_h16.hip
+// DT: YOLO_F32 writes fp32; YOLO_F16 / YOLO_BF16 write 16-bit activations for the 16-bit convolutions (h16.h)
 template <int COUT>
 __global__ __launch_bounds__(256) void stem3x3_f32(const float* __restrict__ x, const float* __restrict__ wt,
                                                    const float* __restrict__ scale, const float* __restrict__ shift,
@@ -179,7 +179,7 @@ int yolo_stem_fwd(const float* x_nchw, const float* w_k_major, const float* scal
         return fail(YOLO_ERR_UNSUPPORTED, "stem: only 3 -> 32 channels, y_ld/y_off multiples of 16 bytes");
     const long long total = (long long)n * h * w;
     if (total > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "stem: too many pixels");
-    // 16-bit output: the matrix-core kernel of conv_h16.hip (input and weights rounded to the 16-bit type, as autocast does)
+    // 16-bit output: the matrix-core kernel of stem_h16.hip (input and weights rounded to the 16-bit type, as autocast does)
     static const bool valu_stem = getenv("YOLO_STEM_VALU") != nullptr;      // A/B switch: keep the vector kernel
     if (dtype != YOLO_F32 && !valu_stem)
         return stem_h16_launch(x_nchw, w_k_major, scale, shift, y, n, h, w, y_ld, y_off, act, dtype, nan_flag, (hipStream_t)stream);
