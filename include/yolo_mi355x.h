@@ -58,7 +58,7 @@ typedef struct yolo_conv_desc {
     int32_t dtype;          /* YOLO_F32, YOLO_F16 or YOLO_BF16: activations (x, residual, y) and   */
                             /* packed weights; accumulation, scale/shift and heads stay fp32       */
     int32_t flags;          /* YOLO_FLAG_*                                                 */
-    int32_t tile;           /* 0 = library heuristic; else forced tile id (tuning/tests)   */
+    int32_t tile;           /* 0 = library heuristic; else forced tile id 1 .. 15 (tuning/tests) */
 } yolo_conv_desc;
 
 /* One queued launch for yolo_conv_fwd_batch (pointers as 64-bit integers so the table can be
@@ -71,6 +71,10 @@ typedef struct yolo_conv_op {
 
 const char* yolo_last_error(void);
 int yolo_version(void);
+/* The A/B environment switches (INTEGRATION.md has the table) are read once, when the library is loaded. This writes what was
+ * read as "NAME=value\n" per switch, in the table's order (a boolean is 0 / 1 in the sense of its name: YOLO_NO_DMA=1 means the
+ * DMA kernels are off), at most cap - 1 characters and a terminating 0; returns the length the whole text needs. */
+int yolo_switches_describe(char* buf, size_t cap);
 
 /* ---- weights (replaces nothing arithmetic: layout change of nn.Conv2d.weight, OIHW fp32,
  *      as filled by the Darknet loader model.py:293-305) ---------------------------------- */

@@ -191,3 +191,68 @@ def test_checkpoint_format_matches_reference(golden, tmp_path):
         assert k == k2 and torch.equal(a, b), k
     for pa, pb in zip(m.parameters(), m2.parameters()):
         assert torch.equal(opt.state[pa]["momentum_buffer"], opt2.state[pb]["momentum_buffer"])
+
+
+# ---- the A/B environment switches: one row per switch, in the order yolo_switches_describe prints them
+PRESENCE_SWITCHES = ("YOLO_NO_DMA", "YOLO_NO_S2_DMA", "YOLO_NO_S2G", "YOLO_NO_STAGGER", "YOLO_NO_WINOGRAD", "YOLO_NO_CONV3_WS",
+                     "YOLO_NO_CONV1_RS", "YOLO_NO_WGRAD_DMA", "YOLO_NO_STEM_WGRAD", "YOLO_STEM_VALU", "YOLO_NMS_ROCPRIM")
+PRIO_SWITCHES = ("YOLO_F32_PRIO", "YOLO_DMA_PRIO")
+INT_SWITCHES = {"YOLO_WGRAD_LA": 3, "YOLO_WGRAD_PRIO": 0, "YOLO_STEM_WGRAD_BLOCKS": 256, "YOLO_WINO2_MAXPIX": 256}
+ALL_SWITCHES = PRESENCE_SWITCHES + PRIO_SWITCHES + tuple(INT_SWITCHES)
+
+# The switches are read once per process, so every case is a fresh child. It loads the library alone (no torch, no package
+# import: about a second), prints yolo_switches_describe and then what the fp32 routing says about one 3x3 stride-1 layer
+# (128 -> 256 channels at 52 x 52, NHWC, tile 0).
+_SWITCH_CHILD = r"""
+import ctypes as C, sys
+lib = C.CDLL(sys.argv[1])
+lib.yolo_switches_describe.restype, lib.yolo_switches_describe.argtypes = C.c_int, [C.c_char_p, C.c_size_t]
+need = lib.yolo_switches_describe(None, 0)
+buf = C.create_string_buffer(need + 1)
+assert lib.yolo_switches_describe(buf, need + 1) == need and len(buf.value) == need
+short = C.create_string_buffer(8)
+assert lib.yolo_switches_describe(short, 8) == need and short.value == buf.value[:7]
+sys.stdout.write(buf.value.decode())
+#            n  h   w   cin  cout k  s  x_ld off y_ld off r_ld off act out dtype flags tile
+d = (C.c_int32 * 18)(1, 52, 52, 128, 256, 3, 1, 128, 0, 256, 0, 0, 0, 1, 0, 0, 0, 0)
+lib.yolo_conv_workspace_bytes.restype = C.c_size_t
+print("pick_tile", lib.yolo_conv_pick_tile(d))
+print("workspace_bytes", lib.yolo_conv_workspace_bytes(d))
+"""
+
+
+def _switch_child(built, env):
+    import subprocess
+    import sys
+    e = {k: v for k, v in os.environ.items() if k not in ALL_SWITCHES}
+    e.update(env)
+    out = subprocess.run([sys.executable, "-c", _SWITCH_CHILD, built.LIB_PATH], env=e, check=True, stdout=subprocess.PIPE,
+                         text=True).stdout.splitlines()
+    rows = [tuple(ln.split("=")) for ln in out[:-2]]
+    assert [k for k, _ in rows] == list(ALL_SWITCHES), "one row per switch, in the table's order"
+    routing = dict(ln.split() for ln in out[-2:])
+    return {k: int(v) for k, v in rows}, int(routing["pick_tile"]), int(routing["workspace_bytes"])
+
+
+@pytest.mark.parametrize("value,presence,prio,ints", [
+    (None, 0, 1, None),        # nothing set: every row at its default
+    ("0", 1, 0, 0),            # a presence switch is on whatever its value; *_PRIO is off when the first character is '0'
+    ("7", 1, 1, 7),
+    ("", 1, 1, 0),             # the empty string: set (presence on), not '0' (*_PRIO on), atoi("") = 0
+])
+def test_switches_are_read_by_their_rules(built, value, presence, prio, ints):
+    got, _, _ = _switch_child(built, {} if value is None else {k: value for k in ALL_SWITCHES})
+    want = {k: presence for k in PRESENCE_SWITCHES}
+    want.update({k: prio for k in PRIO_SWITCHES})
+    want.update({k: (dflt if ints is None else ints) for k, dflt in INT_SWITCHES.items()})
+    assert got == want
+
+
+def test_no_winograd_switch_reaches_the_routing(built):
+    """A switch that silently stopped working would pass every GPU test (they assert that both paths agree): this one is
+    checked by what it selects. fp32 3x3 stride 1, 128 -> 256 at 52 x 52: F(4x4) (tile 15) with a workspace, a direct tile
+    and no workspace under YOLO_NO_WINOGRAD."""
+    sw, tile, ws = _switch_child(built, {})
+    assert sw["YOLO_NO_WINOGRAD"] == 0 and tile == 15 and ws > 0
+    sw, tile, ws = _switch_child(built, {"YOLO_NO_WINOGRAD": "1"})
+    assert sw["YOLO_NO_WINOGRAD"] == 1 and tile not in (13, 14, 15) and tile > 0 and ws == 0

@@ -62,6 +62,7 @@ class YoloLibError(RuntimeError):
 _SIGS = {
     "yolo_last_error": (C.c_char_p, []),
     "yolo_version": (C.c_int, []),
+    "yolo_switches_describe": (C.c_int, [C.c_char_p, C.c_size_t]),
     "yolo_packed_weight_elems": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "yolo_packed_weight_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "yolo_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include "../../include/yolo_mi355x.h"
+#include "switches.h"
 
 namespace yolo {
 
@@ -189,6 +190,30 @@ template <> struct Vec16<_Float16> {
 #define YOLO_SWITCH_H16(dtype, ...)                                                       \
     if ((dtype) == YOLO_BF16) { typedef __bf16 T; __VA_ARGS__; }                          \
     else { typedef _Float16 T; __VA_ARGS__; }
+
+// ---- tile ids (yolo_conv_desc::tile): 0 = the library's heuristic, anything else forces a kernel (tuning, tests, A/B runs). The
+// numbers are the public header's; some mean one kernel for fp32 and another for bf16 / fp16, so those names carry the dtype.
+constexpr int kNumTiles = 10;                // what yolo_conv_num_tiles reports: the ids of the plain tiled kernels, 1 .. 10
+constexpr int kMaxTileId = 15;               // validate() refuses anything above
+// fp32 (conv_f32.hip routes them)
+constexpr int kTileF32Reg128x128 = 1;        // conv_igemm_f32, register-staged, BM x BN
+constexpr int kTileF32Reg128x64 = 2;
+constexpr int kTileF32Reg64x128 = 3;
+constexpr int kTileF32Reg64x64 = 4;
+constexpr int kTileF32V2Bn64 = 5;            // conv_f32_v2.hip, 64 output channels per block
+constexpr int kTileF32V2Bn128 = 6;           //   128 output channels per block
+constexpr int kTileF32V2Single = 7;          //   64, one patch buffer (3 blocks per CU)
+constexpr int kTileF32Rs = 12;               // conv1_rs_f32.hip (1x1, weights in registers)
+constexpr int kTileF32Wino = 13;             // conv_wino_f32 (3x3 stride 1, Winograd F(2x2, 3x3), one pass; needs the caller's workspace)
+constexpr int kTileF32Wino2 = 14;            // conv_wino2_f32 (the same in two passes, two workgroups per CU)
+constexpr int kTileF32Wino4 = 15;            // conv_wino4_f32.hip (Winograd F(4x4, 3x3); needs the caller's workspace)
+// bf16 / fp16 (conv_h16.hip routes them)
+constexpr int kTileH16PatchBn64 = 5;         // conv_patch_h16, 64 output channels per block
+constexpr int kTileH16PatchBn128 = 6;        //   128 output channels per block
+constexpr int kTileH16Dma = 8;               // the LDS-DMA kernels: conv3_dma_h16 (3x3 stride 1), conv1_dma_h16 (1x1)
+constexpr int kTileH16DmaIdentQuads = 10;    //   the same with the identity lane-quad -> pixel-quad map
+constexpr int kTileH16S2Gemm = 13;           // conv1_dma_h16 as a GEMM with gathered rows (3x3 stride 2)
+constexpr int kTileH16Ws = 14;               // conv3_ws_h16 (3x3, <= 64 channels, weights in registers)
 
 // conv_f32_v2.hip ("patch + fragment stream" kernel, stride 1, cin % 32 == 0)
 bool v2_eligible(const yolo_conv_desc* d);

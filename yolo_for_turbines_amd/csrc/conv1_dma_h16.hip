@@ -312,7 +312,7 @@ static int launch_dma1_t(ConvHArgs& a, hipStream_t s) {
     a.tiles_n = ceil_div(a.Cout, BN);
     a.nblocks = a.tiles_n * ceil_div(a.W, 128);
     fill_magics(a);
-    a.prio = g_h_prio ? 1 : 0;
+    a.prio = switches().dma_prio ? 1 : 0;
     const size_t lds = (size_t)E_SLOTS * E_SLOT_BYTES;      // 80 KiB: two blocks per CU
     static LdsOnce once;
     if (int rc = reserve_lds(once, reinterpret_cast<const void*>(&conv1_dma_h16<T, BN, GATH>), lds, "conv1_dma_h16")) return rc;

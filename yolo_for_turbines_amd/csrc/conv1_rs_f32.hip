@@ -227,8 +227,7 @@ __global__ __launch_bounds__(256, 1) void conv1_rs_f32(const Conv1RsArgs p) {
 }
 
 bool conv1_rs_eligible(const yolo_conv_desc* d, const void* residual) {
-    static const bool off = getenv("YOLO_NO_CONV1_RS") != nullptr;   // A/B switch: round 2's kernel
-    if (off || d->dtype != YOLO_F32 || d->ksize != 1 || d->stride != 1 || d->out_mode == YOLO_OUT_HEAD) return false;
+    if (switches().no_conv1_rs || d->dtype != YOLO_F32 || d->ksize != 1 || d->stride != 1 || d->out_mode == YOLO_OUT_HEAD) return false;
     if (d->cin != 256 && d->cin != 384 && d->cin != 512) return false;          // K = 768 / 1024: a 32-pixel tile does not fit a ring
     if (d->cout % 128) return false;
     // persistent workgroups of 32-pixel tiles: below ~4 tiles per workgroup the start-up (K / 2 weight registers per lane, the
@@ -238,8 +237,8 @@ bool conv1_rs_eligible(const yolo_conv_desc* d, const void* residual) {
     // The rule must NOT look at the batch size: this kernel adds the K products in another order than conv_patch_f32 (a lane
     // holds 4 consecutive k of its row), and an image's result may not depend on how many neighbours share its batch
     // (tests/test_gpu_fullsize.py: image 17 of 32 == the same image alone, bit for bit).
-    if (d->tile != 12 && ((long long)d->h * d->w < 2048 || d->cin > 384)) return false;
-    if (d->tile != 12 && residual) return false;            // with a residual row per store it measured slower (79.8 vs 74.9 us at 52 x 52)
+    if (d->tile != kTileF32Rs && ((long long)d->h * d->w < 2048 || d->cin > 384)) return false;
+    if (d->tile != kTileF32Rs && residual) return false;            // with a residual row per store it measured slower (79.8 vs 74.9 us at 52 x 52)
     if ((d->x_ld & 3) || (d->x_off & 3) || (d->y_ld & 3) || (d->y_off & 3)) return false;
     if (residual && ((d->r_ld & 3) || (d->r_off & 3))) return false;
     return true;

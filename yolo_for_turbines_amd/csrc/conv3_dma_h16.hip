@@ -395,7 +395,7 @@ int launch_dma(ConvHArgs& a, int dtype, hipStream_t s) {
     constexpr int BN = 128;
     tile_grid_h(a, BN);
     a.bufmask = 1;
-    a.prio = g_h_prio ? 1 : 0;
+    a.prio = switches().dma_prio ? 1 : 0;
     a.mtab_off = 2 * D_PATCH_BYTES + D_SLOTS * (BN / 32) * 2048;
     const size_t lds = (size_t)a.mtab_off + 256 * sizeof(int) + 2 * BN * sizeof(float);
     YOLO_SWITCH_H16(dtype,

@@ -228,8 +228,7 @@ __global__ __launch_bounds__(256, 2) void conv3_ws_h16(const ConvWsArgs p) {
 }
 
 bool ws_eligible(const yolo_conv_desc* d, const void* residual) {
-    static const bool off = getenv("YOLO_NO_CONV3_WS") != nullptr;
-    if (d->tile != 14 && (off || d->tile != 0)) return false;
+    if (d->tile != kTileH16Ws && (switches().no_conv3_ws || d->tile != 0)) return false;
     if (d->ksize != 3 || d->out_mode != YOLO_OUT_NHWC || d->dtype == YOLO_F32) return false;
     const bool shape = (d->stride == 1 && ((d->cin == 32 && d->cout > 32 && d->cout <= 64) || (d->cin == 64 && d->cout <= 32))) ||
                        (d->stride == 2 && d->cin == 32 && d->cout > 32 && d->cout <= 64);

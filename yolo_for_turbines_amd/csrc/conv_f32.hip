@@ -264,14 +264,6 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvArgs p) {
 }
 
 // ------------------------------------------------------------------------------ host side
-
-
-constexpr int kNumTiles = 10;     // 1-4: register-staged tiles above; 5/6: conv_f32_v2.hip with BN = 64/128; 7: BN = 64, one patch buffer (3 blocks/CU); 8-10: 16-bit only (conv3_dma_h16)
-constexpr int kTileRs = 12;       // conv1_rs_f32.hip (fp32 1x1, weights in registers)
-constexpr int kTileWino = 13;     // conv_wino_f32.hip (fp32 3x3 stride 1, Winograd F(2x2, 3x3); needs the caller's workspace)
-constexpr int kTileWino4 = 15;    // conv_wino4_f32.hip (fp32 3x3 stride 1, Winograd F(4x4, 3x3); needs the caller's workspace)
-constexpr int kMaxTileId = 31;    // ids above kNumTiles: the named ones above; 16 + bits = timing probes of the fp32 Winograd diagnostic library (make wstamps)
-
 static size_t lds_bytes(int bm, int bn) { return (size_t)2 * (bm + bn) * LDS_LD * sizeof(float); }
 
 template <int BM, int BN>
@@ -291,13 +283,6 @@ static int launch_tile(const ConvArgs& a, bool smallc, hipStream_t s) {
 // Measured on MI355X (tools/conv_bench.py, batch 32). The register-staged kernel of this file is
 // latency-bound, so among its tiles 64x64 (4+ resident blocks per CU) wins on every YOLOv3 shape;
 // stride-1 layers with cin % 32 == 0 go to the patch/fragment-stream kernel (ids 5, 6).
-static int pick_direct_tile(const yolo_conv_desc* d);
-static int pick_tile(const yolo_conv_desc* d) {
-    if (wino4_eligible(d)) return kTileWino4;       // with a workspace (yolo_conv_fwd_ws / the launch table); without one: the ids below
-    if (wino_eligible(d)) return kTileWino;
-    return pick_direct_tile(d);
-}
-
 static int pick_direct_tile(const yolo_conv_desc* d) {
     if (v2_eligible(d) && d->ksize == 3) {
         // Measured (tools/conv_bench.py --tile 5,6,7, batch 32): BN = 64 with ONE patch buffer (tile 7: 37 KB of LDS,
@@ -305,10 +290,39 @@ static int pick_direct_tile(const yolo_conv_desc* d) {
         // 104x104, 52x52 and 13x13 — three co-resident blocks cover each other's prologue/epilogue and 752 blocks fill
         // 768 slots in one round at 13x13. At 26x26 (K = 2304, 1440 such blocks) BN = 128 with two buffers stays 9 % ahead.
         const int ho = d->h;
-        if (d->cout > 64 && ho <= 26 && ho > 13 && v2_blocks(d, 128) >= 640) return 6;
-        return 7;
+        if (d->cout > 64 && ho <= 26 && ho > 13 && v2_blocks(d, 128) >= 640) return kTileF32V2Bn128;
+        return kTileF32V2Single;
     }
-    return 4;       // 1x1 (few K steps, prologue-dominated) and stride-2 layers: 64x64 register-staged tile
+    return kTileF32Reg64x64;       // 1x1 (few K steps, prologue-dominated) and stride-2 layers: 64x64 register-staged tile
+}
+
+// Which kernel family runs an fp32 descriptor: the one place that knows. `ws_avail` is the workspace the caller brings (0: none,
+// SIZE_MAX: whatever yolo_conv_workspace_bytes asks for). A forced tile names its family whether or not the layer fits it - the
+// launch then fails with that family's message; tile 0 is the heuristic, which looks at the layer's shape only, never at the batch.
+enum class F32Family { Direct, Rs, Wino, Wino4 };
+
+static F32Family f32_family(const yolo_conv_desc* d, const void* residual, size_t ws_avail) {
+    const bool heuristic = d->tile == 0;
+    // 1x1 with 256 / 384 / 512 input channels and a multiple of 128 output channels: weights stationary in registers
+    if ((heuristic || d->tile == kTileF32Rs) && conv1_rs_eligible(d, residual)) return F32Family::Rs;
+    // 3x3 stride 1 by Winograd F(4x4, 3x3), else by F(2x2, 3x3): the heuristic only with a large enough workspace (yolo_conv_fwd has
+    // none: the library allocates nothing), so a workspace between the two sizes gets F(2x2)
+    if (d->tile == kTileF32Wino4 || (heuristic && wino4_eligible(d) && ws_avail >= wino4_workspace_bytes(d))) return F32Family::Wino4;
+    if (d->tile == kTileF32Wino || d->tile == kTileF32Wino2 || (heuristic && wino_eligible(d) && ws_avail >= wino_workspace_bytes(d)))
+        return F32Family::Wino;
+    return F32Family::Direct;       // tiles 1-7 (and tile 12 on a layer conv1_rs_f32 cannot run: an error)
+}
+
+// what the heuristic picks when the caller brings the workspace (yolo_conv_fwd_ws / the launch table). A layer of the F(2x2) family is
+// reported as tile 13 also where conv_wino_launch then takes the two-pass kernel (tile 14), a conv1_rs_f32 layer as its direct tile
+static int pick_tile(const yolo_conv_desc* d) {
+    yolo_conv_desc h = *d;
+    h.tile = 0;
+    switch (f32_family(&h, nullptr, SIZE_MAX)) {
+    case F32Family::Wino4: return kTileF32Wino4;
+    case F32Family::Wino: return kTileF32Wino;
+    default: return pick_direct_tile(d);
+    }
 }
 
 static int validate(const yolo_conv_desc* d) {
@@ -351,34 +365,30 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     a.nc5 = d->out_mode == YOLO_OUT_HEAD ? d->cout / 3 : 1;
     a.tiles_n = 0;
     const bool smallc = a.Cin == 4;
-    // 1x1 with 256 / 384 / 512 input channels and a multiple of 128 output channels: weights stationary in registers (tile 0 =
-    // heuristic, or tile 12 explicitly; tiles 1-4 keep the register-staged kernel for A/B)
-    if ((d->tile == 0 || d->tile == kTileRs) && conv1_rs_eligible(d, residual)) return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
-    if (d->tile == kTileRs) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 12 needs a 1x1 with 256 / 384 / 512 input channels and cout %% 128 == 0");
-    // 3x3 stride 1 by Winograd F(4x4, 3x3): tile 15 explicitly, or the heuristic when the caller brought a large enough workspace
-    // (yolo_conv_fwd itself has none: the library allocates nothing); the filters are transformed per launch from the row-major section
-    if (d->tile == kTileWino4 || (d->tile == 0 && wino4_eligible(d) && ws && ws_bytes >= wino4_workspace_bytes(d))) {
+    switch (f32_family(d, residual, ws ? ws_bytes : 0)) {
+    case F32Family::Rs: return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
+    case F32Family::Wino4:          // the filters are transformed per launch from the row-major section
         if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         return conv_wino4_launch(d, x, (const float*)w, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
-    }
-    // ... by F(2x2, 3x3): tile 13 explicitly, or the heuristic as above
-    if (d->tile == kTileWino || d->tile == kTileWino + 1 || (d->tile >= 16 && d->ksize == 3 && wino_supported(d)) ||      // 16+: timing probes of the diagnostic library (make wstamps)
-        (d->tile == 0 && wino_eligible(d) && ws && ws_bytes >= wino_workspace_bytes(d))) {
+    case F32Family::Wino: {
         if (!wino_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 13 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         const float* U = (const float*)w + v0_packed_elems(d->cout, d->cin, d->ksize) + v2_frag_elems(d->cout, d->cin, d->ksize);
         return conv_wino_launch(d, x, U, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
     }
+    case F32Family::Direct: break;
+    }
+    if (d->tile == kTileF32Rs) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 12 needs a 1x1 with 256 / 384 / 512 input channels and cout %% 128 == 0");
     const int t = d->tile ? d->tile : pick_direct_tile(d);
-    if (t >= 8) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile ids from 8 up are 16-bit kernels (conv3_dma_h16)");
-    if (t >= 5) {
+    if (t > kTileF32V2Single) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile ids from 8 up are 16-bit kernels (conv3_dma_h16)");
+    if (t >= kTileF32V2Bn64) {
         if (!v2_eligible(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile %d needs stride 1 and cin %% 32 == 0", t);
         const float* wf = (const float*)w + v0_packed_elems(d->cout, d->cin, d->ksize);
-        return conv_v2_launch(d, x, wf, scale, shift, residual, y, nan_flag, t == 6 ? 128 : 64, t == 7, s);
+        return conv_v2_launch(d, x, wf, scale, shift, residual, y, nan_flag, t == kTileF32V2Bn128 ? 128 : 64, t == kTileF32V2Single, s);
     }
     switch (t) {
-        case 1: return launch_tile<128, 128>(a, smallc, s);
-        case 2: return launch_tile<128, 64>(a, smallc, s);
-        case 3: return launch_tile<64, 128>(a, smallc, s);
+        case kTileF32Reg128x128: return launch_tile<128, 128>(a, smallc, s);
+        case kTileF32Reg128x64: return launch_tile<128, 64>(a, smallc, s);
+        case kTileF32Reg64x128: return launch_tile<64, 128>(a, smallc, s);
         default: return launch_tile<64, 64>(a, smallc, s);
     }
 }
@@ -402,9 +412,11 @@ int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, 
 
 size_t yolo_conv_workspace_bytes(const yolo_conv_desc* d) {
     if (yolo::validate(d)) return 0;
-    if (d->tile == yolo::kTileWino4 || (d->tile == 0 && yolo::wino4_eligible(d))) return yolo::wino4_workspace_bytes(d);
-    if (d->tile == yolo::kTileWino || d->tile == yolo::kTileWino + 1 || d->tile >= 16 || (d->tile == 0 && yolo::wino_eligible(d))) return yolo::wino_workspace_bytes(d);
-    return 0;
+    switch (yolo::f32_family(d, nullptr, SIZE_MAX)) {          // (the caller will bring what this asks for)
+    case yolo::F32Family::Wino4: return yolo::wino4_workspace_bytes(d);
+    case yolo::F32Family::Wino: return yolo::wino_workspace_bytes(d);
+    default: return 0;
+    }
 }
 
 int yolo_conv_fwd_ws(const yolo_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,

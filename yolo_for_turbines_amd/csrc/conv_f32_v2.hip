@@ -18,9 +18,8 @@
 //  Occupancy        BN = 128: two patch buffers (64.5 KB LDS, 224 registers) -> 2 blocks per CU. BN = 64 can run with ONE
 //      patch buffer (36.9 KB, 148 registers, one more barrier per chunk) -> 3 blocks per CU, which covers prologue /
 //      epilogue better and fills 768 slots in one round at 13x13: the configuration measured fastest at 208 / 104 / 52 /
-//      13 (conv_f32.hip:pick_tile).
+//      13 (conv_f32.hip:pick_direct_tile).
 #include "common.h"
-#include <cstdlib>
 
 namespace yolo {
 
@@ -467,8 +466,6 @@ __global__ void pack_weights_frag_f32(const float* __restrict__ w, float* __rest
 #ifdef V2_STAMPS
 unsigned long long* g_v2_dbg = nullptr;
 #endif
-static const bool g_v2_stagger = !(getenv("YOLO_NO_STAGGER"));
-static const bool g_v2_prio = !(getenv("YOLO_F32_PRIO") && getenv("YOLO_F32_PRIO")[0] == '0');
 bool v2_eligible(const yolo_conv_desc* d) { return d->stride == 1 && d->cin % 32 == 0; }
 
 size_t v2_frag_elems(int cout, int cin, int ks) {
@@ -521,8 +518,8 @@ static int launch_v2(Conv2Args& a, hipStream_t s) {
     // resident blocks per CU (2, or 3 with a single patch buffer) x 256 CUs are dispatched at once
     a.first_wave = (a.bufmask ? 2 : 3) * 256;
     const long mfma_cycles = (long)a.KT * 32 * (BN / 64) * 64;  // one block's matrix work per wave
-    a.stagger = g_v2_stagger ? (int)((mfma_cycles + 64 * 127 / 2) / (64 * 127)) : 0;
-    a.prio = g_v2_prio ? 1 : 0;
+    a.stagger = !switches().no_stagger ? (int)((mfma_cycles + 64 * 127 / 2) / (64 * 127)) : 0;
+    a.prio = switches().f32_prio ? 1 : 0;
     const size_t lds = (size_t)(a.bufmask + 1) * a.patch_cap * V2_LD * sizeof(float) + 128 * sizeof(int);   // >= 128*68*4 staging
     hipLaunchKernelGGL((conv_patch_f32<KS, BN>), dim3(a.nblocks), dim3(256), lds, s, a);
     return check_launch("conv_patch_f32");

@@ -5,8 +5,6 @@
 
 namespace yolo {
 
-static const bool g_h_dma = !(getenv("YOLO_NO_DMA"));
-
 // The GEMM view of ConvHArgs (conv1_dma_h16): one tile row of M pixels, `taps` K steps per 32-channel chunk. TW and PC are
 // the divisors the gathering variants take a pixel index apart with, H the channels per class of the fused stride-2 gradient.
 static void gemm_view(ConvHArgs& a, int M, int H, int TW, int PC, int taps) {
@@ -41,7 +39,7 @@ int dgrad_s2_h16_launch(const void* dz, int dz_ld, int dz_off, const void* wf, c
     a.act = YOLO_ACT_NONE; a.out_mode = YOLO_OUT_NHWC; a.flags = residual ? YOLO_FLAG_RESIDUAL : 0;
     const long long M = (long long)n * ho * wo;
     if (M * 4 > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "dgrad_s2: too many pixels");
-    if (s2g_ok(cout, cin) && g_h_dma && (dx_ld & 7) == 0 && (dx_off & 7) == 0 && (!residual || ((r_ld & 7) == 0 && (r_off & 7) == 0))) {
+    if (s2g_ok(cout, cin) && !switches().no_dma && (dx_ld & 7) == 0 && (dx_off & 7) == 0 && (!residual || ((r_ld & 7) == 0 && (r_off & 7) == 0))) {
         size_t skip = 0;
         for (int cls = 0; cls < 4; ++cls) skip += cls_frag_elems(cin, cout, cls);
         a.wf = (const unsigned short*)wf + skip;
@@ -114,16 +112,16 @@ int conv_h16_launch_stats(const yolo_conv_desc* d, const void* x, const void* wf
     const long long M = (long long)d->n * a.Ho * a.Wo;
     if (M > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "conv: N*H*W exceeds int32");
     int prmax = 1;
-    // tile ids (16-bit): 5 / 6 = conv_patch_h16 with 64 / 128 output channels per block, 8 = conv3_dma_h16 (3x3 stride 1)
+    // (tile ids of the 16-bit kernels: kTileH16* in common.h)
     const bool dma_ok = d->ksize == 3 && d->stride == 1 && d->cout > 64 && d->cin <= 2048 && d->cout % 8 == 0 && d->out_mode != YOLO_OUT_HEAD &&
                         (d->y_ld & 7) == 0 && (d->y_off & 7) == 0 && (!residual || ((d->r_ld & 7) == 0 && (d->r_off & 7) == 0));
     // 1x1 with >= 128 output channels and >= 4 K steps: conv1_dma_h16 (tile 8 / default); tiles 5, 6 keep conv_patch_h16
     const bool dma1_ok = d->ksize == 1 && d->stride == 1 && d->cout >= 128 && d->cin >= 128 && d->cout % 8 == 0 && d->out_mode != YOLO_OUT_HEAD &&
                          (d->y_ld & 7) == 0 && (d->y_off & 7) == 0 && (!residual || ((d->r_ld & 7) == 0 && (d->r_off & 7) == 0));
-    if (d->tile == 8 && !dma_ok && !dma1_ok)
+    if (d->tile == kTileH16Dma && !dma_ok && !dma1_ok)
         return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 8 needs 3x3 stride 1 with more than 64 output channels, or 1x1 with >= 128 input and output channels");
-    const bool use_dma = dma_ok && (d->tile >= 8 || (d->tile == 0 && g_h_dma));
-    if (d->tile == 14 && !ws_eligible(d, residual)) return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 14 needs a 3x3 32 -> 64 (stride 1 / 2) or 64 -> 32 (stride 1) layer, NHWC");
+    const bool use_dma = dma_ok && (d->tile >= kTileH16Dma || (d->tile == 0 && !switches().no_dma));
+    if (d->tile == kTileH16Ws && !ws_eligible(d, residual)) return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 14 needs a 3x3 32 -> 64 (stride 1 / 2) or 64 -> 32 (stride 1) layer, NHWC");
     if (!want_stats && ws_eligible(d, residual)) return conv_ws_launch(d, x, wf, scale, shift, residual, y, nan_flag, s);
     if (want_stats && !bs && ws_eligible(d, residual)) {            // train-mode forward of the <= 64-channel 3x3 blocks: one row per wave
         if (const int rows = ws_stats_rows(d)) {
@@ -135,21 +133,20 @@ int conv_h16_launch_stats(const yolo_conv_desc* d, const void* x, const void* wf
     // pixel tiles of 52x52 / 104x104 (its two 16-lane groups are quads {0,3,5,6} and {1,2,4,7}: 4 rows whose patch offsets collide
     // mod 16); sending even tile rows to one group and odd rows to the other removes that, and measured 1-4 % at every size
     // (profiles/r02/ab_quad_permutation.txt). Tile 10 keeps the identity map for A/B.
-    a.qperm = d->tile == 10 ? 0x76543210u : 0x76452310u;
+    a.qperm = d->tile == kTileH16DmaIdentQuads ? 0x76543210u : 0x76452310u;
     a.cls_ph = 0;                                           // (the MASK kernels' output parity: dgrad_s2_h16_launch)
-    if (dma1_ok && (d->tile == 8 || (d->tile == 0 && g_h_dma))) {
+    if (dma1_ok && (d->tile == kTileH16Dma || (d->tile == 0 && !switches().no_dma))) {
         gemm_view(a, (int)M, 1, 128, 128, 1);
         if (want_stats)
             if (const int r = stats_rows(2 * ceil_div(a.W, 128), a.stats_ld, rows_ld, dry, stats_bytes)) return r < 0 ? r : YOLO_OK;
         return launch_dma1(a, 0, d->dtype, s);
     }
     // 3x3 stride 2 with >= 128 output channels: conv1_dma_h16 as a GEMM with gathered rows (tile 0 / 13; tiles 5, 6 keep conv_patch_h16)
-    static const bool no_s2_dma = getenv("YOLO_NO_S2_DMA") != nullptr;
     const bool s2_ok = d->ksize == 3 && d->stride == 2 && d->cout >= 128 && d->cout % 8 == 0 && d->out_mode == YOLO_OUT_NHWC &&
                        (d->y_ld & 7) == 0 && (d->y_off & 7) == 0 && (!residual || ((d->r_ld & 7) == 0 && (d->r_off & 7) == 0)) &&
                        (long long)a.Ho * a.Wo < 0x7fffffffLL && d->cin * 9 / 32 >= 4;
-    if (d->tile == 13 && !s2_ok) return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 13 needs 3x3 stride 2 with >= 128 output channels");
-    if (s2_ok && (d->tile == 13 || (d->tile == 0 && g_h_dma && !no_s2_dma))) {
+    if (d->tile == kTileH16S2Gemm && !s2_ok) return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 13 needs 3x3 stride 2 with >= 128 output channels");
+    if (s2_ok && (d->tile == kTileH16S2Gemm || (d->tile == 0 && !switches().no_dma && !switches().no_s2_dma))) {
         gemm_view(a, (int)M, 1, a.Wo, a.Ho * a.Wo, 9);
         if (want_stats)
             if (const int r = stats_rows(2 * ceil_div(a.W, 128), a.stats_ld, rows_ld, dry, stats_bytes)) return r < 0 ? r : YOLO_OK;
@@ -187,7 +184,7 @@ int conv_h16_launch_stats(const yolo_conv_desc* d, const void* x, const void* wf
     // smaller blocks (BN = 64); every 3x3 with more than 64 output channels gains from BN = 128 (64->128 @104: 81 vs 98 us,
     // 64->128 s2 @208: 119 vs 131 us, 13x13 .. 52x52: 15-20 %) - the earlier "only up to 52x52" rule predated the epilogue fixes
     const int auto_bn = (d->ksize == 3 && d->cout > 64) ? 128 : 64;   // same-box A/B of the whole forward: +0.7 % at 416x416, +3.8 % at 608x608
-    const int bn = d->tile == 5 ? 64 : (d->tile == 6 ? 128 : auto_bn);
+    const int bn = d->tile == kTileH16PatchBn64 ? 64 : (d->tile == kTileH16PatchBn128 ? 128 : auto_bn);
     return launch_h(a, d->ksize, d->stride, bn, d->dtype, s);
 }
 

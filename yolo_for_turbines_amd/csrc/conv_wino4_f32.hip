@@ -405,8 +405,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
 }
 
 // ------------------------------------------------------------------------------ host side
-static const bool g_wino4_off = getenv("YOLO_NO_WINOGRAD") != nullptr;     // A/B switch: the direct kernels (F(2x2) is off as well)
-
 static long long wino4_tiles(const yolo_conv_desc* d) { return (long long)d->n * ((d->h + 3) / 4) * ((d->w + 3) / 4); }
 
 bool wino4_supported(const yolo_conv_desc* d) {
@@ -422,7 +420,7 @@ bool wino4_supported(const yolo_conv_desc* d) {
 // the tiles' pixels wasted), 351 against 297 at 13 x 13 (padded to 16 x 16: 51 % wasted). So: maps of at least 26 x 26 pixels whose
 // padding to whole 4 x 4 tiles adds at most a fifth.
 bool wino4_eligible(const yolo_conv_desc* d) {
-    if (g_wino4_off || !wino_eligible(d) || !wino4_supported(d)) return false;
+    if (switches().no_winograd || !wino_eligible(d) || !wino4_supported(d)) return false;
     const long long area = (long long)d->h * d->w, padded = 16LL * ((d->h + 3) / 4) * ((d->w + 3) / 4);
     return area >= 26 * 26 && 5 * padded <= 6 * area;
 }

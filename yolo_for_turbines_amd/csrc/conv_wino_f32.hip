@@ -164,18 +164,11 @@ constexpr int WN_STAGE = 32768;          // bytes per ring stage: V [16][64][4] 
 constexpr int WN_SLOTS = 4;              // (a power of two: slot arithmetic by mask)
 constexpr int WN_DMA = 8;                // DMA wave-instructions per wave and stage
 constexpr int WN_AHEAD = 4;              // fragment reads kept in flight, in xi (2 reads each)
-#ifndef WN_DMA_MODE
-#define WN_DMA_MODE 0
-#endif
 constexpr int WN_BAR = 16 - WN_AHEAD;    // the stage's barrier sits in front of this xi (all reads of the stage are issued by then)
 
-// PROBE (diagnostic build only, garbage results): 1 = no stage barrier / DMA wait, 2 = no DMA requests in the loop, 4 = no fragment reads;
-// 8 + e ablates a part of the EPILOGUE instead: e = 0 the stores, 1 the residual requests, 3 staging and stores
-template <int ACT, bool RES, int PROBE = 0>
+template <int ACT, bool RES>
 __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int MP = (PROBE & 8) ? 0 : PROBE;          // main-loop ablations
-    constexpr int EP = (PROBE & 8) ? (PROBE & 3) : -1;   // epilogue ablation
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, m = lane & 31;
@@ -183,9 +176,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
     const int nt = q % p.n_nt, mt = (q / p.n_nt) * 8 + xcd;
     if (mt >= p.n_mt) return;
     const int wm = wave & 1, wn = wave >> 1;
-#ifdef WN_STAMPS   // diagnostic build (make wstamps): per-workgroup phase stamps into the buffer passed as nan_flag (tools/wino_stamps.py)
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
 
     // ---- DMA roles: this wave moves xi = 4 wave .. 4 wave + 3 of V and of U, lane = row
     const size_t v_xi = (size_t)p.C4 * p.Tpad * 4, v_c4 = (size_t)p.Tpad * 4;
@@ -240,10 +230,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
     else wn_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-#ifdef WN_STAMPS
-    const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     wn_for<0, WN_AHEAD>([&](auto X) { constexpr int x = decltype(X)::value; wn_read2<x * 1024>(fa[x], fb[x], ub, vb); });
 
     int slot = 0;
@@ -252,38 +238,15 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
         int ns = slot + 1;
         ns = ns == WN_SLOTS ? 0 : ns;
         const unsigned nb = (unsigned)ns * WN_STAGE;
-        // Where the DMA requests of the ring go (WN_DMA_MODE; stage st + 3 takes the slot stage st - 1 had, free from this stage's
-        // barrier on). A request costs the issuing wave 60-185 cycles (MI355X_MICROARCH.md, "LDS-DMA piece issue cost") with
-        // ONE MFMA in flight behind it, and this kernel has one wave per SIMD: nobody else issues MFMAs meanwhile.
-        //   0: all eight behind the first xi after the barrier;  1: one behind every second xi (12, 14, then 0 .. 10 of the next stage);
-        //   2: as 1, between the two MFMAs of the xi;  3: one behind each of the eight MFMAs after the barrier
-        auto dma_at = [&](auto XX, auto HH) {
-            constexpr int x = decltype(XX)::value, half = decltype(HH)::value;
-            if constexpr (MP & 2) return;
-            if constexpr (WN_DMA_MODE == 0) {
-                if constexpr (x == WN_BAR && half == 1) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (st + 3 < nst) issue(st + 3, (slot + 3) & (WN_SLOTS - 1));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else if constexpr (WN_DMA_MODE == 3) {
-                if constexpr (x >= WN_BAR) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (st + 3 < nst) issue_piece(std::integral_constant<int, 2 * (x - WN_BAR) + half>{}, st + 3, (slot + 3) & (WN_SLOTS - 1));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else if constexpr (half == (WN_DMA_MODE == 1 ? 1 : 0)) {
-                if constexpr (x == WN_BAR || x == WN_BAR + 2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (st + 3 < nst) issue_piece(std::integral_constant<int, (x - WN_BAR) / 2>{}, st + 3, (slot + 3) & (WN_SLOTS - 1));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (x < WN_BAR && x % 2 == 0) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (st >= 1 && st + 2 < nst) issue_piece(std::integral_constant<int, 2 + x / 2>{}, st + 2, (slot + 2) & (WN_SLOTS - 1));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+        // The DMA requests of stage st + 3, all eight in one burst (it takes the slot stage st - 1 had, free from this stage's barrier
+        // on). A request costs the issuing wave 60-185 cycles (MI355X_MICROARCH.md, "LDS-DMA piece issue cost") with ONE MFMA in
+        // flight behind it, and this kernel has one wave per SIMD: nobody else issues MFMAs meanwhile. Spreading the requests over
+        // the stage was measured and is no faster. (A lambda, not the three lines in place: written in place, the
+        // compiler numbers the kernel's registers differently.)
+        auto issue_ahead = [&] {
+            __builtin_amdgcn_sched_barrier(0);
+            if (st + 3 < nst) issue(st + 3, (slot + 3) & (WN_SLOTS - 1));
+            __builtin_amdgcn_sched_barrier(0);
         };
         wn_for<0, 16>([&](auto X) {
             constexpr int x = decltype(X)::value;
@@ -292,40 +255,30 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
                 // stage st + 1 has to be in LDS for everybody before its first fragments are read; the slot of stage st - 1
                 // (= of stage st + 3) is free once everybody is here
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MP & 1)) {
-                    if (st + 2 < nst) wn_wait_vmcnt<WN_DMA>();
-                    else wn_wait_vmcnt<0>();
-                    __builtin_amdgcn_s_barrier();
-                }
+                if (st + 2 < nst) wn_wait_vmcnt<WN_DMA>();
+                else wn_wait_vmcnt<0>();
+                __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (x + WN_AHEAD < 16 && !(MP & 4)) wn_read2<(x + WN_AHEAD) * 1024>(fa[x + WN_AHEAD], fb[x + WN_AHEAD], ub + sb, vb + sb);
+            if constexpr (x + WN_AHEAD < 16) wn_read2<(x + WN_AHEAD) * 1024>(fa[x + WN_AHEAD], fb[x + WN_AHEAD], ub + sb, vb + sb);
             // reads issued after those of xi = x and still in flight (LDS operations return in order): 2 per xi. Behind the
             // barrier: xi 12 -> 13, 14, 15; 13 -> 14, 15; 14 -> 15 and the next stage's 0, 1; 15 -> the next stage's 0 .. 3
             constexpr int after = x < WN_BAR ? 2 * WN_AHEAD : x == 12 ? 6 : x == 13 ? 4 : x == 14 ? 6 : 8;
-            if constexpr (!(MP & 4)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fa[x]), "+v"(fb[x]) : "n"(after));
-            else asm volatile("" : "+v"(fa[x]), "+v"(fb[x]));
+            asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fa[x]), "+v"(fb[x]) : "n"(after));
             acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[x][0], fb[x][0], acc[x], 0, 0, 0);
-            dma_at(X, std::integral_constant<int, 0>{});
             acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[x][1], fb[x][1], acc[x], 0, 0, 0);
-            dma_at(X, std::integral_constant<int, 1>{});
+            if constexpr (x == WN_BAR) issue_ahead();         // behind the first xi after the barrier
             if constexpr (x == WN_BAR + 1 || x == WN_BAR + 2) {
                 constexpr int y = 2 * (x - WN_BAR - 1);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(MP & 4)) {
-                    wn_read2<y * 1024>(fa[y], fb[y], ub + nb, vb + nb);
-                    wn_read2<(y + 1) * 1024>(fa[y + 1], fb[y + 1], ub + nb, vb + nb);
-                }
+                wn_read2<y * 1024>(fa[y], fb[y], ub + nb, vb + nb);
+                wn_read2<(y + 1) * 1024>(fa[y + 1], fb[y + 1], ub + nb, vb + nb);
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
         slot = ns;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the look-ahead reads of the stage after the last
-#ifdef WN_STAMPS
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-#endif
 
     // ------------------------------------------------------------------ output transform + epilogue through LDS
     // A^T = [1 1 1 0; 0 1 -1 -1]. From registers a lane would store 16 bytes of 16 different pixels per instruction (32-byte pieces
@@ -363,13 +316,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
         pix[it] = pv[it] ? tab[tl] + (pp & 1) + (pp >> 1) * p.W : 0;
     }
     f32x4 rr[16];
-    if (RES && EP != 1) {
+    if (RES) {
 #pragma unroll
         for (int it = 0; it < 16; ++it)
             rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
-    } else if (RES) {
-#pragma unroll
-        for (int it = 0; it < 16; ++it) rr[it] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     __builtin_amdgcn_sched_barrier(0);                                // all residual rows are requested before the transform starts
     {
@@ -396,10 +346,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
                 }
             }
 #pragma unroll
-            for (int pp = 0; pp < 4; ++pp) {
-                if constexpr (EP == 3) { asm volatile("" :: "v"(o[pp])); continue; }
-                *reinterpret_cast<f32x4*>(dst + pp * 64 * OLD + 8 * g) = o[pp];
-            }
+            for (int pp = 0; pp < 4; ++pp) *reinterpret_cast<f32x4*>(dst + pp * 64 * OLD + 8 * g) = o[pp];
         }
     }
     __syncthreads();
@@ -413,24 +360,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino_f32(const WinoArgs p) {
         if (RES) v += rr[it];
         if (pv[it]) {
             saw_nan |= (v[0] != v[0]) | (v[1] != v[1]) | (v[2] != v[2]) | (v[3] != v[3]);
-            if constexpr (EP == 0 || EP == 3) asm volatile("" :: "v"(v));
-            else *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = v;
+            *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = v;
         }
     }
-#ifdef WN_STAMPS
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        unsigned long long* d = reinterpret_cast<unsigned long long*>(p.nan_flag) + (size_t)blockIdx.x * 6;
-        d[0] = st0; d[1] = st1; d[2] = st2; d[3] = st3; d[4] = hwid; d[5] = xcc;
-    }
-    (void)saw_nan;
-#else
     if ((p.flags & YOLO_FLAG_NANCHECK) && saw_nan) atomicOr(p.nan_flag, 2);
-#endif
 }
 
 // ------------------------------------------------------------------------------ the same launch in TWO PASSES over xi, two workgroups per CU
@@ -455,10 +388,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino2_f32(const WinoArgs p) {
     const int nt = q % p.n_nt, mt = (q / p.n_nt) * 8 + xcd;
     if (mt >= p.n_mt) return;
     const int wm = wave & 1, wn = wave >> 1;
-#ifdef WN_STAMPS
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-    unsigned long long st1 = 0;
-#endif
 
     // ---- DMA roles: this wave moves xi = 8 pass + 2 wave, + 1 of V and of U, lane = row
     const size_t v_xi = (size_t)p.C4 * p.Tpad * 4, v_c4 = (size_t)p.Tpad * 4;
@@ -509,10 +438,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino2_f32(const WinoArgs p) {
         else wn_wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-#ifdef WN_STAMPS
-        if constexpr (pass == 0) st1 = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
         wn_read2<0>(fa[0], fb[0], ub, vb);
         wn_read2<1024>(fa[1], fb[1], ub, vb);
 
@@ -584,10 +509,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino2_f32(const WinoArgs p) {
     };
     run_pass(std::integral_constant<int, 0>{});
     run_pass(std::integral_constant<int, 1>{});
-#ifdef WN_STAMPS
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-#endif
 
     // ------------------------------------------------------------------ epilogue through LDS
     // The RAW output tile is staged ([pixel of the tile][tile][64 + 4] over the idle ring); the threads that store (16 lanes per
@@ -656,28 +577,10 @@ __global__ __launch_bounds__(256, 2) void conv_wino2_f32(const WinoArgs p) {
             if (pv[it]) *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = va[i8];
         }
     }
-#ifdef WN_STAMPS
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        unsigned long long* d = reinterpret_cast<unsigned long long*>(p.nan_flag) + (size_t)blockIdx.x * 6;
-        d[0] = st0; d[1] = st1; d[2] = st2; d[3] = st3; d[4] = hwid; d[5] = xcc;
-    }
-    (void)saw_nan;
-#else
     if ((p.flags & YOLO_FLAG_NANCHECK) && saw_nan) atomicOr(p.nan_flag, 2);
-#endif
 }
 
 // ------------------------------------------------------------------------------ host side
-static const bool g_wino_off = getenv("YOLO_NO_WINOGRAD") != nullptr;     // A/B switch: the direct kernels
-// conv_wino2_f32 (two passes, two workgroups per CU) for feature maps of at most this many pixels (shape rule, never the batch):
-// measured 292-297 vs 315-321 us at 13 x 13, equal at 26 x 26 / 52 x 52, 442 vs 372 us at 104 x 104. YOLO_WINO2_MAXPIX=0 switches it off.
-static const long long g_wino2_maxpix = getenv("YOLO_WINO2_MAXPIX") ? atoll(getenv("YOLO_WINO2_MAXPIX")) : 256;
-
 size_t wino_weight_elems(int cout, int cin, int ks) {
     if (ks != 3 || cin % 4) return 0;
     return (size_t)16 * (cin / 4) * round_up(cout, 64) * 4;
@@ -716,7 +619,7 @@ bool wino_supported(const yolo_conv_desc* d) {
 // the heuristic: where the 16 GEMMs are long enough to pay for the transform pass and the 4x larger operand stream.
 // Looks at the layer's shape only, never at the batch size (an image's result may not depend on its neighbours).
 bool wino_eligible(const yolo_conv_desc* d) {
-    if (g_wino_off || !wino_supported(d)) return false;
+    if (switches().no_winograd || !wino_supported(d)) return false;           // (A/B switch: the direct kernels)
     // measured at batch 32 (tools/conv_bench.py --tile 13 / 7): 64 -> 128 at 104 x 104 387 vs 433-460 us, 128 -> 256 at 52 x 52 353 vs
     // 425-470, 256 -> 512 at 26 x 26 274 vs 440-515, 512 -> 1024 at 13 x 13 313-323 vs 430; 32 -> 64 at 208 x 208 would be 8 stages per
     // workgroup behind a 709 MB transform pass: stays direct
@@ -752,7 +655,10 @@ int conv_wino_launch(const yolo_conv_desc* d, const void* x, const float* U, con
     a.n_mt = Tpad / 64; a.n_nt = a.CoutPad / 64;
     const int grid = 8 * a.n_nt * ceil_div(a.n_mt, 8);
     const bool res = d->flags & YOLO_FLAG_RESIDUAL;
-    if (d->tile == 14 || (d->tile != 13 && d->tile < 16 && (long long)d->h * d->w <= g_wino2_maxpix)) {       // two passes over xi, two workgroups per CU (conv_wino2_f32)
+    // conv_wino2_f32 (two passes over xi, two workgroups per CU): tile 14, or the heuristic on feature maps of at most wino2_maxpix
+    // pixels (256; shape rule, never the batch): measured 292-297 vs 315-321 us at 13 x 13, equal at 26 x 26 / 52 x 52, 442 vs 372 us at
+    // 104 x 104. YOLO_WINO2_MAXPIX=0 switches it off.
+    if (d->tile == kTileF32Wino2 || (d->tile == 0 && (long long)d->h * d->w <= switches().wino2_maxpix)) {
         const size_t lds2 = (size_t)256 * 68 * 4 + 512;                        // the store staging (> the 64 KiB ring)
         auto go2 = [&](auto kern) -> int {
             static LdsOnce once;
@@ -770,19 +676,6 @@ int conv_wino_launch(const yolo_conv_desc* d, const void* x, const float* U, con
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
         return check_launch("conv_wino_f32");
     };
-#ifdef WN_STAMPS
-    switch (d->tile >= 16 ? d->tile - 16 : 0) {          // timing probes: tile 16 + bits
-    case 1: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 1>);
-    case 2: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 2>);
-    case 3: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 3>);
-    case 4: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 4>);
-    case 7: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 7>);
-    case 8: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 8>);
-    case 9: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 9>);
-    case 11: return go(&conv_wino_f32<YOLO_ACT_LEAKY, true, 11>);
-    default: break;
-    }
-#endif
     YOLO_SWITCH_ACT(d->act, return res ? go(&conv_wino_f32<ACT, true>) : go(&conv_wino_f32<ACT, false>));
     return fail(YOLO_ERR_ARG, "conv winograd: activation");
 }

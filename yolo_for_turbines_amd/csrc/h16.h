@@ -11,7 +11,6 @@
 // shift, LeakyReLU / Mish, residual) in fp32, one rounding to 16-bit at the store.
 #pragma once
 #include "common.h"
-#include <cstdlib>
 
 namespace yolo {
 
@@ -136,10 +135,6 @@ inline size_t cls_frag_elems(int cin, int cout, int cls) {       // N = cin (dx 
 }
 
 // ------------------------------------------------------------------------------ host side
-// documented A/B switches, read once at load
-inline const bool g_h_stagger = !(getenv("YOLO_NO_STAGGER"));
-inline const bool g_h_prio = !(getenv("YOLO_DMA_PRIO") && getenv("YOLO_DMA_PRIO")[0] == '0');
-
 inline void fill_magics(ConvHArgs& a) {
     a.mg_H = magic_of(a.H); a.mg_TW = magic_of(a.TW); a.mg_PC = magic_of(a.PC);
     a.mg_tn = magic_of(a.tiles_n); a.mg_tw = magic_of(a.tiles_w); a.mg_Hp = magic_of(a.Hin + 2);
@@ -154,7 +149,7 @@ inline void tile_grid_h(ConvHArgs& a, int bn) {
     fill_magics(a);
     a.first_wave = 2 * 256;
     const long mfma_cycles = (long)a.KT * 8 * (bn / 64) / 2 * 32;      // one block's matrix cycles per wave
-    a.stagger = g_h_stagger ? (int)((mfma_cycles + 1024) / 2048) : 0;   // s_sleep 32 = 2048 cycles
+    a.stagger = !switches().no_stagger ? (int)((mfma_cycles + 1024) / 2048) : 0;   // s_sleep 32 = 2048 cycles
 }
 
 // ---- one launcher per kernel family; conv_h16.hip fills the ConvHArgs and picks one

@@ -235,8 +235,7 @@ __global__ void pack_dgrad_s2_cls_h16(const float* __restrict__ w, unsigned shor
 // launches each read all of dz and write a quarter of dx in half-line pieces, HBM-bound at 2.5 TB/s (4 x ~97 us for the
 // 64-channel layers); here dz is read once and dx written once in full 16-byte rows.
 bool s2g_ok(int cout, int cin) {
-    static const bool off = getenv("YOLO_NO_S2G") != nullptr;
-    return !off && (cin == 32 || cin == 64) && cout % 32 == 0 && cout >= 32;
+    return !switches().no_s2g && (cin == 32 || cin == 64) && cout % 32 == 0 && cout >= 32;
 }
 static size_t s2g_frag_elems(int cout, int cin) { return s2g_ok(cout, cin) ? (size_t)(4 * cin / 32) * (4 * cout / 32) * 1024 : 0; }
 

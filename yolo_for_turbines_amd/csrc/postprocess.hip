@@ -1370,8 +1370,6 @@ __global__ __launch_bounds__(1024) void nms_scan_classes_kernel(const unsigned l
     }
 }
 
-static const bool g_nms_rocprim = getenv("YOLO_NMS_ROCPRIM") != nullptr;       // A/B switch: the library sorts instead of the chunk sort + rank merge
-
 struct NmsWs { int* nvalid; unsigned long long* row_any; int* order; SBox* sbox; unsigned long long* mask; size_t zero_bytes; size_t total;
                unsigned long long* keys_in; unsigned long long* keys_out; void* sort_tmp; size_t sort_tmp_bytes;
                int* grank; int* blk_lo; int* blk_hi; int* chunk_valid; unsigned long long* chunked;
@@ -1522,7 +1520,7 @@ int yolo_nms(const float* boxes, int b, int n, double iou_threshold, double obj_
     const bool sorted_keys = n >= 2048 && n < (1 << 20) && b <= 2047;      // large n: sort the keys instead of counting
     const size_t fixed = (size_t)W * 16 + 128;              // class-range scan: kept words, lo/hi, count, cuts ...
     int K = (int)((60 * 1024 - (long long)fixed) / (long long)((size_t)W * 8));   // ... and one removed[] array per wave, in LDS
-    const bool own_order = sorted_keys && K >= 1 && n <= SC * SC_MAXCH && !g_nms_rocprim;   // chunk sort + rank merge: they zero what they need
+    const bool own_order = sorted_keys && K >= 1 && n <= SC * SC_MAXCH && !switches().nms_rocprim;   // chunk sort + rank merge: they zero what they need
     if (!own_order && hipMemsetAsync(w.nvalid, 0, w.zero_bytes, st) != hipSuccess) return fail(YOLO_ERR_LAUNCH, "nms: memset");
     K = K > 16 ? 16 : K;
     const dim3 gn(ceil_div(n, 256), b);
@@ -1539,7 +1537,7 @@ int yolo_nms(const float* boxes, int b, int n, double iou_threshold, double obj_
     } else if (sorted_keys) {                               // + class-sorted rows
         int* slot = (int*)w.keys_in;                        // kept boxes by global rank, -1 elsewhere (library-sort path only)
         const unsigned long long* order1 = nullptr;         // order 1 when it survives to the scan (chunk-sort path)
-        if (n <= SC * SC_MAXCH && !g_nms_rocprim) {          // both orders by the chunk sort + rank merge kernels (4 launches)
+        if (n <= SC * SC_MAXCH && !switches().nms_rocprim) {          // both orders by the chunk sort + rank merge kernels (4 launches)
             const int nch = ceil_div(n, SC);
             const dim3 ga(nch, b), gb(nch * 8, b);
             hipLaunchKernelGGL(nms_chunksort_kernel<1>, ga, dim3(SC_THREADS), 0, st, boxes, (const unsigned long long*)nullptr, (const int*)nullptr, n,

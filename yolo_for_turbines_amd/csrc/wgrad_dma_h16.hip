@@ -400,8 +400,7 @@ static WgradDPlan plan_wgrad_d(int n, int h, int w, int cin, int cout) {
 }
 
 bool wgrad_dma_eligible(int cin, int cout, int ks, int stride, int dz_ld, int dz_off, int x_ld, int x_off) {
-    static const bool off = getenv("YOLO_NO_WGRAD_DMA") != nullptr;      // A/B switch: round 2's kernel
-    if (off || ks != 3 || stride != 1 || cin < 32) return false;         // (the 3-channel stem stays on wgrad_patch_h16)
+    if (switches().no_wgrad_dma || ks != 3 || stride != 1 || cin < 32) return false;         // (the 3-channel stem stays on wgrad_patch_h16)
     if ((dz_ld & 7) || (dz_off & 7) || (x_ld & 7) || (x_off & 7)) return false;
     return dz_ld >= round_up(cout, 8) && x_ld >= round_up(cin, 8);
 }
@@ -425,9 +424,8 @@ int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x
     a.th_tiles = q.th_tiles; a.tw_tiles = q.tw_tiles; a.total_tiles = q.total_tiles;
     a.tiles_per_slice = q.tiles_per_slice; a.nslices = q.nslices;
     const int grid = a.ntile * a.nslices;
-    static const int la = getenv("YOLO_WGRAD_LA") ? atoi(getenv("YOLO_WGRAD_LA")) : 3;        // tuning knobs (A/B runs)
-    static const int prio = getenv("YOLO_WGRAD_PRIO") ? atoi(getenv("YOLO_WGRAD_PRIO")) : 0;
-    a.prio = prio;
+    const int la = switches().wgrad_la;                     // tuning knobs (A/B runs)
+    a.prio = switches().wgrad_prio;
     auto go3 = [&](auto kern) -> int {
         static LdsOnce once;                                // one per instantiation of this generic lambda
         if (int rc = reserve_lds(once, reinterpret_cast<const void*>(kern), WD_LDS, "wgrad3_dma_h16")) return rc;

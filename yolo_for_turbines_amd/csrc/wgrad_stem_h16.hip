@@ -219,14 +219,12 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce(const float* __restrict
 
 static int stem_wgrad_blocks(long long segs) {
     long long nb = (segs + 4 * SW_NSEG * 4 - 1) / (4 * SW_NSEG * 4);       // at least four batches per wave
-    static const int cap = getenv("YOLO_STEM_WGRAD_BLOCKS") ? atoi(getenv("YOLO_STEM_WGRAD_BLOCKS")) : 256;
-    if (nb > cap) nb = cap;                                               // one workgroup per CU (96 KiB of LDS each)
+    if (nb > switches().stem_wgrad_blocks) nb = switches().stem_wgrad_blocks;      // (256: one workgroup per CU, 96 KiB of LDS each)
     return (int)(nb < 1 ? 1 : nb);
 }
 
 bool wgrad_stem_eligible(int n, int h, int w, int cin, int cout, int ksize, int stride, int dz_ld, int dz_off, int x_ld, int x_off) {
-    static const bool off = getenv("YOLO_NO_STEM_WGRAD") != nullptr;
-    if (off || ksize != 3 || stride != 1 || cin < 1 || cin > 3 || cout < 1 || cout > 32) return false;
+    if (switches().no_stem_wgrad || ksize != 3 || stride != 1 || cin < 1 || cin > 3 || cout < 1 || cout > 32) return false;
     if (x_ld != SW_XLD || (x_off & 7) || dz_ld < 32 || (dz_ld & 7) || (dz_off & 7) || (w & 15) || h < 1) return false;
     return (long long)n * h * w <= 0x7fffffffLL;
 }
