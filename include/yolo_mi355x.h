@@ -40,7 +40,9 @@ enum { YOLO_ACT_NONE = 0, YOLO_ACT_LEAKY = 1, YOLO_ACT_MISH = 2 };
  * 222); or the detection-head layout (B,3,g,g,5+nc) contiguous (replaces the reshape + permute
  * of ScalePredictionBlock.forward, model.py:145-148; conv channel = a*(5+nc)+k). */
 enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
-enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2 };
+/* YOLO_FLAG_FILTERS_READY (layers of the Winograd F(4x4) family, tile 15, only): w_packed is not the packed weight buffer but the
+ * transformed filters U4 that yolo_wino4_filters made of it. */
+enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -141,6 +143,19 @@ int yolo_conv_fwd_ws(const yolo_conv_desc* d, const void* x, const void* w_packe
 /* tile id the heuristic would pick (exposed for tests / tuning) and number of tile ids */
 int yolo_conv_pick_tile(const yolo_conv_desc* d);
 int yolo_conv_num_tiles(void);
+/* Winograd F(4x4, 3x3) (tile 15) with the filters transformed once instead of on every launch, for weights that stay the same
+ * from call to call (inference). yolo_wino4_filter_bytes: size of U4 = G g G^T, 36 * cin4_pad2 * cout_pad64 * 16 bytes (it
+ * depends on cin and cout only; 0: the descriptor cannot run as tile 15). yolo_wino4_filters writes U4 (16-byte aligned) from
+ * w_packed (yolo_pack_weights, or yolo_pack_weights_dgrad with flip = 1): the very values a launch without the flag leaves behind
+ * V4 in its workspace. A descriptor with YOLO_FLAG_FILTERS_READY then takes that U4 as the w_packed of yolo_conv_fwd_ws /
+ * yolo_conv_fwd_batch; the workspace size stays what yolo_conv_workspace_bytes reports, its U4 part is left alone. The flag
+ * on a descriptor that does not run as tile 15 is an argument error. */
+size_t yolo_wino4_filter_bytes(const yolo_conv_desc* d);
+int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, void* stream);
+/* How a tile-15 launch is cut on the current device: *whole tile blocks (64 tiles each) run as one workgroup per channel block;
+ * *half tile blocks, those of a last round that would fill at most half the compute units, run as two workgroups of 32 tiles.
+ * The result of a tile does not depend on the cut. */
+int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half);
 
 /* ---- training: batch-statistics BatchNorm, activation, and the conv gradients ------------- */
 /* All of these replace pieces of `grad_scaler.scale(loss).backward()` / the train-mode forward of

@@ -7,6 +7,7 @@
 Layers are the dominant YOLOv3 shapes at batch 32, 416x416.
 """
 import argparse
+import ctypes as C
 import os
 import sys
 
@@ -74,7 +75,12 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32"):
     ms = e0.elapsed_time(e1) / reps
     gflop = 2.0 * batch * Ho * Ho * cout * cin * k * k / 1e9
     picked = (lib.yolo_conv_pick_tile(d) if dtype == "fp32" else 0) if tile == 0 else tile
-    print(f"{name:12s} tile={picked} {ms * 1e3:8.1f} us  {gflop / ms:7.2f} TFLOP/s  ({gflop:.1f} GFLOP)", flush=True)
+    cut = ""
+    if picked == 15:                                              # Winograd F(4x4): how the launch is cut on this device
+        whole, half = C.c_int(), C.c_int()
+        L.check(lib.yolo_conv_wino4_blocks(d, C.byref(whole), C.byref(half)), "yolo_conv_wino4_blocks")
+        cut = f"  tile blocks: {whole.value} whole + {half.value} in halves"
+    print(f"{name:12s} tile={picked} {ms * 1e3:8.1f} us  {gflop / ms:7.2f} TFLOP/s  ({gflop:.1f} GFLOP){cut}", flush=True)
     return ms
 
 

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("YOLO_MI355X_LIB") or os.path.join(_HERE, "libyolo_mi3
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_LEAKY, ACT_MISH = 0, 1, 2
 OUT_NHWC, OUT_UPSAMPLE2X, OUT_HEAD = 0, 1, 2
-FLAG_RESIDUAL, FLAG_NANCHECK = 1, 2
+FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY = 1, 2, 4
 
 
 class PackItem(C.Structure):
@@ -96,6 +96,9 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "yolo_conv_pick_tile": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_num_tiles": (C.c_int, []),
+    "yolo_wino4_filter_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "yolo_wino4_filters": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_conv_wino4_blocks": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "yolo_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_bn_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

@@ -347,6 +347,9 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     if (!x || !w || !scale || !shift || !y) return fail(YOLO_ERR_ARG, "conv: null pointer");
     if ((d->flags & YOLO_FLAG_RESIDUAL) && !residual) return fail(YOLO_ERR_ARG, "conv: residual flag without pointer");
     if ((d->flags & YOLO_FLAG_NANCHECK) && !nan_flag) return fail(YOLO_ERR_ARG, "conv: nancheck flag without pointer");
+    const bool filters_ready = d->flags & YOLO_FLAG_FILTERS_READY;
+    if (filters_ready && (d->dtype != YOLO_F32 || f32_family(d, residual, ws ? ws_bytes : 0) != F32Family::Wino4))
+        return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_READY on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
     if (d->dtype != YOLO_F32) return conv_h16_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     ConvArgs a;
     a.x = (const float*)x; a.w = (const float*)w; a.scale = scale; a.shift = shift;
@@ -367,9 +370,10 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     const bool smallc = a.Cin == 4;
     switch (f32_family(d, residual, ws ? ws_bytes : 0)) {
     case F32Family::Rs: return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
-    case F32Family::Wino4:          // the filters are transformed per launch from the row-major section
+    case F32Family::Wino4:          // the filters are transformed per launch from the row-major section, unless w is their transform
         if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
-        return conv_wino4_launch(d, x, (const float*)w, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
+        return conv_wino4_launch(d, x, filters_ready ? nullptr : (const float*)w, filters_ready ? (const float*)w : nullptr, scale, shift,
+                                 residual, y, ws, ws_bytes, nan_flag, s);
     case F32Family::Wino: {
         if (!wino_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 13 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         const float* U = (const float*)w + v0_packed_elems(d->cout, d->cin, d->ksize) + v2_frag_elems(d->cout, d->cin, d->ksize);

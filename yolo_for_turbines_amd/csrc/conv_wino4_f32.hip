@@ -16,6 +16,8 @@
 //                    U4[xi][c4][co_pad64][4] = (G g G^T)[xi] from the row-major section at the start of the packed weights
 //                    (yolo_pack_weights, and yolo_pack_weights_dgrad with flip = 1 for the stride-1 input gradient). U4 is
 //                    computed per launch and lives in the workspace behind V4: the packed weight format stays as it is.
+//                    Inference, whose weights stay the same from call to call, makes U4 once instead (wino4_filters_f32 through
+//                    yolo_wino4_filters, YOLO_FLAG_FILTERS_READY): the launch then has no filter blocks.
 //   conv_wino4_f32   per workgroup 64 tiles x 64 output channels (the block of conv_wino_f32: the same operand bytes per MFMA, so
 //                    the same LDS-DMA price per matrix cycle): 36 GEMMs D_xi[co][tile] = sum_ci U4_xi[co][ci] V4_xi[tile][ci] in SIX
 //                    passes over K, one row a of the 6x6 product matrix M per pass (xi = 6a .. 6a + 5). Y = A^T M A is linear in the
@@ -24,7 +26,10 @@
 //                    16 x 16 blocks of v_mfma_f32_16x16x4_f32 per xi: 48 accumulators per pass (VGPRs), 128 partial-tile registers
 //                    (parked in the AGPR half between passes). A stage is 8 channels = two planes x 6 xi x (V, U) = 24 KiB.
 //                    Epilogue: BN scale / shift, activation, residual, ld / off views and the NaN flag as in conv_wino_f32,
-//                    staged through LDS one output row of the tile at a time.
+//                    staged through LDS one output row of the tile at a time; the residual is requested one row ahead.
+//                    One workgroup per CU and round: the tile blocks of a last round that would fill at most half the CUs run as
+//                    two workgroups of 32 tiles each (wino4_whole_blocks), the same 16 x 16 MFMA blocks in the same order on half
+//                    the waves, so a tile's bits do not depend on the cut.
 #include "wino_dma.h"
 
 namespace yolo {
@@ -68,31 +73,41 @@ struct Wino4XArgs {
     long long utotal;        // C4p * coutp * 4: one thread per (ci, co) pair computes all 36 xi
 };
 
+// U4 = G g G^T: element i = (c4, co, e) of every xi plane, for i = first, first + stride, ... One function for the per-launch
+// blocks of wino4_xform_f32 and for wino4_filters_f32 (yolo_wino4_filters), so both write the same bits.
+__device__ __forceinline__ void wino4_filter_elems(const Wino4XArgs& p, long long first, long long stride) {
+    for (long long i = first; i < p.utotal; i += stride) {
+        const int e = (int)(i & 3);
+        const long long r = i >> 2;
+        const int co = (int)(r % p.coutp), c4 = (int)(r / p.coutp);
+        const int ci = 4 * c4 + e;
+        double g[3][3];
+        const bool ok = co < p.cout && ci < p.cin;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = ok ? (double)p.w[(size_t)co * p.kpad + k * p.cinp + ci] : 0.0;
+        double t[6][3];                                  // G g
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) t[j][q] = W4_G[j][0] * g[0][q] + W4_G[j][1] * g[1][q] + W4_G[j][2] * g[2][q];
+        float* dst = p.U + i;
+        const size_t xs = (size_t)p.C4p * p.coutp * 4;
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+#pragma unroll
+            for (int l = 0; l < 6; ++l)
+                dst[(6 * j + l) * xs] = (float)(t[j][0] * W4_G[l][0] + t[j][1] * W4_G[l][1] + t[j][2] * W4_G[l][2]);
+    }
+}
+
+// the filters alone, once per weight update (yolo_wino4_filters): only w, U and the filter geometry of the arguments are read
+__global__ __launch_bounds__(256) void wino4_filters_f32(const Wino4XArgs p) {
+    wino4_filter_elems(p, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
 __global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
     if ((int)blockIdx.x >= p.nxb) {
-        const long long stride = (long long)(gridDim.x - p.nxb) * blockDim.x;
-        for (long long i = (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x; i < p.utotal; i += stride) {
-            const int e = (int)(i & 3);
-            const long long r = i >> 2;
-            const int co = (int)(r % p.coutp), c4 = (int)(r / p.coutp);
-            const int ci = 4 * c4 + e;
-            double g[3][3];
-            const bool ok = co < p.cout && ci < p.cin;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = ok ? (double)p.w[(size_t)co * p.kpad + k * p.cinp + ci] : 0.0;
-            double t[6][3];                                  // G g
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) t[j][q] = W4_G[j][0] * g[0][q] + W4_G[j][1] * g[1][q] + W4_G[j][2] * g[2][q];
-            float* dst = p.U + i;
-            const size_t xs = (size_t)p.C4p * p.coutp * 4;
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int l = 0; l < 6; ++l)
-                    dst[(6 * j + l) * xs] = (float)(t[j][0] * W4_G[l][0] + t[j][1] * W4_G[l][1] + t[j][2] * W4_G[l][2]);
-        }
+        wino4_filter_elems(p, (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x, (long long)(gridDim.x - p.nxb) * blockDim.x);
         return;
     }
     // 8 lanes = the 8 channel quads of one pixel's 128-byte line, 8 tiles per wave (the access pattern of wino_xform_f32)
@@ -164,11 +179,13 @@ struct Wino4Args {
     int y_ld, y_off, r_ld, r_off;
     int flags;
     int n_mt, n_nt;
+    int n_whole;             // tile blocks 0 .. n_whole - 1 run as one workgroup each, the rest as two workgroups of 32 tiles
 };
 
 constexpr int W4_STAGE = 24576;          // bytes per ring stage: V [2 planes][6 xi][64][4] floats, then U the same
 constexpr int W4_SLOTS = 4;              // (a power of two: slot arithmetic by mask)
 constexpr int W4_DMA = 3;                // DMA wave-instructions per wave and stage
+constexpr int W4_TAB = 512;              // bytes behind the ring: the epilogue's tile table
 
 // fragments of one sub-step: the U row (A operand) and the V rows of the wave's two tile blocks (B operands)
 template <int OFF>
@@ -186,10 +203,34 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, kq = lane >> 4;
+    // block map: 8 tile blocks (one per XCD) x all channel blocks per row, so the channel blocks of a tile block share an L2. The
+    // rows of the whole tile blocks come first; each row of 8 tail blocks then comes twice, once per half
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int nt = q % p.n_nt, mt = (q / p.n_nt) * 8 + xcd;
-    if (mt >= p.n_mt) return;
-    const int wm = wave & 1, wn = wave >> 1;
+    const int nt = q % p.n_nt, row = q / p.n_nt;
+    const int wrows = (p.n_whole + 7) >> 3;
+    const bool cut = row >= wrows;
+    const int half = (row - wrows) & 1;
+    const int mt = cut ? p.n_whole + ((row - wrows) >> 1) * 8 + xcd : row * 8 + xcd;
+    if (mt >= (cut ? p.n_mt : p.n_whole)) return;
+    // a half workgroup covers tiles 32 half .. + 31 of its block: waves 0 .. 3 (one per SIMD) take the 16 channels each of that
+    // half, the same 16 x 16 blocks in the same order as in a whole workgroup; waves 4 .. 7 only move their DMA pieces
+    const int wm = cut ? half : wave & 1, wn = cut ? wave & 3 : wave >> 1;
+    const bool busy = !cut || wave < 4;
+
+    // the epilogue's table: [64] first output pixel of the tile, [64] valid rows << 4 | columns (0: no such tile, or the other
+    // half's); visible to everybody after the first barrier of the K loop
+    int* tab = reinterpret_cast<int*>(smem + W4_SLOTS * W4_STAGE);
+    if (tid < 64) {
+        const int t = mt * 64 + tid;
+        const bool tv = t < p.T && (!cut || (tid >> 5) == half);
+        const int tt = tv ? t : 0;
+        const int per = p.th * p.tw;
+        const int n = tt / per, rem = tt - n * per;
+        const int ty = rem / p.tw, tx = rem - ty * p.tw;
+        const int nr = p.H - 4 * ty < 4 ? p.H - 4 * ty : 4, nc = p.W - 4 * tx < 4 ? p.W - 4 * tx : 4;
+        tab[tid] = (n * p.H + 4 * ty) * p.W + 4 * tx;
+        tab[64 + tid] = tv ? (nr << 4 | nc) : 0;
+    }
 
     // ---- DMA roles: waves 2 grp, 2 grp + 1 move part grp of a stage (0 / 1: plane 0 / 1 of V, 2 / 3: the same planes of U),
     // three xi each; lane = row
@@ -323,29 +364,46 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(py[bb][i][j]));
     };
-    run_pass(std::integral_constant<int, 0>{});
-    run_pass(std::integral_constant<int, 1>{});
-    run_pass(std::integral_constant<int, 2>{});
-    run_pass(std::integral_constant<int, 3>{});
-    run_pass(std::integral_constant<int, 4>{});
-    run_pass(std::integral_constant<int, 5>{});
+    if (busy) {
+        run_pass(std::integral_constant<int, 0>{});
+        run_pass(std::integral_constant<int, 1>{});
+        run_pass(std::integral_constant<int, 2>{});
+        run_pass(std::integral_constant<int, 3>{});
+        run_pass(std::integral_constant<int, 4>{});
+        run_pass(std::integral_constant<int, 5>{});
+    } else {
+        // the idle waves of a half workgroup: the DMA pieces, the waits and the barriers of run_pass, in the same places
+        for (int a = 0; a < 6; ++a) {
+            if (a == 0) {
+                issue(0, 0, 0);
+                if (nst > 1) issue(0, 1, 1);
+                if (nst > 2) issue(0, 2, 2);
+            }
+            if (nst > 2) wn_wait_vmcnt<2 * W4_DMA>();
+            else if (nst > 1) wn_wait_vmcnt<W4_DMA>();
+            else wn_wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            int slot = 0;
+            for (int st = 0; st < nst; ++st) {
+                if (st >= 1 && st + 2 < nst) issue(a, st + 2, (slot + 2) & (W4_SLOTS - 1));
+                if (st + 2 < nst) wn_wait_vmcnt<W4_DMA>();
+                else wn_wait_vmcnt<0>();
+                __builtin_amdgcn_s_barrier();
+                slot = (slot + 1) & (W4_SLOTS - 1);
+            }
+            __syncthreads();
+            if (a < 5) {
+                issue(a + 1, 0, 0);
+                if (nst > 1) issue(a + 1, 1, 1);
+                if (nst > 2) issue(a + 1, 2, 2);
+            }
+        }
+    }
 
     // ------------------------------------------------------------------ epilogue through LDS, one output row i of the tiles at a time
     // ([pixel j][tile][64 + 4] over the idle ring, 16 lanes per pixel row: stores and residual loads are 256-byte runs)
     constexpr int OLD = 68;
     float* ost = reinterpret_cast<float*>(smem);
-    int* tab = reinterpret_cast<int*>(smem + 256 * OLD * 4);        // [64] first output pixel of the tile, [64] valid rows << 4 | columns
-    if (tid < 64) {
-        const int t = mt * 64 + tid;
-        const bool tv = t < p.T;
-        const int tt = tv ? t : 0;
-        const int per = p.th * p.tw;
-        const int n = tt / per, rem = tt - n * per;
-        const int ty = rem / p.tw, tx = rem - ty * p.tw;
-        const int nr = p.H - 4 * ty < 4 ? p.H - 4 * ty : 4, nc = p.W - 4 * tx < 4 ? p.W - 4 * tx : 4;
-        tab[tid] = (n * p.H + 4 * ty) * p.W + 4 * tx;
-        tab[64 + tid] = tv ? (nr << 4 | nc) : 0;
-    }
     // scale / shift of the 4 channels this thread STORES (4 (tid % 16) .. of the block); requested here, not at kernel start:
     // eight registers less through the K loops
     const int c16 = tid & 15;
@@ -353,21 +411,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
     const bool cv = co_t < p.Cout;
     const f32x4 sc_t = *reinterpret_cast<const f32x4*>(p.scale + (cv ? co_t : 0));
     const f32x4 sh_t = *reinterpret_cast<const f32x4*>(p.shift + (cv ? co_t : 0));
-    bool saw_nan = false;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i > 0) __syncthreads();                                  // the previous row's staging has been read back
-        {
-            float* dst = ost + (32 * wm + l16) * OLD + 16 * wn + 4 * kq;
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(dst + (j * 64 + 16 * bb) * OLD) = py[bb][i][j];
-        }
-        __syncthreads();
-        // this thread's 8 rows of the staged row: pixel j = it / 2 of tile (tid / 16) + 32 (it % 2), channels 4 (tid % 16) ..
-        int pix[8];
-        bool pv[8];
+    // this thread's 8 rows of staged row i: pixel j = it / 2 of tile (tid / 16) + 32 (it % 2), channels 4 (tid % 16) ..
+    auto row_pixels = [&](int i, int (&pix)[8], bool (&pv)[8]) {
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int tl = (tid >> 4) + 32 * (it & 1), j = it >> 1;
@@ -375,13 +420,38 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
             pv[it] = cv && j < (fl & 15) && i < (fl >> 4);
             pix[it] = pv[it] ? tab[tl] + i * p.W + j : 0;
         }
-        f32x4 rr[8];
-        if (RES) {
+    };
+    auto request_res = [&](const int (&pix)[8], f32x4 (&rr)[8]) {
 #pragma unroll
-            for (int it = 0; it < 8; ++it)
-                rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
+        for (int it = 0; it < 8; ++it)
+            rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
+    };
+    // the residual runs one output row ahead: row 0 is requested before the first staging barrier, row i + 1 once row i has taken
+    // its residual and before it is stored (rr is free again there, so the look-ahead costs no registers; the loads are older
+    // than the stores, so waiting for them does not wait for the stores)
+    f32x4 rr[8];
+    if (RES) {
+        int pix[8];
+        bool pv[8];
+        row_pixels(0, pix, pv);
+        request_res(pix, rr);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    bool saw_nan = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i > 0) __syncthreads();                                  // the previous row's staging has been read back
+        if (busy) {
+            float* dst = ost + (32 * wm + l16) * OLD + 16 * wn + 4 * kq;
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(dst + (j * 64 + 16 * bb) * OLD) = py[bb][i][j];
         }
-        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        int pix[8];
+        bool pv[8];
+        row_pixels(i, pix, pv);
         f32x4 va[8];
 #pragma unroll
         for (int it = 0; it < 8; ++it)
@@ -397,6 +467,13 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
         }
 #pragma unroll
         for (int it = 0; it < 8; ++it) asm volatile("" : "+v"(va[it]));
+        if (RES && i < 3) {
+            int npix[8];
+            bool npv[8];
+            row_pixels(i + 1, npix, npv);
+            request_res(npix, rr);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int it = 0; it < 8; ++it)
             if (pv[it]) *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = va[it];
@@ -433,39 +510,80 @@ size_t wino4_workspace_bytes(const yolo_conv_desc* d) {
     return 36 * C4p * (Tpad + CoutPad) * 4 * sizeof(float);
 }
 
-// w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad)
-int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* scale, const float* shift,
+// compute units of the current device, asked once per device (0: no device)
+static int wino4_num_cus() {
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int n = cus[dev & 63].load(std::memory_order_relaxed);
+    if (n > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) { (void)hipGetLastError(); return 0; }
+    cus[dev & 63].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+// How a launch of n_mt tile blocks x n_nt channel blocks is cut, one workgroup per CU and round: the tile blocks of the full rounds
+// stay whole (all channel blocks of a tile block together). If the rest is at most half a round of workgroups, each of its tile
+// blocks runs as two workgroups of 32 tiles, so the short last round uses twice the CUs for half the multiply work each.
+// Looks at (n_mt, n_nt, CUs) only; the arithmetic of a tile does not depend on the cut.
+static int wino4_whole_blocks(int n_mt, int n_nt, int cus) {
+    if (cus <= 0) return n_mt;
+    const long long wgs = (long long)n_mt * n_nt;
+    const int whole = (int)(wgs / cus * cus / n_nt);
+    const long long tail = (long long)(n_mt - whole) * n_nt;
+    return tail == 0 || 2 * tail > cus ? n_mt : whole;
+}
+
+static void wino4_filter_args(Wino4XArgs& xa, const yolo_conv_desc* d, const float* w_rm, float* U) {
+    const int C4p = round_up(d->cin / 4, 2), CoutPad = round_up(d->cout, 64);
+    xa.C4p = C4p;
+    xa.w = w_rm; xa.U = U; xa.cout = d->cout; xa.cin = d->cin; xa.coutp = CoutPad; xa.cinp = cin_pad_of(d->cin); xa.kpad = kpad_of(d->cin, 3);
+    xa.utotal = (long long)C4p * CoutPad * 4;
+}
+static int wino4_filter_blocks(const Wino4XArgs& xa) {
+    const long long ub = (xa.utotal + 255) / 256;
+    return (int)(ub < 1024 ? ub : 1024);
+}
+
+size_t wino4_filter_bytes(const yolo_conv_desc* d) {
+    if (!wino4_supported(d)) return 0;
+    return (size_t)36 * round_up(d->cin / 4, 2) * round_up(d->cout, 64) * 4 * sizeof(float);
+}
+
+// w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad); U4_ready: the
+// filters transformed before (yolo_wino4_filters), or NULL: this launch transforms them into the workspace behind V4
+int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
     if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4): needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
     const size_t need = wino4_workspace_bytes(d);
     if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4): workspace %zu < %zu bytes", workspace_bytes, need);
     if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4): workspace must be 16-byte aligned");
+    if ((size_t)U4_ready & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4): transformed filters must be 16-byte aligned");
     const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
     const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4, C4p = round_up(C4, 2);
     const int CoutPad = round_up(d->cout, 64);
     float* V = (float*)workspace;
     float* U = V + (size_t)36 * C4p * Tpad * 4;
     Wino4XArgs xa;
-    xa.x = (const float*)x; xa.V = V; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.C4p = C4p; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
+    wino4_filter_args(xa, d, w_rm, U);
+    xa.x = (const float*)x; xa.V = V; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
     xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = ceil_div(C4p, 8);
     xa.nxb = (Tpad / 32) * xa.ncg;
-    xa.w = w_rm; xa.U = U; xa.cout = d->cout; xa.cin = d->cin; xa.coutp = CoutPad; xa.cinp = cin_pad_of(d->cin); xa.kpad = kpad_of(d->cin, 3);
-    xa.utotal = (long long)C4p * CoutPad * 4;
-    const long long ub = (xa.utotal + 255) / 256;
-    const int nub = (int)(ub < 1024 ? ub : 1024);
+    const int nub = U4_ready ? 0 : wino4_filter_blocks(xa);
     hipLaunchKernelGGL(wino4_xform_f32, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
     if (int rc = check_launch("wino4_xform_f32")) return rc;
 
     Wino4Args a;
-    a.V = V; a.U = U; a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y;
+    a.V = V; a.U = U4_ready ? U4_ready : U; a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y;
     a.nan_flag = nan_flag;
     a.T = T; a.Tpad = Tpad; a.C4p = C4p; a.Cout = d->cout; a.CoutPad = CoutPad;
     a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
     a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
     a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64;
-    const int grid = 8 * a.n_nt * ceil_div(a.n_mt, 8);
+    a.n_whole = wino4_whole_blocks(a.n_mt, a.n_nt, wino4_num_cus());
+    const int grid = 8 * a.n_nt * (ceil_div(a.n_whole, 8) + 2 * ceil_div(a.n_mt - a.n_whole, 8));
     const bool res = d->flags & YOLO_FLAG_RESIDUAL;
-    const size_t lds = (size_t)W4_SLOTS * W4_STAGE;                  // (> the epilogue's staging, 256 x 68 x 4 + 512)
+    const size_t lds = (size_t)W4_SLOTS * W4_STAGE + W4_TAB;         // (the epilogue's staging, 256 x 68 x 4, lies over the idle ring)
     auto go = [&](auto kern) -> int {
         static LdsOnce once;
         if (int rc = reserve_lds(once, reinterpret_cast<const void*>(kern), lds, "conv_wino4_f32")) return rc;
@@ -477,3 +595,32 @@ int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm,
 }
 
 }  // namespace yolo
+
+extern "C" {
+
+size_t yolo_wino4_filter_bytes(const yolo_conv_desc* d) { return d ? yolo::wino4_filter_bytes(d) : 0; }
+
+int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, void* stream) {
+    using namespace yolo;
+    if (!d || !w_packed || !U4) return fail(YOLO_ERR_ARG, "wino4 filters: null pointer");
+    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filters: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    if ((size_t)U4 & 15) return fail(YOLO_ERR_ARG, "wino4 filters: U4 must be 16-byte aligned");
+    Wino4XArgs xa{};
+    wino4_filter_args(xa, d, (const float*)w_packed, (float*)U4);
+    hipLaunchKernelGGL(wino4_filters_f32, dim3((unsigned)wino4_filter_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);
+    return check_launch("wino4_filters_f32");
+}
+
+int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half) {
+    using namespace yolo;
+    if (!d || !whole || !half) return fail(YOLO_ERR_ARG, "wino4 blocks: null pointer");
+    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 blocks: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    const int cus = wino4_num_cus();
+    if (cus <= 0) return fail(YOLO_ERR_LAUNCH, "wino4 blocks: no current device");
+    const int n_mt = (int)((wino4_tiles(d) + 63) / 64), n_nt = round_up(d->cout, 64) / 64;
+    *whole = wino4_whole_blocks(n_mt, n_nt, cus);
+    *half = n_mt - *whole;
+    return YOLO_OK;
+}
+
+}  // extern "C"

@@ -202,6 +202,12 @@ class PackedBlock:
         if stem_ok:
             self.stem_w = torch.empty(27 * cv.out_channels, dtype=torch.float32, device=device)   # [27][cout]
         self.stamp = None                 # conv weight (data_ptr, version) the packed copy was made from
+        # Winograd F(4x4) filters U4 = G g G^T of the packed weights (yolo_wino4_filters), for the eval plans whose launch of
+        # this block picks tile 15: they depend on (cout, cin) only, so one buffer serves every plan. Made in
+        # ModelState._refresh_weights_slow whenever u4_stamp falls behind stamp.
+        self.u4 = None
+        self.u4_desc = None
+        self.u4_stamp = None
         self.fold_stamp = None            # same for the tensors behind scale / shift; None = not folded
         self.folded = False
 
@@ -240,6 +246,22 @@ class PackedBlock:
             return ((conv._parameters, "weight"), (pr, "weight"), (pr, "bias"), (bf, "running_mean"), (bf, "running_var"))
         return ((conv._parameters, "weight"), (conv._parameters, "bias"))
 
+    def want_u4(self, desc):
+        """An eval plan runs this block as Winograd F(4x4) with YOLO_FLAG_FILTERS_READY: own the transformed filters."""
+        if self.u4 is None:
+            n = L.lib().yolo_wino4_filter_bytes(C.byref(desc))
+            if n == 0:
+                raise L.YoloLibError("yolo_wino4_filter_bytes: the layer cannot run as tile 15")
+            self.u4_desc = L.ConvDesc.from_buffer_copy(desc)
+            self.u4 = torch.empty(n, dtype=torch.uint8, device=self.w.device)
+            self.u4_stamp = None
+        return self.u4
+
+    def refresh_u4(self, stream):
+        """U4 from the packed weights as they are now (call after the pack on the same stream)."""
+        L.check(L.lib().yolo_wino4_filters(C.byref(self.u4_desc), self.w.data_ptr(), self.u4.data_ptr(), stream), "yolo_wino4_filters")
+        self.u4_stamp = self.stamp
+
     def refresh(self, block, stream, fold_bn=True, conv_packed=False, pack=True):
         """fold_bn=False (training: batch statistics are used, not the running ones) skips the BN fold.
         conv_packed: the conv weights were already written by a batched pack (ModelState.refresh_weights).
@@ -250,6 +272,7 @@ class PackedBlock:
         if w.dtype != torch.float32 or not w.is_contiguous():
             w = w.float().contiguous()
         if pack:
+            self.u4_stamp = None          # (the training path re-packs every step and never reads U4: it is re-made on the eval side)
             if self.packs_conv and not conv_packed:
                 L.check(lib.yolo_pack_weights(w.data_ptr(), self.w.data_ptr(), cv.out_channels, cv.in_channels,
                                               cv.kernel_size[0], self.code, stream), "yolo_pack_weights")
@@ -350,6 +373,12 @@ class Plan:
             if i >= self.first:
                 e.x = self.phys[x.buf].data_ptr()
             e.w_packed, e.scale, e.shift = pk.w.data_ptr(), pk.scale.data_ptr(), pk.shift.data_ptr()
+            # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
+            if (dtype == "fp32" and i >= self.first and op["k"] == 3 and op["s"] == 1 and (tile_override or 0) in (0, 15)
+                    and L.lib().yolo_conv_workspace_bytes(C.byref(d))
+                    and (d.tile == 15 or L.lib().yolo_conv_pick_tile(C.byref(d)) == 15)):
+                e.w_packed = pk.want_u4(d).data_ptr()
+                d.flags |= L.FLAG_FILTERS_READY
             if i == 0 and self.stem is not None:
                 self.stem_pk = pk
             if op["pred"] is not None:
@@ -461,6 +490,7 @@ class ModelState:
         for per_dev in self._packed.values():
             for pk in per_dev.values():
                 pk.stamp = None
+                pk.u4_stamp = None
                 pk.fold_stamp = None
                 pk.folded = False
         if drop_plans:
@@ -536,6 +566,11 @@ class ModelState:
             pk.refresh(blk, stream, fold_bn, conv_packed=id(pk) in batched)
         for blk, pk in refold:
             pk.refresh(blk, stream, True, pack=False)
+        if fold_bn:                       # eval: the transformed filters of the blocks that keep some follow the packed weights
+            for blk in blocks:
+                pk = self.packed(blk, device, dtype)
+                if pk.u4 is not None and (pk.u4_stamp is None or pk.u4_stamp != pk.stamp):
+                    pk.refresh_u4(stream)
 
     def mark_unfolded(self, blocks):
         """The BatchNorm running statistics of ``blocks`` were just written by a kernel (train-mode forward): every folded
