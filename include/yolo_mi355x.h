@@ -41,8 +41,15 @@ enum { YOLO_ACT_NONE = 0, YOLO_ACT_LEAKY = 1, YOLO_ACT_MISH = 2 };
  * of ScalePredictionBlock.forward, model.py:145-148; conv channel = a*(5+nc)+k). */
 enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
 /* YOLO_FLAG_FILTERS_READY (layers of the Winograd F(4x4) family, tile 15, only): w_packed is not the packed weight buffer but the
- * transformed filters U4 that yolo_wino4_filters made of it. */
-enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4 };
+ * transformed filters U4 that yolo_wino4_filters made of it.
+ * YOLO_FLAG_SPLIT_BF16 (fp32 layers of the direct kernels only: ksize 1 or 3, stride 1 or 2, cin a multiple of 32, no Winograd
+ * workspace in play): the products run on the bf16 matrix cores. Each fp32 operand is split exactly into three bf16 values and six
+ * of the nine partial products are accumulated in fp32, in one fixed order: the result has the accuracy of the fp32 kernel
+ * (measured: DESIGN 4.13) but not its bits. Deterministic, and independent of the batch on finite data. A block of the output (up
+ * to 128 pixels x 128 channels, possibly of two images) that reads an Inf or a NaN is computed with exact fp32 products, all of
+ * it. tile: 0 = heuristic, 1 / 2 / 4 = 128x128 / 128x64 / 64x64 blocks. On any other descriptor the flag is refused with
+ * YOLO_ERR_UNSUPPORTED. Without the flag nothing changes. */
+enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -143,6 +150,12 @@ int yolo_conv_fwd_ws(const yolo_conv_desc* d, const void* x, const void* w_packe
 /* tile id the heuristic would pick (exposed for tests / tuning) and number of tile ids */
 int yolo_conv_pick_tile(const yolo_conv_desc* d);
 int yolo_conv_num_tiles(void);
+/* YOLO_FLAG_SPLIT_BF16 for plans (flags and tile of d are not looked at; the layer's shape only, never the batch).
+ * yolo_conv_split3_supported: 1 when the library honours the flag on a tile-0 launch of d that brings the workspace
+ * yolo_conv_workspace_bytes asks for. yolo_conv_split3_eligible: 1 when, in addition, the shape measured faster that way than
+ * on its exact kernel: what an inference plan should flag. */
+int yolo_conv_split3_supported(const yolo_conv_desc* d);
+int yolo_conv_split3_eligible(const yolo_conv_desc* d);
 /* Winograd F(4x4, 3x3) (tile 15) with the filters transformed once instead of on every launch, for weights that stay the same
  * from call to call (inference). yolo_wino4_filter_bytes: size of U4 = G g G^T, 36 * cin4_pad2 * cout_pad64 * 16 bytes (it
  * depends on cin and cout only; 0: the descriptor cannot run as tile 15). yolo_wino4_filters writes U4 (16-byte aligned) from

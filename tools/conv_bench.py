@@ -2,6 +2,7 @@
 """Single-layer conv micro-benchmark (tuning aid; calls the C-ABI directly).
 
   python tools/conv_bench.py --layer c52_3x3 --tile 0 --reps 20
+  python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3 --rounds 5      (YOLO_FLAG_SPLIT_BF16; median and spread of 5 rounds)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
 
 Layers are the dominant YOLOv3 shapes at batch 32, 416x416.
@@ -34,10 +35,18 @@ LAYERS = {   # name: (H, cin, cout, k, stride)
     "c13_1x1": (13, 1024, 512, 1, 1),
     "c13_3x3": (13, 512, 1024, 3, 1),
     "c13_head": (13, 1024, 255, 1, 1),
+    # the remaining 1x1 shapes of the neck and the other two heads
+    "c52_1x1_384": (52, 384, 128, 1, 1),
+    "c26_1x1_768": (26, 768, 256, 1, 1),
+    "c26_1x1_256": (26, 256, 128, 1, 1),
+    "c13_1x1_512": (13, 512, 256, 1, 1),
+    "c26_head": (26, 512, 255, 1, 1),
+    "c52_head": (52, 256, 255, 1, 1),
 }
+OUT_MODES = {"nhwc": L.OUT_NHWC, "up2x": L.OUT_UPSAMPLE2X, "head": L.OUT_HEAD}
 
 
-def run(name, batch, tile, reps, residual, dev, dtype="fp32"):
+def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1):
     H, cin, cout, k, s = LAYERS[name]
     lib = L.lib()
     cpad = (cin + 3) // 4 * 4
@@ -50,12 +59,12 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32"):
     L.check(lib.yolo_pack_weights(w.data_ptr(), wp.data_ptr(), cout, cin, k, code, stream))
     scale = torch.rand(cout, device=dev) + 0.5
     shift = torch.randn(cout, device=dev) * 0.1
-    y = torch.empty(batch * Ho * Ho * cout, device=dev, dtype=tdt)
+    y = torch.empty(batch * Ho * Ho * cout * (4 if out == "up2x" else 1), device=dev, dtype=tdt if out != "head" else torch.float32)
     r = torch.randn(batch * Ho * Ho * cout, device=dev).to(tdt) if residual else None
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     d = L.ConvDesc(n=batch, h=H, w=H, cin=cin, cout=cout, ksize=k, stride=s, x_ld=cpad, x_off=0, y_ld=cout, y_off=0,
-                   r_ld=cout, r_off=0, act=L.ACT_LEAKY, out_mode=L.OUT_NHWC, dtype=code,
-                   flags=(L.FLAG_RESIDUAL if residual else 0) | L.FLAG_NANCHECK, tile=tile)
+                   r_ld=cout, r_off=0, act=L.ACT_NONE if out == "head" else L.ACT_LEAKY, out_mode=OUT_MODES[out], dtype=code,
+                   flags=(L.FLAG_RESIDUAL if residual else 0) | L.FLAG_NANCHECK | (L.FLAG_SPLIT_BF16 if split3 else 0), tile=tile)
 
     need = lib.yolo_conv_workspace_bytes(d)                       # > 0: Winograd (tile 13, or the heuristic's choice for tile 0)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -66,16 +75,26 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32"):
     for _ in range(3):
         launch()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        launch()
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / reps
+    times = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) / reps)
+    times.sort()
+    ms = times[len(times) // 2]                                   # median round
     gflop = 2.0 * batch * Ho * Ho * cout * cin * k * k / 1e9
     picked = (lib.yolo_conv_pick_tile(d) if dtype == "fp32" else 0) if tile == 0 else tile
     cut = ""
+    if split3:
+        cut += f"  split3 (tile {tile})"
+    if out != "nhwc" or residual:
+        cut += f"  out={out}" + (" +res" if residual else "")
+    if rounds > 1:
+        cut += f"  rounds min/max {times[0] * 1e3:.1f}/{times[-1] * 1e3:.1f} us"
     if picked == 15:                                              # Winograd F(4x4): how the launch is cut on this device
         whole, half = C.c_int(), C.c_int()
         L.check(lib.yolo_conv_wino4_blocks(d, C.byref(whole), C.byref(half)), "yolo_conv_wino4_blocks")
@@ -92,6 +111,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--residual", action="store_true")
     ap.add_argument("--dtype", default="fp32")
+    ap.add_argument("--split3", action="store_true", help="set YOLO_FLAG_SPLIT_BF16 (tile 0, 1, 2 or 4)")
+    ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
+    ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     names = list(LAYERS) if a.layer == "all" else a.layer.split(",")
@@ -99,7 +121,7 @@ def main():
     tiles = list(range(1, nt + 1)) if a.tile == "all" else [int(t) for t in a.tile.split(",")]
     for n in names:
         for t in tiles:
-            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype)
+            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds)
 
 
 if __name__ == "__main__":

@@ -17,31 +17,10 @@
 // (16 different rows, same column chunk) hit 16 different 16-byte slots.  Register-staged
 // double buffering: global loads of step t+1 are issued before the MFMAs of step t and written
 // to the other LDS buffer after them; one barrier per K step.
-#include "common.h"
+#include "conv_f32_epilogue.h"
 
 namespace yolo {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct ConvArgs {
-    const float* x;
-    const float* w;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    float* y;
-    int* nan_flag;
-    int N, H, W, Cin, Cout, Ho, Wo, M;
-    int ks, stride, pad;
-    int x_ld, x_off, y_ld, y_off, r_ld, r_off;
-    int Kpad, KT;
-    int act, out_mode, flags;
-    int nc5;
-    int tiles_n;
-};
-
-constexpr int BK = 32;
 constexpr int LDS_LD = 36;   // padded row length (floats)
 
 
@@ -161,106 +140,8 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(const ConvArgs p) {
         __syncthreads();
     }
 
-    // ---------------------------------------------------------------------- epilogue
-    // C/D map of the 32x32 tile: column (N = cout) = lane & 31, row (M = pixel) =
-    // (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-    const bool has_res = p.flags & YOLO_FLAG_RESIDUAL;
-    const bool nan_chk = p.flags & YOLO_FLAG_NANCHECK;
-    bool saw_nan = false;
-    // NHWC outputs with cout % 4 == 0 (every BN block): scale/shift/activation in registers, transpose the BM x BN tile
-    // through the (now idle) operand LDS, and let every lane move 16 contiguous bytes of one pixel row. The direct stores
-    // below are 4-byte pieces of different rows per lane; on the short 1x1 blocks they were most of the block's life.
-    const bool aligned4 = ((p.y_ld | p.y_off) & 3) == 0 && (!has_res || ((p.r_ld | p.r_off) & 3) == 0);
-    if (p.out_mode != YOLO_OUT_HEAD && (p.Cout & 3) == 0 && aligned4) {
-        constexpr int OLD = BN + 4;
-        float* ost = As;                                   // [BM][OLD] floats <= 2 * (BM + BN) * LDS_LD
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * WN + j * 32 + frow;
-            const bool nv = n < p.Cout;
-            const float sc = nv ? p.scale[n] : 0.f;
-            const float sh = nv ? p.shift[n] : 0.f;
-            float* dst = ost + wn * WN + j * 32 + frow;
-            YOLO_SWITCH_ACT(p.act,
-                _Pragma("unroll") for (int i = 0; i < TM; ++i)
-                    _Pragma("unroll") for (int r = 0; r < 16; ++r) {
-                        const int row = wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                        dst[row * OLD] = act_c<ACT>(acc[i][j][r] * sc + sh);
-                    })
-        }
-        __syncthreads();
-        constexpr int C4 = BN / 4;
-#pragma unroll 4
-        for (int idx = tid; idx < BM * C4; idx += 256) {
-            const int row = idx / C4, c4 = idx - row * C4;
-            const int m = m0 + row, n = n0 + c4 * 4;
-            if (m >= p.M || n >= p.Cout) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(ost + row * OLD + c4 * 4);
-            if (has_res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.r_ld + p.r_off + n);
-            if (nan_chk && (v[0] != v[0] || v[1] != v[1] || v[2] != v[2] || v[3] != v[3])) saw_nan = true;
-            if (p.out_mode == YOLO_OUT_NHWC) {
-                *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.y_ld + p.y_off + n) = v;
-            } else {                                        // YOLO_OUT_UPSAMPLE2X
-                const int img = m / HoWo;
-                const int rem = m - img * HoWo;
-                const int ho = rem / p.Wo;
-                const int wo = rem - ho * p.Wo;
-                const int W2 = 2 * p.Wo;
-                float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
-                *reinterpret_cast<f32x4*>(d) = v;
-                *reinterpret_cast<f32x4*>(d + p.y_ld) = v;
-                *reinterpret_cast<f32x4*>(d + (size_t)W2 * p.y_ld) = v;
-                *reinterpret_cast<f32x4*>(d + (size_t)(W2 + 1) * p.y_ld) = v;
-            }
-        }
-        if (nan_chk && saw_nan) atomicOr(p.nan_flag, 2);
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * WN + j * 32 + frow;
-        const bool nv = n < p.Cout;
-        const float sc = nv ? p.scale[n] : 0.f;
-        const float sh = nv ? p.shift[n] : 0.f;
-        int head_a = 0, head_k = 0;
-        if (p.out_mode == YOLO_OUT_HEAD) {
-            head_a = n / p.nc5;
-            head_k = n - head_a * p.nc5;
-        }
-        YOLO_SWITCH_ACT(p.act,                          // activation chosen once, outside the element loops
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)
-                _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[i][j][r] = act_c<ACT>(acc[i][j][r] * sc + sh);)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (m >= p.M || !nv) continue;
-                float v = acc[i][j][r];
-                if (has_res) v += p.res[(size_t)m * p.r_ld + p.r_off + n];
-                if (nan_chk && v != v) saw_nan = true;
-                if (p.out_mode == YOLO_OUT_NHWC) {
-                    p.y[(size_t)m * p.y_ld + p.y_off + n] = v;
-                } else {
-                    const int img = m / HoWo;
-                    const int rem = m - img * HoWo;
-                    const int ho = rem / p.Wo;
-                    const int wo = rem - ho * p.Wo;
-                    if (p.out_mode == YOLO_OUT_UPSAMPLE2X) {
-                        const int W2 = 2 * p.Wo;
-                        float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
-                        d[0] = v;
-                        d[p.y_ld] = v;
-                        d[(size_t)W2 * p.y_ld] = v;
-                        d[(size_t)(W2 + 1) * p.y_ld] = v;
-                    } else {  // YOLO_OUT_HEAD: (B,3,g,g,5+nc)
-                        p.y[((size_t)((img * 3 + head_a) * p.Ho + ho) * p.Wo + wo) * p.nc5 + head_k] = v;
-                    }
-                }
-            }
-        }
-    }
-    if (nan_chk && saw_nan) atomicOr(p.nan_flag, 2);
+    // ---------------------------------------------------------------------- epilogue (conv_f32_epilogue.h)
+    conv_f32_epilogue<BM, BN>(p, acc, As, m0, n0);   // As: [BM][BN + 4] floats <= 2 * (BM + BN) * LDS_LD, idle behind the last barrier
 }
 
 // ------------------------------------------------------------------------------ host side
@@ -325,6 +206,13 @@ static int pick_tile(const yolo_conv_desc* d) {
     }
 }
 
+// YOLO_FLAG_SPLIT_BF16 is honoured on fp32 descriptors of the Direct and Rs families that conv_split3_f32 can run
+static bool split3_honoured(const yolo_conv_desc* d, const void* residual, size_t ws_avail) {
+    if (!split3_supported(d)) return false;
+    const F32Family f = f32_family(d, residual, ws_avail);
+    return f == F32Family::Direct || f == F32Family::Rs;
+}
+
 static int validate(const yolo_conv_desc* d) {
     if (!d) return fail(YOLO_ERR_ARG, "conv: null descriptor");
     if (d->dtype < 0 || d->dtype > 2) return fail(YOLO_ERR_ARG, "conv: dtype %d", d->dtype);
@@ -350,6 +238,11 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     const bool filters_ready = d->flags & YOLO_FLAG_FILTERS_READY;
     if (filters_ready && (d->dtype != YOLO_F32 || f32_family(d, residual, ws ? ws_bytes : 0) != F32Family::Wino4))
         return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_READY on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
+    // the three-way bf16 split runs what the direct kernels would run (conv_igemm_f32, conv_f32_v2, conv1_rs_f32) and nothing else
+    const bool split3 = d->flags & YOLO_FLAG_SPLIT_BF16;
+    if (split3 && !split3_honoured(d, residual, ws ? ws_bytes : 0))
+        return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_BF16 needs an fp32 layer of the direct kernels (no Winograd workspace in play) with "
+                                          "ksize 1 or 3, stride 1 or 2 and cin %% 32 == 0");
     if (d->dtype != YOLO_F32) return conv_h16_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     ConvArgs a;
     a.x = (const float*)x; a.w = (const float*)w; a.scale = scale; a.shift = shift;
@@ -368,6 +261,7 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     a.nc5 = d->out_mode == YOLO_OUT_HEAD ? d->cout / 3 : 1;
     a.tiles_n = 0;
     const bool smallc = a.Cin == 4;
+    if (split3) return conv_split3_launch(a, d->tile == kTileF32Rs ? 0 : d->tile, s);
     switch (f32_family(d, residual, ws ? ws_bytes : 0)) {
     case F32Family::Rs: return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     case F32Family::Wino4:          // the filters are transformed per launch from the row-major section, unless w is their transform
@@ -408,6 +302,15 @@ int yolo_conv_pick_tile(const yolo_conv_desc* d) {
     if (rc) return rc;
     return yolo::pick_tile(d);
 }
+
+int yolo_conv_split3_supported(const yolo_conv_desc* d) {
+    if (yolo::validate(d)) return 0;
+    yolo_conv_desc h = *d;
+    h.tile = 0;
+    return yolo::split3_honoured(&h, nullptr, SIZE_MAX);
+}
+
+int yolo_conv_split3_eligible(const yolo_conv_desc* d) { return yolo_conv_split3_supported(d) && yolo::split3_eligible(d); }
 
 int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
                   const void* residual, void* y, int32_t* nan_flag, void* stream) {

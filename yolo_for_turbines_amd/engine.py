@@ -379,6 +379,11 @@ class Plan:
                     and (d.tile == 15 or L.lib().yolo_conv_pick_tile(C.byref(d)) == 15)):
                 e.w_packed = pk.want_u4(d).data_ptr()
                 d.flags |= L.FLAG_FILTERS_READY
+            # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
+            # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
+            elif (dtype == "fp32" and state.split3 and i >= self.first and not tile_override
+                    and (L.lib().yolo_conv_split3_supported if state.split3 == "all" else L.lib().yolo_conv_split3_eligible)(C.byref(d))):
+                d.flags |= L.FLAG_SPLIT_BF16
             if i == 0 and self.stem is not None:
                 self.stem_pk = pk
             if op["pred"] is not None:
@@ -438,6 +443,10 @@ class ModelState:
         self._train_nan_pending = None   # not None: deferred guards are queued (see defer_nan)
         self._nan_host, self._nan_queue, self._nan_next = None, [], 0
         self.tile_override = None
+        # fp32 inference: the direct convolutions that measured faster that way run as three-way bf16 split products
+        # (YOLO_FLAG_SPLIT_BF16: fp32 accuracy, other bits). False: plans made from then on keep the exact-f32 kernels.
+        # "all": every launch the library honours the flag on, measured faster or not (A/B runs, tests).
+        self.split3 = True
         self.compute_dtype = None        # None: follow torch.autocast (fp32 outside it); or "fp32" / "fp16" / "bf16"
         self.ddp = None                  # (torch.distributed module, bucket MB) when data-parallel (dist.data_parallel)
         # Under an active torch.autocast the reference's forward returns its predictions in the autocast dtype (the head
@@ -465,17 +474,19 @@ class ModelState:
         return plan
 
     def __getstate__(self):
-        return {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads}
+        return {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3}
 
     def __setstate__(self, st):
         self.__init__()
         self.nan_check = st.get("nan_check", True)
         self.autocast_heads = st.get("autocast_heads", True)
+        self.split3 = st.get("split3", True)
 
     def __deepcopy__(self, memo):
         new = ModelState()
         new.nan_check = self.nan_check
         new.autocast_heads = self.autocast_heads
+        new.split3 = self.split3
         return new
 
     def head_dtype(self):
@@ -605,7 +616,7 @@ class ModelState:
         with torch.cuda.device(x.device):
             stream = L.current_stream()
             dt = resolve_dtype(self.compute_dtype)
-            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt)
+            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt, self.split3)
             plan = self._plans.get(key)
             if plan is None:
                 prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4, W=W)
