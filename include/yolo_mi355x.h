@@ -48,8 +48,12 @@ enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
  * (measured: DESIGN 4.13) but not its bits. Deterministic, and independent of the batch on finite data. A block of the output (up
  * to 128 pixels x 128 channels, possibly of two images) that reads an Inf or a NaN is computed with exact fp32 products, all of
  * it. tile: 0 = heuristic, 1 / 2 / 4 = 128x128 / 128x64 / 64x64 blocks. On any other descriptor the flag is refused with
- * YOLO_ERR_UNSUPPORTED. Without the flag nothing changes. */
-enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8 };
+ * YOLO_ERR_UNSUPPORTED. Without the flag nothing changes.
+ * YOLO_FLAG_SPLIT_WEIGHTS_READY (together with YOLO_FLAG_SPLIT_BF16 only): w_packed is the buffer that yolo_split3_weights made, the
+ * packed weights with their bf16 planes behind them, for weights that stay the same from call to call. Same bits as the launch
+ * without it. Anywhere else the flag is refused with YOLO_ERR_UNSUPPORTED. */
+enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8,
+       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -156,6 +160,25 @@ int yolo_conv_num_tiles(void);
  * on its exact kernel: what an inference plan should flag. */
 int yolo_conv_split3_supported(const yolo_conv_desc* d);
 int yolo_conv_split3_eligible(const yolo_conv_desc* d);
+/* YOLO_FLAG_SPLIT_BF16 with the weights split once instead of by every block of every launch (inference).
+ * yolo_split3_weights reads the row-major fp32 section of w_packed (yolo_pack_weights, YOLO_F32) and writes the prepared buffer:
+ *     [the packed weights, P = yolo_packed_weight_bytes(cout, cin, ksize, YOLO_F32) rounded up to 16 bytes]
+ *     [K step = K_pad32 / 32][plane: hi, mid, lo][cout_pad128][64 bytes]
+ *     [cout_pad128 / 32] 32-bit words
+ * The planes hold the three bf16 parts of every weight (the truncation split of the kernel itself: w = hi + mid + lo exactly). A
+ * 64-byte row holds the 32 k of the step as four 16-byte slots of 8 bf16 (k ascending), slot s of output channel n stored at slot
+ * s ^ ((n >> 2) & 3): the kernel's LDS image, so the rows of one (K step, plane) that a block needs are contiguous and copied as
+ * they are. Rows from cout up to cout_pad128 are zero. Word g of the table is 1 when a weight of output channels 32 g .. 32 g + 31
+ * is an Inf or a NaN, else 0; a block whose channels have a word set is computed with exact fp32 products, as a launch on the
+ * packed weights would, and reads the fp32 weights for that from the copy in front. out == w_packed prepares in place (the
+ * packed buffer then needs yolo_split3_weight_bytes of room; one launch): the same pointer serves launches with and without the
+ * flag. Otherwise the packed weights are copied to the front of out first; the two may not overlap. The planes add 6 bytes per
+ * weight of the padded matrix:
+ *     yolo_split3_weight_bytes = P + K_pad32 / 32 * 3 * cout_pad128 * 64 + cout_pad128 / 32 * 4,
+ * or 0 where yolo_conv_split3_supported(d) is 0 (only the shape of d is looked at). out: 16-byte aligned. A descriptor with
+ * YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY then takes that buffer as its w_packed. */
+size_t yolo_split3_weight_bytes(const yolo_conv_desc* d);
+int yolo_split3_weights(const yolo_conv_desc* d, const void* w_packed, void* out, void* stream);
 /* Winograd F(4x4, 3x3) (tile 15) with the filters transformed once instead of on every launch, for weights that stay the same
  * from call to call (inference). yolo_wino4_filter_bytes: size of U4 = G g G^T, 36 * cin4_pad2 * cout_pad64 * 16 bytes (it
  * depends on cin and cout only; 0: the descriptor cannot run as tile 15). yolo_wino4_filters writes U4 (16-byte aligned) from

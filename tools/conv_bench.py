@@ -3,6 +3,7 @@
 
   python tools/conv_bench.py --layer c52_3x3 --tile 0 --reps 20
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3 --rounds 5      (YOLO_FLAG_SPLIT_BF16; median and spread of 5 rounds)
+  python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3-ready --rounds 5    (the same on weights split once: yolo_split3_weights)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
 
 Layers are the dominant YOLOv3 shapes at batch 32, 416x416.
@@ -46,7 +47,7 @@ LAYERS = {   # name: (H, cin, cout, k, stride)
 OUT_MODES = {"nhwc": L.OUT_NHWC, "up2x": L.OUT_UPSAMPLE2X, "head": L.OUT_HEAD}
 
 
-def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1):
+def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False):
     H, cin, cout, k, s = LAYERS[name]
     lib = L.lib()
     cpad = (cin + 3) // 4 * 4
@@ -65,6 +66,11 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     d = L.ConvDesc(n=batch, h=H, w=H, cin=cin, cout=cout, ksize=k, stride=s, x_ld=cpad, x_off=0, y_ld=cout, y_off=0,
                    r_ld=cout, r_off=0, act=L.ACT_NONE if out == "head" else L.ACT_LEAKY, out_mode=OUT_MODES[out], dtype=code,
                    flags=(L.FLAG_RESIDUAL if residual else 0) | L.FLAG_NANCHECK | (L.FLAG_SPLIT_BF16 if split3 else 0), tile=tile)
+    if ready:                                                     # the bf16 planes of the weights, made once, in place of wp
+        d.flags |= L.FLAG_SPLIT_BF16 | L.FLAG_SPLIT_WEIGHTS_READY
+        ws3 = torch.empty(lib.yolo_split3_weight_bytes(d), dtype=torch.uint8, device=dev)
+        L.check(lib.yolo_split3_weights(d, wp.data_ptr(), ws3.data_ptr(), stream), "yolo_split3_weights")
+        wp = ws3
 
     need = lib.yolo_conv_workspace_bytes(d)                       # > 0: Winograd (tile 13, or the heuristic's choice for tile 0)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -86,11 +92,12 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
         times.append(e0.elapsed_time(e1) / reps)
     times.sort()
     ms = times[len(times) // 2]                                   # median round
+    run.rounds = list(times)                                      # (for drivers that want the spread as numbers)
     gflop = 2.0 * batch * Ho * Ho * cout * cin * k * k / 1e9
     picked = (lib.yolo_conv_pick_tile(d) if dtype == "fp32" else 0) if tile == 0 else tile
     cut = ""
-    if split3:
-        cut += f"  split3 (tile {tile})"
+    if split3 or ready:
+        cut += f"  split3{'-ready' if ready else ''} (tile {tile})"
     if out != "nhwc" or residual:
         cut += f"  out={out}" + (" +res" if residual else "")
     if rounds > 1:
@@ -112,6 +119,7 @@ def main():
     ap.add_argument("--residual", action="store_true")
     ap.add_argument("--dtype", default="fp32")
     ap.add_argument("--split3", action="store_true", help="set YOLO_FLAG_SPLIT_BF16 (tile 0, 1, 2 or 4)")
+    ap.add_argument("--split3-ready", action="store_true", help="YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY on prepared weights")
     ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
     a = ap.parse_args()
@@ -121,7 +129,7 @@ def main():
     tiles = list(range(1, nt + 1)) if a.tile == "all" else [int(t) for t in a.tile.split(",")]
     for n in names:
         for t in tiles:
-            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds)
+            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready)
 
 
 if __name__ == "__main__":

@@ -243,9 +243,11 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     if (split3 && !split3_honoured(d, residual, ws ? ws_bytes : 0))
         return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_BF16 needs an fp32 layer of the direct kernels (no Winograd workspace in play) with "
                                           "ksize 1 or 3, stride 1 or 2 and cin %% 32 == 0");
+    if ((d->flags & YOLO_FLAG_SPLIT_WEIGHTS_READY) && !split3)
+        return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_WEIGHTS_READY goes with YOLO_FLAG_SPLIT_BF16 only");
     if (d->dtype != YOLO_F32) return conv_h16_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     ConvArgs a;
-    a.x = (const float*)x; a.w = (const float*)w; a.scale = scale; a.shift = shift;
+    a.x = (const float*)x; a.w = (const float*)w; a.w_planes = nullptr; a.scale = scale; a.shift = shift;
     a.res = (const float*)residual; a.y = (float*)y; a.nan_flag = nan_flag;
     a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = cin_pad_of(d->cin); a.Cout = d->cout;
     a.ks = d->ksize; a.stride = d->stride; a.pad = d->ksize / 2;
@@ -261,7 +263,10 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     a.nc5 = d->out_mode == YOLO_OUT_HEAD ? d->cout / 3 : 1;
     a.tiles_n = 0;
     const bool smallc = a.Cin == 4;
-    if (split3) return conv_split3_launch(a, d->tile == kTileF32Rs ? 0 : d->tile, s);
+    if (split3) {
+        if (d->flags & YOLO_FLAG_SPLIT_WEIGHTS_READY) a.w_planes = (const char*)w + split3_planes_offset(d);
+        return conv_split3_launch(a, d->tile == kTileF32Rs ? 0 : d->tile, s);
+    }
     switch (f32_family(d, residual, ws ? ws_bytes : 0)) {
     case F32Family::Rs: return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
     case F32Family::Wino4:          // the filters are transformed per launch from the row-major section, unless w is their transform
@@ -311,6 +316,15 @@ int yolo_conv_split3_supported(const yolo_conv_desc* d) {
 }
 
 int yolo_conv_split3_eligible(const yolo_conv_desc* d) { return yolo_conv_split3_supported(d) && yolo::split3_eligible(d); }
+
+size_t yolo_split3_weight_bytes(const yolo_conv_desc* d) { return d && yolo_conv_split3_supported(d) ? yolo::split3_weight_bytes(d) : 0; }
+
+int yolo_split3_weights(const yolo_conv_desc* d, const void* w_packed, void* out, void* stream) {
+    if (!d || !yolo_conv_split3_supported(d))
+        return yolo::fail(YOLO_ERR_UNSUPPORTED, "yolo_split3_weights: the library does not honour YOLO_FLAG_SPLIT_BF16 on this layer");
+    if (!w_packed || !out || ((uintptr_t)out & 15)) return yolo::fail(YOLO_ERR_ARG, "yolo_split3_weights: null or misaligned pointer");
+    return yolo::split3_weights_launch(d, w_packed, out, (hipStream_t)stream);
+}
 
 int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
                   const void* residual, void* y, int32_t* nan_flag, void* stream) {

@@ -12,6 +12,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 struct ConvArgs {
     const float* x;
     const float* w;
+    const char* w_planes;    // conv_split3_f32 on prepared weights: the bf16 planes behind w (else null)
     const float* scale;
     const float* shift;
     const float* res;
@@ -31,7 +32,11 @@ constexpr int BK = 32;       // one K step: 32 consecutive input channels of one
 // conv_split3_f32.hip (fp32 operands split into three bf16 each, six bf16 MFMAs per product; YOLO_FLAG_SPLIT_BF16)
 bool split3_supported(const yolo_conv_desc* d);
 bool split3_eligible(const yolo_conv_desc* d);
+// a.w_planes set: a.w is the buffer split3_weights_launch made (YOLO_FLAG_SPLIT_WEIGHTS_READY), the planes split3_planes_offset in
 int conv_split3_launch(const ConvArgs& a, int tile, hipStream_t s);
+size_t split3_planes_offset(const yolo_conv_desc* d);
+size_t split3_weight_bytes(const yolo_conv_desc* d);
+int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* out, hipStream_t s);
 
 // Epilogue of a BM x BN block of 256 threads = 2 x 2 waves with (BM/2) x (BN/2) wave tiles of 32x32 MFMA tiles.
 // C/D map of the 32x32 tile: column (N = cout) = lane & 31, row (M = pixel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).

@@ -24,6 +24,24 @@
 // product cannot keep an Inf. Every thread tracks whether anything it staged was not finite; a block that saw such a value
 // computes its tile again with v_mfma_f32_32x32x2_f32 straight from global memory, in conv_igemm_f32's order of additions:
 // that tile then equals the exact kernel's bit for bit (Inf stays Inf, NaN stays NaN, finite stays finite).
+//
+// Prepared weights (YOLO_FLAG_SPLIT_WEIGHTS_READY, WREADY): inference weights stay the same from call to call, so
+// split3_weights_f32 (yolo_split3_weights) splits the row-major section once, with s3_split. The prepared buffer is
+//     [the packed weights as they are, padded to 16 bytes]
+//     [K step][plane hi / mid / lo][cout_pad128][64 bytes]
+//     [cout_pad128 / 32] 32-bit words,
+// each 64-byte row with the slot swizzle above already applied (the row index is the output channel; blocks start at
+// multiples of 64, so the channel's swizzle is the LDS row's). The BN rows a block needs of one (K step, plane) are BN * 64
+// contiguous bytes and byte for byte the LDS image: the B side of a WREADY launch is a linear copy, 16 bytes per thread, with
+// no split arithmetic and no chk. Word g of the table behind the planes is non-zero when a weight of output channels
+// 32 g .. 32 g + 31 is an Inf or a NaN; a block ORs the words of its BN channels into its vote, so it takes the exact path
+// exactly where the in-flight kernel does. The exact path reads its fp32 weights from the packed weights in front, as the
+// in-flight kernel does. That copy in front is also what lets a packed buffer with room behind it be prepared in place: the same
+// pointer then serves launches with and without the flag. 6 bytes per weight on top of the packed weights.
+// WDMA moves the prepared B rows by LDS-DMA (global_load_lds, 16 bytes per lane) instead of through registers: a B ring of two
+// slots, step kt + 1 requested at the top of step kt and retired by the vmcnt(0) in front of the barrier that ends the step.
+// 64x64 blocks have the two slots already (48 KB), a 128x128 block takes 72 KB with them (still two workgroups per CU), a 128x64
+// block would take 48 KB and lose its fourth workgroup, so that tile copies through registers (ds_write_b128, 36 KB as before).
 #include "conv_f32_epilogue.h"
 
 namespace yolo {
@@ -32,6 +50,13 @@ typedef __bf16 s3_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int s3_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int S3_ROWB = 64;      // bytes per LDS row: 32 bf16 as four 16-byte slots, slot s of row r stored at s ^ ((r >> 2) & 3)
+
+// byte offset, inside a plane of 64-byte rows, of the 8 bytes that hold k = 4 * chunk .. + 3 of row r
+__device__ __forceinline__ int s3_row_off(int r, int chunk) { return r * S3_ROWB + (((chunk >> 1) ^ ((r >> 2) & 3)) * 16 + (chunk & 1) * 8); }
+
+typedef const __attribute__((address_space(1))) void* s3_gptr;
+typedef __attribute__((address_space(3))) void* s3_lptr;
+__device__ __forceinline__ void s3_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((s3_gptr)g, (s3_lptr)l, 16, 0, 0); }
 
 // two floats' upper halves as one bf16 pair, `a` in the low half (the lower k)
 __device__ __forceinline__ unsigned s3_pack(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
@@ -51,14 +76,50 @@ __device__ __forceinline__ void s3_split(const f32x4 v, u32x2& hi, u32x2& mid, u
     lo[0] = s3_pack(r2b[0], r2b[1]); lo[1] = s3_pack(r2b[2], r2b[3]);
 }
 
-template <int BM, int BN>
+// Prepared weights of yolo_split3_weights: one block per 32 output channels, the staging geometry of conv_split3_f32 (thread =
+// row tid >> 3, 16-byte chunk tid & 7 of every K step), so that the bytes written are the ones store_lds would have written.
+struct S3PrepArgs {
+    const float* w;      // row-major section of the packed weights [cout_pad128][Kpad]
+    char* out;           // the planes (behind the packed weights of the prepared buffer)
+    int Kpad, KT, cp;    // cp = cout_pad128
+};
+
+__global__ __launch_bounds__(256) void split3_weights_f32(const S3PrepArgs p) {
+    const int tid = threadIdx.x;
+    const int chunk = tid & 7;
+    const int n = blockIdx.x * 32 + (tid >> 3);
+    const size_t plane_b = (size_t)p.cp * S3_ROWB;
+    const float* src = p.w + (size_t)n * p.Kpad + chunk * 4;
+    char* dst = p.out + s3_row_off(n, chunk);
+    f32x4 chk = {0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < p.KT; ++kt) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + kt * BK);
+        u32x2 h, m, l;
+        s3_split(v, h, m, l, chk);
+        char* d = dst + (size_t)kt * 3 * plane_b;
+        *reinterpret_cast<u32x2*>(d) = h;
+        *reinterpret_cast<u32x2*>(d + plane_b) = m;
+        *reinterpret_cast<u32x2*>(d + 2 * plane_b) = l;
+    }
+    const bool nonfinite = chk[0] != chk[0] || chk[1] != chk[1] || chk[2] != chk[2] || chk[3] != chk[3];
+    const int any = __syncthreads_or(nonfinite);
+    if (tid == 0) reinterpret_cast<unsigned*>(p.out + (size_t)p.KT * 3 * plane_b)[blockIdx.x] = any ? 1u : 0u;
+}
+
+// WREADY: p.w_planes points at the planes of the prepared buffer above, whose front p.w is. WDMA (with WREADY): its rows go to LDS by LDS-DMA.
+template <int BM, int BN, bool WREADY, bool WDMA>
 __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
+    static_assert(WREADY || !WDMA, "LDS-DMA needs the prepared weights");
     constexpr int WM = BM / 2, WN = BN / 2;      // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;    // 32x32 MFMA tiles per wave
     constexpr int RA = BM / 32, RB = BN / 32;    // rows staged per thread
     constexpr bool DBUF = BM + BN <= 128;
     constexpr int A_BYTES = 3 * BM * S3_ROWB;                    // [3][BM][64 bytes]
-    constexpr int BUF_BYTES = 3 * (BM + BN) * S3_ROWB;           // A planes, then B planes [3][BN][64 bytes]
+    constexpr int B_BYTES = 3 * BN * S3_ROWB;                    // [3][BN][64 bytes]
+    constexpr int BUF_BYTES = A_BYTES + B_BYTES;                 // A planes, then B planes
+    constexpr bool BRING = DBUF || WDMA;                         // B has two slots: both buffers, or (one A buffer) a ring behind A
+    constexpr int B_SLOT = DBUF ? BUF_BYTES : B_BYTES;           // B slot s starts at A_BYTES + s * B_SLOT
+    constexpr int PB = BN / 64;                                  // prepared B: 16-byte pieces per thread and plane
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
     const int tid = threadIdx.x;
@@ -96,8 +157,13 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
 #pragma unroll
     for (int i = 0; i < RA; ++i) row_geom(m0 + lrow + 32 * i, a_base[i], a_mask[i]);
     const float* wrow = p.w + (size_t)(n0 + lrow) * p.Kpad + chunk * 4;
+    // prepared weights: plane (kt, q) of this block is BN * 64 contiguous bytes, thread tid copies bytes 16 * tid .. + 15 of every 4 KB
+    const char* wq = p.w_planes;
+    const size_t plane_b = (size_t)((p.Cout + 127) & ~127) * S3_ROWB;
+    const char* wsrc = wq + (size_t)n0 * S3_ROWB + tid * 16;
 
     f32x4 ra[RA], rb[RB];
+    s3_u32x4 rw[3][PB];
     f32x4 chk = {0.f, 0.f, 0.f, 0.f};
     auto load_global = [&](int kt) {
         const int kg = kt * BK;
@@ -111,13 +177,27 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
             ra[i] = v ? *reinterpret_cast<const f32x4*>(p.x + a_base[i] + toff) : z;
         }
+        if constexpr (!WREADY) {
 #pragma unroll
-        for (int i = 0; i < RB; ++i)
-            rb[i] = *reinterpret_cast<const f32x4*>(wrow + (size_t)(32 * i) * p.Kpad + kt * BK);
+            for (int i = 0; i < RB; ++i)
+                rb[i] = *reinterpret_cast<const f32x4*>(wrow + (size_t)(32 * i) * p.Kpad + kt * BK);
+        } else {
+            const char* src = wsrc + (size_t)kt * 3 * plane_b;
+            char* dst = smem_raw + A_BYTES + (kt & 1) * B_SLOT + wave * 1024;      // (WDMA: the wave's KB of every 4; lane l lands 16 l in)
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int i = 0; i < PB; ++i) {
+                    if constexpr (WDMA)
+                        s3_glds16(src + q * plane_b + i * 4096, dst + q * BN * S3_ROWB + i * 4096);
+                    else
+                        rw[q][i] = *reinterpret_cast<const s3_u32x4*>(src + q * plane_b + i * 4096);
+                }
+        }
     };
-    auto store_lds = [&](int buf) {
-        char* a = smem_raw + buf * BUF_BYTES + lrow * S3_ROWB + (((chunk >> 1) ^ ((lrow >> 2) & 3)) * 16 + (chunk & 1) * 8);
-        char* b = a + A_BYTES;
+    auto store_lds = [&](int buf, int bslot) {
+        char* a = smem_raw + buf * BUF_BYTES + s3_row_off(lrow, chunk);
+        char* b = smem_raw + A_BYTES + bslot * B_SLOT + s3_row_off(lrow, chunk);
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             u32x2 h, m, l;
@@ -126,13 +206,21 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
             *reinterpret_cast<u32x2*>(a + (1 * BM + 32 * i) * S3_ROWB) = m;
             *reinterpret_cast<u32x2*>(a + (2 * BM + 32 * i) * S3_ROWB) = l;
         }
+        if constexpr (!WREADY) {
 #pragma unroll
-        for (int i = 0; i < RB; ++i) {
-            u32x2 h, m, l;
-            s3_split(rb[i], h, m, l, chk);
-            *reinterpret_cast<u32x2*>(b + (0 * BN + 32 * i) * S3_ROWB) = h;
-            *reinterpret_cast<u32x2*>(b + (1 * BN + 32 * i) * S3_ROWB) = m;
-            *reinterpret_cast<u32x2*>(b + (2 * BN + 32 * i) * S3_ROWB) = l;
+            for (int i = 0; i < RB; ++i) {
+                u32x2 h, m, l;
+                s3_split(rb[i], h, m, l, chk);
+                *reinterpret_cast<u32x2*>(b + (0 * BN + 32 * i) * S3_ROWB) = h;
+                *reinterpret_cast<u32x2*>(b + (1 * BN + 32 * i) * S3_ROWB) = m;
+                *reinterpret_cast<u32x2*>(b + (2 * BN + 32 * i) * S3_ROWB) = l;
+            }
+        } else if constexpr (!WDMA) {
+            char* bw = smem_raw + A_BYTES + bslot * B_SLOT + tid * 16;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int i = 0; i < PB; ++i) *reinterpret_cast<s3_u32x4*>(bw + q * BN * S3_ROWB + i * 4096) = rw[q][i];
         }
     };
 
@@ -147,20 +235,22 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
     // fragment reads: lane l -> row (l & 31), k = 8 * (l >> 5) .. + 7 of each 16-wide chunk
     const int frow = lane & 31, fh = lane >> 5;
     const int a_frag = (wm * WM + frow) * S3_ROWB;
-    const int b_frag = A_BYTES + (wn * WN + frow) * S3_ROWB;
+    const int b_frag = A_BYTES + (wn * WN + frow) * S3_ROWB;       // in B slot 0
     const int fsw = (frow >> 2) & 3;                       // the swizzle of this lane's rows (the same in every 32-row tile)
     const int f_slot[2] = {(fh ^ fsw) * 16, ((2 + fh) ^ fsw) * 16};
 
     load_global(0);
-    store_lds(0);
+    store_lds(0, 0);
+    if constexpr (WDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     for (int kt = 0; kt < p.KT; ++kt) {
         const int cur = DBUF ? (kt & 1) : 0;
+        const int bcur = BRING ? (kt & 1) : 0;
         const bool more = kt + 1 < p.KT;
-        if (more) load_global(kt + 1);
+        if (more) load_global(kt + 1);           // (WDMA: B slot bcur ^ 1 was last read in step kt - 1, behind that step's barrier)
         const char* Ab = smem_raw + cur * BUF_BYTES + a_frag;
-        const char* Bb = smem_raw + cur * BUF_BYTES + b_frag;
+        const char* Bb = smem_raw + bcur * B_SLOT + b_frag;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             s3_bf16x8 af[TM][3], bf[TN][3];
@@ -186,7 +276,8 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][QA[t]], bf[j][QB[t]], acc[i][j], 0, 0, 0);
         }
         if (!DBUF) __syncthreads();              // one buffer: everybody has read step kt before step kt + 1 lands
-        if (more) store_lds(DBUF ? (cur ^ 1) : 0);
+        if (more) store_lds(DBUF ? (cur ^ 1) : 0, BRING ? (bcur ^ 1) : 0);
+        if constexpr (WDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the DMA of step kt + 1 has landed before the barrier
         __syncthreads();
     }
 
@@ -194,7 +285,12 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
     // slow is fine) and in conv_igemm_f32's order: k = 8 s + 4 (l >> 5) + e for MFMA (s, e) of each K step.
     // The whole block goes that way, the rows of a neighbouring image that share it included: their finite outputs then carry the
     // exact kernel's bits instead of the split products' (batch independence holds for finite data).
-    const bool nonfinite = chk[0] != chk[0] || chk[1] != chk[1] || chk[2] != chk[2] || chk[3] != chk[3];
+    bool nonfinite = chk[0] != chk[0] || chk[1] != chk[1] || chk[2] != chk[2] || chk[3] != chk[3];
+    if constexpr (WREADY) {                      // chk saw the A side only: the weights' vote was taken when they were prepared
+        const unsigned* table = reinterpret_cast<const unsigned*>(wq + (size_t)p.KT * 3 * plane_b);
+#pragma unroll
+        for (int g = 0; g < BN / 32; ++g) nonfinite |= table[n0 / 32 + g] != 0;
+    }
     if (__syncthreads_or(nonfinite)) {
         long long f_base[TM];
         unsigned f_mask[TM];
@@ -240,9 +336,10 @@ bool split3_supported(const yolo_conv_desc* d) {
     return d->dtype == YOLO_F32 && (d->ksize == 1 || d->ksize == 3) && (d->stride == 1 || d->stride == 2) && d->cin % 32 == 0;
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool WREADY, bool WDMA>
 static int launch_split3(const ConvArgs& a, hipStream_t s) {
-    constexpr size_t operands = (size_t)(BM + BN <= 128 ? 2 : 1) * 3 * (BM + BN) * S3_ROWB;
+    constexpr bool dbuf = BM + BN <= 128;
+    constexpr size_t operands = dbuf ? (size_t)2 * 3 * (BM + BN) * S3_ROWB : (size_t)3 * (BM + (WDMA ? 2 : 1) * BN) * S3_ROWB;
     constexpr size_t transpose = (size_t)BM * (BN + 4) * sizeof(float);
     constexpr size_t lds = operands > transpose ? operands : transpose;
     ConvArgs p = a;
@@ -251,40 +348,86 @@ static int launch_split3(const ConvArgs& a, hipStream_t s) {
     if (blocks > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "conv_split3_f32: too many blocks");
     if (lds > 64 * 1024) {
         static LdsOnce once;
-        if (int rc = reserve_lds(once, reinterpret_cast<const void*>(&conv_split3_f32<BM, BN>), lds, "conv_split3_f32")) return rc;
+        if (int rc = reserve_lds(once, reinterpret_cast<const void*>(&conv_split3_f32<BM, BN, WREADY, WDMA>), lds, "conv_split3_f32")) return rc;
     }
-    hipLaunchKernelGGL((conv_split3_f32<BM, BN>), dim3((unsigned)blocks), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((conv_split3_f32<BM, BN, WREADY, WDMA>), dim3((unsigned)blocks), dim3(256), lds, s, p);
     return check_launch("conv_split3_f32");
 }
 
-// Tile of the heuristic: the layer's shape only, never the batch. Measured at batch 32 (tools/conv_bench.py --split3 --tile 1,2,4,
-// profiles/r06/conv_bench_split3.txt, medians in us). Stride-2 3x3: 128x128 wins with 64 .. 256 input channels (349 / 323 / 353
-// against 379 / 353 / 363 for 128x64), 128x64 wins 32 -> 64 at 416 x 416 (cout 64: half a 128-wide block would be padding) and
-// 512 -> 1024 at 26 x 26 (348 against 381). 1x1: 128x64 wins wherever it makes enough blocks; the launches with h * w * cout below
-// 100,000 (256 -> 128 at 26 x 26, 1024 -> 512 at 13 x 13: 338 / 344 blocks of 128x64 at batch 32 on 256 CUs) run faster as twice
-// as many 64x64 blocks (20.2 against 24.1, 54.1 against 65.2). 64x64 wins nowhere else.
-static int pick_split3_tile(const ConvArgs& a) {
-    if (a.ks == 3 && a.stride == 2 && a.Cin >= 64 && a.Cin < 512) return kTileF32Reg128x128;
+// How a launch on prepared weights moves them into LDS, per tile (batch 32, medians in us, profiles/r07/conv_bench_regs.txt and
+// conv_bench_dma.txt). 128x128 and 64x64: LDS-DMA, 6 - 13 % under the in-flight kernel on the stride-2 layers and up to 22 % at
+// 13 x 13, where registers gain 0 - 5 %. 128x64: registers. Its DMA ring takes 48 KB, three workgroups per CU instead of four, and
+// loses 3 - 8 % on the launches with few K steps (64 -> 32 at 208 x 208, the 52 x 52 head, 32 -> 64 3x3); registers are level
+// with the in-flight kernel there (0 - 2 %, inside the spread) and never behind it.
+constexpr bool kS3Dma128x128 = true, kS3Dma128x64 = false, kS3Dma64x64 = true;
+
+template <int BM, int BN, bool WDMA>
+static int launch_split3(const ConvArgs& a, hipStream_t s) {
+    return a.w_planes ? launch_split3<BM, BN, true, WDMA>(a, s) : launch_split3<BM, BN, false, false>(a, s);
+}
+
+// ---- prepared weights (yolo_split3_weights): layout in the comment at the top of this file
+size_t split3_planes_offset(const yolo_conv_desc* d) {
+    return (yolo_packed_weight_bytes(d->cout, d->cin, d->ksize, YOLO_F32) + 15) & ~(size_t)15;
+}
+
+size_t split3_weight_bytes(const yolo_conv_desc* d) {
+    const size_t cp = coutpad_of(d->cout), KT = kpad_of(d->cin, d->ksize) / BK;
+    return split3_planes_offset(d) + KT * 3 * cp * S3_ROWB + cp / 32 * sizeof(unsigned);
+}
+
+int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* out, hipStream_t s) {
+    const size_t off = split3_planes_offset(d);
+    if (out != w_packed) {                           // not in place: the packed weights go in front
+        const char *a = static_cast<const char*>(w_packed), *b = static_cast<const char*>(out);
+        if (a < b + split3_weight_bytes(d) && b < a + off) return fail(YOLO_ERR_ARG, "yolo_split3_weights: out overlaps w_packed (pass the same pointer to prepare in place)");
+        if (hipMemcpyAsync(out, w_packed, off, hipMemcpyDeviceToDevice, s) != hipSuccess) return check_launch("yolo_split3_weights: copy");
+    }
+    S3PrepArgs p;
+    p.w = static_cast<const float*>(w_packed);
+    p.out = static_cast<char*>(out) + off;
+    p.Kpad = kpad_of(d->cin, d->ksize);
+    p.KT = p.Kpad / BK;
+    p.cp = coutpad_of(d->cout);
+    hipLaunchKernelGGL(split3_weights_f32, dim3(p.cp / 32), dim3(256), 0, s, p);
+    return check_launch("split3_weights_f32");
+}
+
+// Tile of the heuristic: the layer's shape only, never the batch. Measured at batch 32 (tools/conv_bench.py --split3 /
+// --split3-ready --tile 1,2,4, medians in us).
+// Weights split in flight (profiles/r06/conv_bench_split3.txt). Stride-2 3x3: 128x128 wins with 64 .. 256 input channels (349 /
+// 323 / 353 against 379 / 353 / 363 for 128x64), 128x64 wins 32 -> 64 at 416 x 416 (cout 64: half a 128-wide block would be
+// padding) and 512 -> 1024 at 26 x 26 (348 against 381). 1x1: 128x64 wins wherever it makes enough blocks; the launches with
+// h * w * cout below 100,000 (256 -> 128 at 26 x 26, 1024 -> 512 at 13 x 13: 338 / 344 blocks of 128x64 at batch 32 on 256 CUs)
+// run faster as twice as many 64x64 blocks (20.2 against 24.1, 54.1 against 65.2). 64x64 wins nowhere else.
+// Prepared weights (profiles/r07/conv_bench_ready.txt): the B side of a 128x128 block is a DMA and A's split is shared by 128
+// columns, so 128x128 also wins 512 -> 1024 stride 2 at 26 x 26 (345 against 357) and the 1x1 layers with a multiple of 128 output
+// channels and many K steps: 256 -> 128 and 384 -> 128 at 52 x 52 (46.4 / 63.0 against 49.8 / 68.9), 768 -> 256 at 26 x 26 (64.9
+// against 65.8). 512 -> 256 at 26 x 26 (46.6 against 47.2) gains less than its own spread and stays.
+static int pick_split3_tile(const ConvArgs& a, bool ready) {
+    if (a.ks == 3 && a.stride == 2 && a.Cin >= 64 && (ready || a.Cin < 512)) return kTileF32Reg128x128;
     if (a.ks == 1 && (long long)a.H * a.W * a.Cout < 100000) return kTileF32Reg64x64;
+    if (ready && a.ks == 1 && a.Cout % 128 == 0 && a.Cin >= ((long long)a.H * a.W >= 52 * 52 ? 256 : 768)) return kTileF32Reg128x128;
     return kTileF32Reg128x64;
 }
 
 // Shapes that the eval plan runs on this kernel: the supported ones whose median at batch 32 improved by more than the spread of
-// their own baseline (profiles/r06/conv_bench_split3.txt). The five stride-2 3x3 layers gain 20 - 31 %, 32 -> 64 3x3 stride 1 at
-// 208 x 208 gains 11 % on conv_patch_f32 (smaller maps of that layer were not measured and stay), the 1x1 layers and heads with
-// h * w * cout >= 80,000 gain 11 - 25 %. The two 13 x 13 launches below that (512 -> 256 and the 1024 -> 255 head, 43,000) are
-// 340 blocks of 64x64 at batch 32 and level with the exact kernel (-3.7 % and -0.2 %): they stay.
+// their own baseline (profiles/r06/conv_bench_split3.txt, profiles/r07/conv_bench_ready.txt). The five stride-2 3x3 layers gain
+// 20 - 34 %, 32 -> 64 3x3 stride 1 at 208 x 208 gains 11 % on conv_patch_f32 (smaller maps of that layer were not measured and
+// stay), the 1x1 layers and heads with h * w * cout >= 80,000 gain 11 - 28 %. The two 13 x 13 launches below that (512 -> 256 and
+// the 1024 -> 255 head, 43,000: 340 blocks of 64x64 at batch 32) were level with the exact kernel while every block split its
+// weights; on prepared weights they gain 17 % and 22 %, so the bound is 40,000 now. Nothing smaller was measured.
 bool split3_eligible(const yolo_conv_desc* d) {
     if (!split3_supported(d)) return false;
     if (d->ksize == 3) return d->stride == 2 || (d->cin == 32 && (long long)d->h * d->w >= 208 * 208);
-    return d->stride == 1 && (long long)d->h * d->w * d->cout >= 80000;
+    return d->stride == 1 && (long long)d->h * d->w * d->cout >= 40000;
 }
 
 int conv_split3_launch(const ConvArgs& a, int tile, hipStream_t s) {
-    switch (tile ? tile : pick_split3_tile(a)) {
-    case kTileF32Reg128x128: return launch_split3<128, 128>(a, s);
-    case kTileF32Reg128x64: return launch_split3<128, 64>(a, s);
-    case kTileF32Reg64x64: return launch_split3<64, 64>(a, s);
+    switch (tile ? tile : pick_split3_tile(a, a.w_planes != nullptr)) {
+    case kTileF32Reg128x128: return launch_split3<128, 128, kS3Dma128x128>(a, s);
+    case kTileF32Reg128x64: return launch_split3<128, 64, kS3Dma128x64>(a, s);
+    case kTileF32Reg64x64: return launch_split3<64, 64, kS3Dma64x64>(a, s);
     default: return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_BF16 has tiles 1 (128x128), 2 (128x64) and 4 (64x64), not %d", tile);
     }
 }

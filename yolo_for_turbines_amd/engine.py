@@ -194,7 +194,15 @@ class PackedBlock:
         if n == 0 and not (stem_ok and dtype != "fp32"):
             raise NotImplementedError(f"conv {cv.in_channels}->{cv.out_channels} k{cv.kernel_size[0]} has no {dtype} kernel "
                                       "(16-bit needs cin % 32 == 0)")
-        self.w = torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+        # fp32 layers that never run as Winograd (1x1, stride 2, fewer than 64 channels on a side) and that conv_split3_f32 can run
+        # get room behind the packed weights for their bf16 planes (want_s3; 6 bytes per weight): the buffer cannot grow
+        # later, plans hold its address
+        room = 0
+        if dtype == "fp32" and n and (cv.kernel_size[0] == 1 or cv.stride[0] == 2 or min(cv.in_channels, cv.out_channels) < 64):
+            d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=cv.kernel_size[0], stride=cv.stride[0],
+                           x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=self.code)
+            room = lib.yolo_split3_weight_bytes(C.byref(d))
+        self.w = torch.empty(max(n, room, 16), dtype=torch.uint8, device=device)
         self.scale = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.shift = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.stem_w = None
@@ -208,6 +216,12 @@ class PackedBlock:
         self.u4 = None
         self.u4_desc = None
         self.u4_stamp = None
+        # The bf16 planes of the packed weights (yolo_split3_weights), for the eval plans whose launch of this block carries
+        # YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY: a view of w (packed weights, then planes) once a plan wants them;
+        # they too depend on (cout, cin, ksize) only and follow the stamp.
+        self.s3 = None
+        self.s3_desc = None
+        self.s3_stamp = None
         self.fold_stamp = None            # same for the tensors behind scale / shift; None = not folded
         self.folded = False
 
@@ -262,6 +276,23 @@ class PackedBlock:
         L.check(L.lib().yolo_wino4_filters(C.byref(self.u4_desc), self.w.data_ptr(), self.u4.data_ptr(), stream), "yolo_wino4_filters")
         self.u4_stamp = self.stamp
 
+    def want_s3(self, desc):
+        """An eval plan runs this block as split products with YOLO_FLAG_SPLIT_WEIGHTS_READY: the bf16 planes are made in place,
+        behind the packed weights in ``w`` (the launch keeps its ``w_packed``). None: ``w`` has no room for them."""
+        if self.s3 is None:
+            n = L.lib().yolo_split3_weight_bytes(C.byref(desc))
+            if n == 0 or n > self.w.numel():
+                return None
+            self.s3_desc = L.ConvDesc.from_buffer_copy(desc)
+            self.s3 = self.w[:n]
+            self.s3_stamp = None
+        return self.s3
+
+    def refresh_s3(self, stream):
+        """The planes from the packed weights as they are now (call after the pack on the same stream)."""
+        L.check(L.lib().yolo_split3_weights(C.byref(self.s3_desc), self.w.data_ptr(), self.w.data_ptr(), stream), "yolo_split3_weights")
+        self.s3_stamp = self.stamp
+
     def refresh(self, block, stream, fold_bn=True, conv_packed=False, pack=True):
         """fold_bn=False (training: batch statistics are used, not the running ones) skips the BN fold.
         conv_packed: the conv weights were already written by a batched pack (ModelState.refresh_weights).
@@ -273,6 +304,7 @@ class PackedBlock:
             w = w.float().contiguous()
         if pack:
             self.u4_stamp = None          # (the training path re-packs every step and never reads U4: it is re-made on the eval side)
+            self.s3_stamp = None          # (likewise the bf16 planes)
             if self.packs_conv and not conv_packed:
                 L.check(lib.yolo_pack_weights(w.data_ptr(), self.w.data_ptr(), cv.out_channels, cv.in_channels,
                                               cv.kernel_size[0], self.code, stream), "yolo_pack_weights")
@@ -384,6 +416,9 @@ class Plan:
             elif (dtype == "fp32" and state.split3 and i >= self.first and not tile_override
                     and (L.lib().yolo_conv_split3_supported if state.split3 == "all" else L.lib().yolo_conv_split3_eligible)(C.byref(d))):
                 d.flags |= L.FLAG_SPLIT_BF16
+                # ... on weights split once, in place behind the packed ones ("inflight": by every launch, for A/B runs)
+                if state.split3 != "inflight" and pk.want_s3(d) is not None:
+                    d.flags |= L.FLAG_SPLIT_WEIGHTS_READY
             if i == 0 and self.stem is not None:
                 self.stem_pk = pk
             if op["pred"] is not None:
@@ -445,7 +480,9 @@ class ModelState:
         self.tile_override = None
         # fp32 inference: the direct convolutions that measured faster that way run as three-way bf16 split products
         # (YOLO_FLAG_SPLIT_BF16: fp32 accuracy, other bits). False: plans made from then on keep the exact-f32 kernels.
-        # "all": every launch the library honours the flag on, measured faster or not (A/B runs, tests).
+        # "all": every launch the library honours the flag on, measured faster or not (A/B runs, tests). True and "all" read
+        # weights split into their bf16 planes once per weight update (YOLO_FLAG_SPLIT_WEIGHTS_READY, PackedBlock.want_s3);
+        # "inflight": the launches of True, every one splitting the packed weights itself (same bits; A/B runs).
         self.split3 = True
         self.compute_dtype = None        # None: follow torch.autocast (fp32 outside it); or "fp32" / "fp16" / "bf16"
         self.ddp = None                  # (torch.distributed module, bucket MB) when data-parallel (dist.data_parallel)
@@ -502,6 +539,7 @@ class ModelState:
             for pk in per_dev.values():
                 pk.stamp = None
                 pk.u4_stamp = None
+                pk.s3_stamp = None
                 pk.fold_stamp = None
                 pk.folded = False
         if drop_plans:
@@ -582,6 +620,8 @@ class ModelState:
                 pk = self.packed(blk, device, dtype)
                 if pk.u4 is not None and (pk.u4_stamp is None or pk.u4_stamp != pk.stamp):
                     pk.refresh_u4(stream)
+                if pk.s3 is not None and (pk.s3_stamp is None or pk.s3_stamp != pk.stamp):
+                    pk.refresh_s3(stream)
 
     def mark_unfolded(self, blocks):
         """The BatchNorm running statistics of ``blocks`` were just written by a kernel (train-mode forward): every folded
