@@ -51,9 +51,19 @@ enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
  * YOLO_ERR_UNSUPPORTED. Without the flag nothing changes.
  * YOLO_FLAG_SPLIT_WEIGHTS_READY (together with YOLO_FLAG_SPLIT_BF16 only): w_packed is the buffer that yolo_split3_weights made, the
  * packed weights with their bf16 planes behind them, for weights that stay the same from call to call. Same bits as the launch
- * without it. Anywhere else the flag is refused with YOLO_ERR_UNSUPPORTED. */
+ * without it. Anywhere else the flag is refused with YOLO_ERR_UNSUPPORTED.
+ * YOLO_FLAG_SPLIT_K (fp32 descriptors with ksize 1 or 3, stride 1 or 2, cin a multiple of 32 and tile 0; any act, out_mode, residual):
+ * the launch for small batches. K is cut into S slices (yolo_conv_splitk_slices: a function of h, w, cin, cout, ksize, stride alone,
+ * never of n or of the device); one launch writes the S partial sums of every output value into the caller's workspace, a second adds
+ * them in ascending slice order and applies the epilogue. Exact fp32 products, no atomics on floats: deterministic, an image's bits
+ * do not depend on its batch; fp32 accuracy, but not the bits of the launch without the flag (the sum is ordered differently). It
+ * runs whatever Winograd or the bf16 split would have chosen, through yolo_conv_fwd_ws / yolo_conv_fwd_batch with the workspace
+ * yolo_conv_workspace_bytes asks for (16-byte aligned), else YOLO_ERR_WORKSPACE (always from yolo_conv_fwd, which has none).
+ * Together with YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, with a forced tile, on a 16-bit
+ * descriptor or with cin of 3 or 4 the flag is refused with YOLO_ERR_UNSUPPORTED and nothing is launched. Without the flag nothing
+ * changes. */
 enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8,
-       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16 };
+       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -147,7 +157,10 @@ int yolo_conv_fwd_batch(const yolo_conv_op* ops, int n_ops, int32_t* nan_flag, v
  * epilogue; 1 / 2.25 of the direct convolution's multiplications, same result within a few ulp of the transforms'
  * additions. yolo_conv_workspace_bytes: what descriptor d needs (0 = the launch takes no workspace); a NULL or smaller
  * workspace makes tile 0 fall back to the direct kernels of yolo_conv_fwd, tile 13 (= Winograd, forced) fail.
- * Streams that run concurrently need a workspace each. */
+ * Streams that run concurrently need a workspace each.
+ * With YOLO_FLAG_SPLIT_K set on d: the partial sums, S * n * Ho * Wo * cout_pad4 * 4 bytes, S = yolo_conv_splitk_slices(d), cout_pad4 =
+ * cout rounded up to 4 (it grows linearly with the batch); 0 wherever a launch of d would refuse the flag (its shape or dtype, a forced
+ * tile, one of the other kernel flags next to it). */
 size_t yolo_conv_workspace_bytes(const yolo_conv_desc* d);
 int yolo_conv_fwd_ws(const yolo_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
                      const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, void* stream);
@@ -160,6 +173,13 @@ int yolo_conv_num_tiles(void);
  * on its exact kernel: what an inference plan should flag. */
 int yolo_conv_split3_supported(const yolo_conv_desc* d);
 int yolo_conv_split3_eligible(const yolo_conv_desc* d);
+/* YOLO_FLAG_SPLIT_K for plans (n, flags and tile of d are not looked at). yolo_conv_splitk_supported: 1 when the library honours the
+ * flag on d's shape and dtype. yolo_conv_splitk_eligible: 1 when, in addition, the shape measured faster that way at batch 1 than on
+ * the kernel a default plan gives it: what a latency-mode plan should flag. yolo_conv_splitk_slices: the number of K slices S (1 ..
+ * 32) such a launch uses, 0 where unsupported. */
+int yolo_conv_splitk_supported(const yolo_conv_desc* d);
+int yolo_conv_splitk_eligible(const yolo_conv_desc* d);
+int yolo_conv_splitk_slices(const yolo_conv_desc* d);
 /* YOLO_FLAG_SPLIT_BF16 with the weights split once instead of by every block of every launch (inference).
  * yolo_split3_weights reads the row-major fp32 section of w_packed (yolo_pack_weights, YOLO_F32) and writes the prepared buffer:
  *     [the packed weights, P = yolo_packed_weight_bytes(cout, cin, ksize, YOLO_F32) rounded up to 16 bytes]

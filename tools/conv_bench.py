@@ -4,6 +4,8 @@
   python tools/conv_bench.py --layer c52_3x3 --tile 0 --reps 20
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3 --rounds 5      (YOLO_FLAG_SPLIT_BF16; median and spread of 5 rounds)
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3-ready --rounds 5    (the same on weights split once: yolo_split3_weights)
+  python tools/conv_bench.py --splitk --rounds 7 --reps 100      (batch 1: every fp32 conv shape of the 416 and 608 networks on the
+                                                                  default plan's launch and as YOLO_FLAG_SPLIT_K, alternating)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
 
 Layers are the dominant YOLOv3 shapes at batch 32, 416x416.
@@ -110,6 +112,72 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     return ms
 
 
+def splitk_table(dev, reps, rounds, sizes=(416, 608)):
+    """Batch 1, every distinct fp32 conv launch of the default eval plan (its flags, its prepared weights, its workspace) against the
+    same launch with YOLO_FLAG_SPLIT_K, on the plan's own buffers after one forward. The two are timed in alternating rounds of
+    `reps` back-to-back launches; a shape counts as faster cut along K when the slowest split-K round beats the fastest default
+    round, i.e. by more than the spread that rounds of the same code show."""
+    import yolo_for_turbines_amd as yt
+    lib = L.lib()
+    stream = L.current_stream()
+    model = yt.YOLOv3(num_classes=80).to(dev).eval()
+    print(f"# batch 1, {rounds} alternating rounds of {reps} launches; us per launch: median [min..max]; S = K slices, blocks = workgroups "
+          "of the first split-K launch; wins = max(split-K) < min(default)")
+    print("# size  h    w   cin  cout k s out res | default: tile flags   med     min     max | split-K: S blocks   med     min     max | ratio wins")
+    for size in sizes:
+        x = torch.rand(1, 3, size, size, device=dev)
+        with torch.no_grad():
+            preds = model(x)                                          # builds the plan, packs the weights, leaves real activations
+        plan = list(model._engine._plans.values())[-1]
+        seen = set()
+        for i in range(plan.first, len(plan.table)):
+            e = plan.table[i]
+            d = e.d
+            res = bool(d.flags & L.FLAG_RESIDUAL)
+            key = (d.h, d.w, d.cin, d.cout, d.ksize, d.stride, d.out_mode, res, d.act)
+            if key in seen or not lib.yolo_conv_splitk_supported(C.byref(d)):
+                continue
+            seen.add(key)
+            base = (L.ConvOp * 1)()
+            C.memmove(base, C.byref(e), C.sizeof(L.ConvOp))
+            sk = (L.ConvOp * 1)()
+            C.memmove(sk, C.byref(e), C.sizeof(L.ConvOp))
+            sk[0].d.flags = (d.flags & (L.FLAG_RESIDUAL | L.FLAG_NANCHECK)) | L.FLAG_SPLIT_K
+            sk[0].w_packed = model._engine.packed(plan.blocks[i], dev).w.data_ptr()
+            need = lib.yolo_conv_workspace_bytes(C.byref(sk[0].d))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            sk[0].workspace, sk[0].workspace_bytes = ws.data_ptr(), need
+            flag = plan.nan_flag.data_ptr()
+
+            def timed(op):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    L.check(lib.yolo_conv_fwd_batch(op, 1, flag, stream), "conv")
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / reps * 1e3
+            for op in (base, sk):
+                for _ in range(5):
+                    L.check(lib.yolo_conv_fwd_batch(op, 1, flag, stream), "conv")
+            torch.cuda.synchronize()
+            tb, tk = [], []
+            for _ in range(rounds):
+                tb.append(timed(base))
+                tk.append(timed(sk))
+            tb.sort()
+            tk.sort()
+            S = lib.yolo_conv_splitk_slices(C.byref(d))
+            pad = d.ksize // 2
+            ho, wo = (d.h + 2 * pad - d.ksize) // d.stride + 1, (d.w + 2 * pad - d.ksize) // d.stride + 1
+            blocks = -(-ho * wo // 64) * -(-d.cout // 64) * S
+            mb, mk = tb[len(tb) // 2], tk[len(tk) // 2]
+            print(f"{size:5d} {d.h:4d} {d.w:4d} {d.cin:5d} {d.cout:5d} {d.ksize} {d.stride} {d.out_mode:3d} {int(res):3d} | "
+                  f"{lib.yolo_conv_pick_tile(C.byref(d)):13d} {d.flags:5d} {mb:7.1f} {tb[0]:7.1f} {tb[-1]:7.1f} | "
+                  f"{S:10d} {blocks:6d} {mk:7.1f} {tk[0]:7.1f} {tk[-1]:7.1f} | {mk / mb:5.2f} {int(tk[-1] < tb[0])}", flush=True)
+        del preds
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layer", default="all")
@@ -122,8 +190,12 @@ def main():
     ap.add_argument("--split3-ready", action="store_true", help="YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY on prepared weights")
     ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
+    ap.add_argument("--splitk", action="store_true", help="batch-1 table: the default plan's launch against YOLO_FLAG_SPLIT_K, per conv shape")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.splitk:
+        splitk_table(dev, a.reps, a.rounds)
+        return
     names = list(LAYERS) if a.layer == "all" else a.layer.split(",")
     nt = L.lib().yolo_conv_num_tiles()
     tiles = list(range(1, nt + 1)) if a.tile == "all" else [int(t) for t in a.tile.split(",")]

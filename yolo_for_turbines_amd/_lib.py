@@ -15,6 +15,7 @@ F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_LEAKY, ACT_MISH = 0, 1, 2
 OUT_NHWC, OUT_UPSAMPLE2X, OUT_HEAD = 0, 1, 2
 FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY, FLAG_SPLIT_BF16, FLAG_SPLIT_WEIGHTS_READY = 1, 2, 4, 8, 16
+FLAG_SPLIT_K = 32
 
 
 class PackItem(C.Structure):
@@ -97,6 +98,9 @@ _SIGS = {
     "yolo_conv_pick_tile": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_split3_eligible": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_split3_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "yolo_conv_splitk_supported": (C.c_int, [C.POINTER(ConvDesc)]),
+    "yolo_conv_splitk_eligible": (C.c_int, [C.POINTER(ConvDesc)]),
+    "yolo_conv_splitk_slices": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_split3_weight_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "yolo_split3_weights": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_conv_num_tiles": (C.c_int, []),

@@ -235,6 +235,18 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     if (!x || !w || !scale || !shift || !y) return fail(YOLO_ERR_ARG, "conv: null pointer");
     if ((d->flags & YOLO_FLAG_RESIDUAL) && !residual) return fail(YOLO_ERR_ARG, "conv: residual flag without pointer");
     if ((d->flags & YOLO_FLAG_NANCHECK) && !nan_flag) return fail(YOLO_ERR_ARG, "conv: nancheck flag without pointer");
+    // the split-K pair runs whatever Winograd or the bf16 split would have chosen: it goes with none of their flags, with no forced tile
+    const bool splitk = d->flags & YOLO_FLAG_SPLIT_K;
+    if (splitk) {
+        if (d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_K goes with none of YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16, "
+                                              "YOLO_FLAG_SPLIT_WEIGHTS_READY");
+        if (d->tile != 0 || !splitk_supported(d))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_K needs an fp32 layer with ksize 1 or 3, stride 1 or 2, cin %% 32 == 0 and tile 0");
+        if (!ws || ws_bytes < splitk_workspace_bytes(d))
+            return fail(YOLO_ERR_WORKSPACE, "conv: YOLO_FLAG_SPLIT_K needs a workspace of %zu bytes (yolo_conv_workspace_bytes)",
+                        splitk_workspace_bytes(d));
+    }
     const bool filters_ready = d->flags & YOLO_FLAG_FILTERS_READY;
     if (filters_ready && (d->dtype != YOLO_F32 || f32_family(d, residual, ws ? ws_bytes : 0) != F32Family::Wino4))
         return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_READY on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
@@ -263,6 +275,7 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     a.nc5 = d->out_mode == YOLO_OUT_HEAD ? d->cout / 3 : 1;
     a.tiles_n = 0;
     const bool smallc = a.Cin == 4;
+    if (splitk) return conv_splitk_launch(a, d, ws, ws_bytes, s);
     if (split3) {
         if (d->flags & YOLO_FLAG_SPLIT_WEIGHTS_READY) a.w_planes = (const char*)w + split3_planes_offset(d);
         return conv_split3_launch(a, d->tile == kTileF32Rs ? 0 : d->tile, s);
@@ -317,6 +330,12 @@ int yolo_conv_split3_supported(const yolo_conv_desc* d) {
 
 int yolo_conv_split3_eligible(const yolo_conv_desc* d) { return yolo_conv_split3_supported(d) && yolo::split3_eligible(d); }
 
+int yolo_conv_splitk_supported(const yolo_conv_desc* d) { return !yolo::validate(d) && yolo::splitk_supported(d); }
+
+int yolo_conv_splitk_eligible(const yolo_conv_desc* d) { return yolo_conv_splitk_supported(d) && yolo::splitk_eligible(d); }
+
+int yolo_conv_splitk_slices(const yolo_conv_desc* d) { return yolo_conv_splitk_supported(d) ? yolo::splitk_slices(d, nullptr) : 0; }
+
 size_t yolo_split3_weight_bytes(const yolo_conv_desc* d) { return d && yolo_conv_split3_supported(d) ? yolo::split3_weight_bytes(d) : 0; }
 
 int yolo_split3_weights(const yolo_conv_desc* d, const void* w_packed, void* out, void* stream) {
@@ -333,6 +352,11 @@ int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, 
 
 size_t yolo_conv_workspace_bytes(const yolo_conv_desc* d) {
     if (yolo::validate(d)) return 0;
+    if (d->flags & YOLO_FLAG_SPLIT_K)               // 0 wherever the launch refuses the flag: another kernel flag, a forced tile, the shape
+        return !(d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY)) && d->tile == 0 &&
+                       yolo::splitk_supported(d)
+                   ? yolo::splitk_workspace_bytes(d)
+                   : 0;
     switch (yolo::f32_family(d, nullptr, SIZE_MAX)) {          // (the caller will bring what this asks for)
     case yolo::F32Family::Wino4: return yolo::wino4_workspace_bytes(d);
     case yolo::F32Family::Wino: return yolo::wino_workspace_bytes(d);

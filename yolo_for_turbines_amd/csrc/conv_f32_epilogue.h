@@ -1,5 +1,6 @@
 // conv_f32_epilogue.h — what the fp32 implicit-GEMM kernels of conv_f32.hip (exact f32 products) and conv_split3_f32.hip
-// (three-way bf16 split products) share: the launch arguments and the epilogue. Both accumulate 32x32 MFMA tiles whose C/D
+// (three-way bf16 split products) share: the launch arguments and the epilogue (conv_splitk_f32.hip takes the arguments; its
+// combine pass ends in the epilogue's per-pixel stores, conv_f32_store4 / conv_f32_store1). Both accumulate 32x32 MFMA tiles whose C/D
 // layout is the same, so scale / shift / activation, the transpose through LDS, residual, 2x upsampling store, head layout and
 // NaN flag are one piece of code.
 #pragma once
@@ -37,6 +38,60 @@ int conv_split3_launch(const ConvArgs& a, int tile, hipStream_t s);
 size_t split3_planes_offset(const yolo_conv_desc* d);
 size_t split3_weight_bytes(const yolo_conv_desc* d);
 int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* out, hipStream_t s);
+
+// conv_splitk_f32.hip (exact f32 products, K cut into slices whose partial sums a second launch combines; YOLO_FLAG_SPLIT_K)
+bool splitk_supported(const yolo_conv_desc* d);
+bool splitk_eligible(const yolo_conv_desc* d);
+int splitk_slices(const yolo_conv_desc* d, int* steps);          // S; *steps = K steps of 32 per slice
+size_t splitk_workspace_bytes(const yolo_conv_desc* d);
+int conv_splitk_launch(const ConvArgs& a, const yolo_conv_desc* d, void* ws, size_t ws_bytes, hipStream_t s);
+
+// What follows scale / shift / activation for one output pixel m (shared by conv_f32_epilogue and splitk_combine_f32, so the store
+// paths exist once): residual, NaN check, store. conv_f32_store4: channels n .. n + 3 as one 16-byte piece, YOLO_OUT_NHWC or
+// YOLO_OUT_UPSAMPLE2X with y / residual views that are multiples of 4. conv_f32_store1: one channel, any output mode
+// (head_a, head_k = n / nc5, n % nc5 for YOLO_OUT_HEAD).
+__device__ __forceinline__ void conv_f32_store4(const ConvArgs& p, int m, int n, f32x4 v, int HoWo, bool has_res, bool nan_chk, bool& saw_nan) {
+    if (has_res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.r_ld + p.r_off + n);
+    if (nan_chk && (v[0] != v[0] || v[1] != v[1] || v[2] != v[2] || v[3] != v[3])) saw_nan = true;
+    if (p.out_mode == YOLO_OUT_NHWC) {
+        *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.y_ld + p.y_off + n) = v;
+    } else {                                        // YOLO_OUT_UPSAMPLE2X
+        const int img = m / HoWo;
+        const int rem = m - img * HoWo;
+        const int ho = rem / p.Wo;
+        const int wo = rem - ho * p.Wo;
+        const int W2 = 2 * p.Wo;
+        float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
+        *reinterpret_cast<f32x4*>(d) = v;
+        *reinterpret_cast<f32x4*>(d + p.y_ld) = v;
+        *reinterpret_cast<f32x4*>(d + (size_t)W2 * p.y_ld) = v;
+        *reinterpret_cast<f32x4*>(d + (size_t)(W2 + 1) * p.y_ld) = v;
+    }
+}
+
+__device__ __forceinline__ void conv_f32_store1(const ConvArgs& p, int m, int n, float v, int HoWo, int head_a, int head_k, bool has_res,
+                                                bool nan_chk, bool& saw_nan) {
+    if (has_res) v += p.res[(size_t)m * p.r_ld + p.r_off + n];
+    if (nan_chk && v != v) saw_nan = true;
+    if (p.out_mode == YOLO_OUT_NHWC) {
+        p.y[(size_t)m * p.y_ld + p.y_off + n] = v;
+    } else {
+        const int img = m / HoWo;
+        const int rem = m - img * HoWo;
+        const int ho = rem / p.Wo;
+        const int wo = rem - ho * p.Wo;
+        if (p.out_mode == YOLO_OUT_UPSAMPLE2X) {
+            const int W2 = 2 * p.Wo;
+            float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
+            d[0] = v;
+            d[p.y_ld] = v;
+            d[(size_t)W2 * p.y_ld] = v;
+            d[(size_t)(W2 + 1) * p.y_ld] = v;
+        } else {  // YOLO_OUT_HEAD: (B,3,g,g,5+nc)
+            p.y[((size_t)((img * 3 + head_a) * p.Ho + ho) * p.Wo + wo) * p.nc5 + head_k] = v;
+        }
+    }
+}
 
 // Epilogue of a BM x BN block of 256 threads = 2 x 2 waves with (BM/2) x (BN/2) wave tiles of 32x32 MFMA tiles.
 // C/D map of the 32x32 tile: column (N = cout) = lane & 31, row (M = pixel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
@@ -81,23 +136,7 @@ __device__ __forceinline__ void conv_f32_epilogue(const ConvArgs& p, f32x16 (&ac
             const int row = idx / C4, c4 = idx - row * C4;
             const int m = m0 + row, n = n0 + c4 * 4;
             if (m >= p.M || n >= p.Cout) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(ost + row * OLD + c4 * 4);
-            if (has_res) v += *reinterpret_cast<const f32x4*>(p.res + (size_t)m * p.r_ld + p.r_off + n);
-            if (nan_chk && (v[0] != v[0] || v[1] != v[1] || v[2] != v[2] || v[3] != v[3])) saw_nan = true;
-            if (p.out_mode == YOLO_OUT_NHWC) {
-                *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.y_ld + p.y_off + n) = v;
-            } else {                                        // YOLO_OUT_UPSAMPLE2X
-                const int img = m / HoWo;
-                const int rem = m - img * HoWo;
-                const int ho = rem / p.Wo;
-                const int wo = rem - ho * p.Wo;
-                const int W2 = 2 * p.Wo;
-                float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
-                *reinterpret_cast<f32x4*>(d) = v;
-                *reinterpret_cast<f32x4*>(d + p.y_ld) = v;
-                *reinterpret_cast<f32x4*>(d + (size_t)W2 * p.y_ld) = v;
-                *reinterpret_cast<f32x4*>(d + (size_t)(W2 + 1) * p.y_ld) = v;
-            }
+            conv_f32_store4(p, m, n, *reinterpret_cast<const f32x4*>(ost + row * OLD + c4 * 4), HoWo, has_res, nan_chk, saw_nan);
         }
         if (nan_chk && saw_nan) atomicOr(p.nan_flag, 2);
         return;
@@ -122,27 +161,7 @@ __device__ __forceinline__ void conv_f32_epilogue(const ConvArgs& p, f32x16 (&ac
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
                 if (m >= p.M || !nv) continue;
-                float v = acc[i][j][r];
-                if (has_res) v += p.res[(size_t)m * p.r_ld + p.r_off + n];
-                if (nan_chk && v != v) saw_nan = true;
-                if (p.out_mode == YOLO_OUT_NHWC) {
-                    p.y[(size_t)m * p.y_ld + p.y_off + n] = v;
-                } else {
-                    const int img = m / HoWo;
-                    const int rem = m - img * HoWo;
-                    const int ho = rem / p.Wo;
-                    const int wo = rem - ho * p.Wo;
-                    if (p.out_mode == YOLO_OUT_UPSAMPLE2X) {
-                        const int W2 = 2 * p.Wo;
-                        float* d = p.y + ((size_t)(img * 2 * p.Ho + 2 * ho) * W2 + 2 * wo) * p.y_ld + p.y_off + n;
-                        d[0] = v;
-                        d[p.y_ld] = v;
-                        d[(size_t)W2 * p.y_ld] = v;
-                        d[(size_t)(W2 + 1) * p.y_ld] = v;
-                    } else {  // YOLO_OUT_HEAD: (B,3,g,g,5+nc)
-                        p.y[((size_t)((img * 3 + head_a) * p.Ho + ho) * p.Wo + wo) * p.nc5 + head_k] = v;
-                    }
-                }
+                conv_f32_store1(p, m, n, acc[i][j][r], HoWo, head_a, head_k, has_res, nan_chk, saw_nan);
             }
         }
     }

@@ -405,8 +405,13 @@ class Plan:
             if i >= self.first:
                 e.x = self.phys[x.buf].data_ptr()
             e.w_packed, e.scale, e.shift = pk.w.data_ptr(), pk.scale.data_ptr(), pk.shift.data_ptr()
+            # latency mode (ModelState.latency): the layers that measured faster at batch 1 cut along K (the library's
+            # splitk_eligible keeps the list; "all": every layer it can run that way). Such a launch takes none of the flags below.
+            if (dtype == "fp32" and state.latency and i >= self.first and not tile_override
+                    and (L.lib().yolo_conv_splitk_supported if state.latency == "all" else L.lib().yolo_conv_splitk_eligible)(C.byref(d))):
+                d.flags |= L.FLAG_SPLIT_K
             # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
-            if (dtype == "fp32" and i >= self.first and op["k"] == 3 and op["s"] == 1 and (tile_override or 0) in (0, 15)
+            elif (dtype == "fp32" and i >= self.first and op["k"] == 3 and op["s"] == 1 and (tile_override or 0) in (0, 15)
                     and L.lib().yolo_conv_workspace_bytes(C.byref(d))
                     and (d.tile == 15 or L.lib().yolo_conv_pick_tile(C.byref(d)) == 15)):
                 e.w_packed = pk.want_u4(d).data_ptr()
@@ -423,8 +428,8 @@ class Plan:
                 self.stem_pk = pk
             if op["pred"] is not None:
                 self.pred_ops[op["pred"]] = (i, op["Ho"], blk.conv.out_channels // 3)
-        # one workspace for the launches that take one (fp32 3x3 stride 1 -> Winograd, yolo_conv_fwd_ws): the table runs on one
-        # stream, so the largest request serves them all
+        # one workspace for the launches that take one (fp32 3x3 stride 1 -> Winograd, the partial sums of a split-K launch;
+        # yolo_conv_fwd_ws): the table runs on one stream, so the largest request serves them all
         lib = L.lib()
         need = [lib.yolo_conv_workspace_bytes(C.byref(self.table[i].d)) if i >= self.first else 0 for i in range(n_ops)]
         self.workspace = torch.empty(max(need), dtype=torch.uint8, device=device) if n_ops and max(need) else None
@@ -484,6 +489,10 @@ class ModelState:
         # weights split into their bf16 planes once per weight update (YOLO_FLAG_SPLIT_WEIGHTS_READY, PackedBlock.want_s3);
         # "inflight": the launches of True, every one splitting the packed weights itself (same bits; A/B runs).
         self.split3 = True
+        # fp32 inference at small batches (single-image detection, demo.py:41-42): True = eval plans made from then on run the
+        # layers that measured faster that way at batch 1 cut along K (YOLO_FLAG_SPLIT_K: fp32 accuracy, other bits; the plan's
+        # workspace grows linearly with the batch). "all": every layer the library can run that way (A/B runs, tests).
+        self.latency = False
         self.compute_dtype = None        # None: follow torch.autocast (fp32 outside it); or "fp32" / "fp16" / "bf16"
         self.ddp = None                  # (torch.distributed module, bucket MB) when data-parallel (dist.data_parallel)
         # Under an active torch.autocast the reference's forward returns its predictions in the autocast dtype (the head
@@ -511,19 +520,22 @@ class ModelState:
         return plan
 
     def __getstate__(self):
-        return {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3}
+        return {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3,
+                "latency": self.latency}
 
     def __setstate__(self, st):
         self.__init__()
         self.nan_check = st.get("nan_check", True)
         self.autocast_heads = st.get("autocast_heads", True)
         self.split3 = st.get("split3", True)
+        self.latency = st.get("latency", False)
 
     def __deepcopy__(self, memo):
         new = ModelState()
         new.nan_check = self.nan_check
         new.autocast_heads = self.autocast_heads
         new.split3 = self.split3
+        new.latency = self.latency
         return new
 
     def head_dtype(self):
@@ -656,7 +668,8 @@ class ModelState:
         with torch.cuda.device(x.device):
             stream = L.current_stream()
             dt = resolve_dtype(self.compute_dtype)
-            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt, self.split3)
+            latency = self.latency if dt == "fp32" and not self.tile_override else False
+            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt, self.split3, latency)
             plan = self._plans.get(key)
             if plan is None:
                 prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4, W=W)
