@@ -487,6 +487,36 @@ size_t yolo_nms_workspace_bytes(int b, int n);
 int yolo_nms(const float* boxes, int b, int n, double iou_threshold, double obj_threshold, int center,
              int32_t* keep_idx, int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- tiled detection of frames larger than the network input (nothing of the reference: its dataset was tiled offline) -- */
+/* HOST ONLY, no launch. Overlapping tiles of an h x w image: returns their number and, when origins_yx (HOST, may be NULL)
+ * is given, writes [y0, x0] rows in row-major tile order; cap = rows origins_yx has room for. Per axis, with length L, tile t,
+ * overlap o and stride s = t - o: L <= t is one tile at 0 (zero-padded at the bottom / right by the gather); otherwise
+ * n = ceil((L - t) / s) + 1 tiles at k s for k < n - 1 and the last one at L - t, flush with the edge (no padding).
+ * YOLO_ERR_ARG unless 0 <= o < t, all sizes are positive and cap covers the count. Any tile size (the network's multiple of 32
+ * is the caller's business). */
+int yolo_tile_grid(int h, int w, int tile_h, int tile_w, int overlap_h, int overlap_w, int32_t* origins_yx, int cap);
+/* img_hwc: uint8 (h, w, 3); origins_yx (device): n_tiles rows [y0, x0], any values (odd ones too; no alignment is assumed);
+ * out: (n_tiles, 3, tile_h, tile_w) fp32 = (float) u8 * (1.0f / 255.0f), the normalisation of yolo_letterbox; 0.0f outside the
+ * image. n_tiles <= 65535. */
+int yolo_tile_gather(const unsigned char* img_hwc, int h, int w, const int32_t* origins_yx, int n_tiles, int tile_h, int tile_w,
+                     float* out, void* stream);
+/* Threshold, remap to the frame and compact, in order. boxes: (n_tiles, n_per, 6) decoded rows [cx, cy, w, h, obj, cls]
+ * normalised to the tile (what yolo_decode3_hw writes); tiles: int32 [n_tiles][4] = {image, y0, x0, 0}, an image outside
+ * [0, n_images) (-1) marks a padding tile that contributes nothing; img_hw: int32 [n_images][2]; cand: (n_images, cap, 6);
+ * count: int32 [n_images], the running number of candidates per image: READ and ADVANCED here, so the tiles of a frame may
+ * arrive in several calls (zero it before the first). A row is a candidate iff (double) obj > obj_threshold (the test of
+ * yolo_nms: NaN and equality are out) and its remapped centre has cx' <= 1 and cy' <= 1 (not in a tile's zero padding).
+ * fp32, each operation rounded once: cx' = (cx tile_w + x0) / W, cy' = (cy tile_h + y0) / H, w' = (w tile_w) / W,
+ * h' = (h tile_h) / H; obj and cls are copied. The candidates of an image are stored in (call, tile, row) order - the
+ * input order yolo_nms breaks score ties by - at cand[image][count before ...]; rows at an index >= cap are not written but
+ * counted, so count[image] > cap tells the caller about the overflow. Nothing else in cand is touched. Three launches (block
+ * counts, one small in-order scan, writes), no atomics, no waiting between workgroups. n_tiles <= 65535 and
+ * n_tiles * n_per < 2^31 per call. */
+size_t yolo_tile_collect_workspace_bytes(int n_tiles, int n_per);
+int yolo_tile_collect(const float* boxes, int n_tiles, int n_per, const int32_t* tiles, const int32_t* img_hw, int n_images, int tile_h,
+                      int tile_w, double obj_threshold, float* cand, int cap, int32_t* count, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["iou_aligned", "calc_iou", "cells_to_boxes", "non_max_suppression", "decode_boxes", "nms_indices",
-           "detect", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
+           "detect", "detect_tiled", "tile_grid", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
            "augment_params", "augment_batch", "train_batch",
            "save_checkpoint", "load_checkpoint", "scaled_anchors"]
 
@@ -218,6 +218,167 @@ def detect_images(model, x, scaled_anchors, iou_threshold=0.45, obj_threshold=0.
     if flag is not None:
         eng.raise_on_nan(flag)
     return out
+
+
+# ------------------------------------------------------------------------------ tiled detection
+def _tile_hw(tile):
+    th, tw = _grid_hw(tile)
+    if th <= 0 or tw <= 0 or th % 32 or tw % 32:
+        raise ValueError(f"tile sides must be positive multiples of 32, got {th} x {tw}")
+    return th, tw
+
+
+def _overlap_px(overlap, th, tw):
+    """fraction | pixels | (per axis) -> (oh, ow) pixels: an int is a pixel count, anything else a fraction of the tile side."""
+    oh, ow = overlap if isinstance(overlap, (tuple, list)) else (overlap, overlap)
+
+    def px(o, t):
+        return int(o) if isinstance(o, int) and not isinstance(o, bool) else int(round(float(o) * t))
+    oh, ow = px(oh, th), px(ow, tw)
+    if not (0 <= oh < th and 0 <= ow < tw):
+        raise ValueError(f"overlap must satisfy 0 <= overlap < tile, got {oh} of {th}, {ow} of {tw} pixels")
+    return oh, ow
+
+
+def _tile_origins(h, w, th, tw, oh, ow):
+    """yolo_tile_grid: the flat [y0, x0, y0, x0, ...] list of one image's tiles in row-major order."""
+    lib = L.lib()
+    n = lib.yolo_tile_grid(h, w, th, tw, oh, ow, None, 0)
+    L.check(min(n, 0), "yolo_tile_grid")
+    buf = (C.c_int32 * (2 * n))()
+    L.check(min(lib.yolo_tile_grid(h, w, th, tw, oh, ow, buf, n), 0), "yolo_tile_grid")
+    return list(buf)
+
+
+def tile_grid(h, w, tile=416, overlap=0.2):
+    """Origins of the overlapping tiles an h x w image is cut into, an int32 (T, 2) tensor of [y0, x0] rows in row-major tile
+    order (``yolo_tile_grid``). ``tile``: t or (th, tw), any size. ``overlap``: a fraction of the tile side (``int(round(overlap *
+    t))`` pixels per axis), or pixels when given as int(s); a pair is (rows, columns). Per axis the stride is t - overlap; an axis
+    that is no longer than the tile has one tile at 0 (zero-padded), otherwise the last tile is flush with the edge."""
+    th, tw = _grid_hw(tile)
+    oh, ow = _overlap_px(overlap, th, tw)
+    return torch.tensor(_tile_origins(int(h), int(w), th, tw, oh, ow), dtype=torch.int32).reshape(-1, 2)
+
+
+def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_threshold=0.45, obj_threshold=0.5, box_format="center",
+                 batch=32, max_candidates=65536):
+    """Detection on frames that are larger than the network input, at native resolution: every frame is cut into overlapping
+    tiles (:func:`tile_grid`), the tiles of all frames run through ``model(x)`` in chunks of ``batch``, the decoded boxes
+    above ``obj_threshold`` are mapped back to their frame and compacted on the device (``yolo_tile_collect``), and one
+    per-class NMS per frame merges the duplicates along the seams. ``images``: one uint8 (H, W, 3) tensor / array or a list of
+    them (any sizes; on the host or already on the device). ``scaled_anchors``: for the TILE size, as for
+    :func:`detect_images` (``scaled_anchors(anchors, th, tw)``).
+
+    Returns ``(boxes (F, max_candidates, 6), keep (F, max_candidates) int32, count (F,) int32, candidates (F,) int32)``:
+    ``boxes[f, :candidates[f]]`` are frame f's candidates ``[cx, cy, w, h, obj, cls]`` normalised to that frame, in (tile, row)
+    order, zero rows behind them; ``keep`` / ``count`` index them as from :func:`nms_indices`. Everything is stream-ordered
+    with ONE host synchronisation, which reads ``candidates`` and the forwards' NaN flags together; the forward's exceptions are
+    raised as by :func:`detect_images`, and a frame with more than ``max_candidates`` candidates raises ``ValueError``.
+    A last chunk shorter than ``batch`` runs at its own size (a second plan of the model, at most two per call).
+    Not built: resampled / multi-scale tiling, heuristics for boxes cut by an interior tile edge, class-agnostic merging."""
+    th, tw = _tile_hw(tile)
+    oh, ow = _overlap_px(overlap, th, tw)
+    if not float(obj_threshold) >= 0:
+        raise ValueError(f"obj_threshold must be >= 0 (the zero rows behind the candidates must not pass it), got {obj_threshold}")
+    batch, cap = int(batch), int(max_candidates)
+    if batch < 1 or cap < 1:
+        raise ValueError(f"batch and max_candidates must be >= 1, got {batch} and {cap}")
+    if isinstance(images, torch.Tensor) and images.dim() == 3 or not isinstance(images, (list, tuple)):
+        images = [images]
+    ts = []
+    for im in images:
+        t = torch.as_tensor(im)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.numel() == 0:
+            raise ValueError("images must be uint8 (H, W, 3)")
+        ts.append(t)
+    if not ts:
+        raise ValueError("detect_tiled needs at least one image")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("detect_tiled runs on MI355X only (no CPU fallback)")
+    F = len(ts)
+    lib = L.lib()
+    # host tables: per tile [y0, x0] (gather) and {image, y0, x0, 0} (collect), per image [H, W]
+    origins, tiles, first = [], [], []
+    for f, t in enumerate(ts):
+        o = _tile_origins(int(t.shape[0]), int(t.shape[1]), th, tw, oh, ow)
+        first.append(len(origins) // 2)
+        origins += o
+        for k in range(0, len(o), 2):
+            tiles += [f, o[k], o[k + 1], 0]
+    T = len(origins) // 2
+    first.append(T)
+    hw = [int(v) for t in ts for v in t.shape[:2]]
+    host = _pinned(6 * T + 2 * F, torch.int32)
+    host.copy_(torch.tensor(origins + tiles + hw, dtype=torch.int32))
+    anc = [torch.as_tensor(a, dtype=torch.float32).reshape(3, 2) for a in scaled_anchors]
+    if any(a.device != dev for a in anc):
+        anc_host = _pinned(18, torch.float32)
+        anc_host.copy_(torch.cat([a.cpu().reshape(-1) for a in anc]))
+    chunks = [(s, min(batch, T - s)) for s in range(0, T, batch)]
+    eng = model._engine
+    with torch.cuda.device(dev):
+        stream = L.current_stream()
+        tab = host.to(dev, non_blocking=True)
+        d_origins, d_tiles, d_hw = tab[:2 * T], tab[2 * T:6 * T], tab[6 * T:]
+        if any(a.device != dev for a in anc):
+            anc = list(anc_host.to(dev, non_blocking=True).reshape(3, 3, 2))
+        anc = [a.contiguous() for a in anc]
+        frames = []
+        for t in ts:
+            if t.device.type != "cuda":
+                staged = _pinned(t.numel(), torch.uint8)
+                staged.copy_(t.reshape(-1))
+                t = staged.to(dev, non_blocking=True)
+            frames.append(t.to(dev).contiguous())
+        cand = torch.empty((F, cap, 6), dtype=torch.float32, device=dev)
+        tail = torch.empty(F + len(chunks), dtype=torch.int32, device=dev)       # candidates per image | NaN flag per chunk
+        L.check(lib.yolo_fill_zero(cand.data_ptr(), cand.numel() * 4, stream), "yolo_fill_zero")
+        L.check(lib.yolo_fill_zero(tail.data_ptr(), tail.numel() * 4, stream), "yolo_fill_zero")
+        x = torch.empty((min(batch, T), 3, th, tw), dtype=torch.float32, device=dev)
+        boxes = ws = None
+        eng._defer_nan, eng._pending_flag = True, None
+        try:
+            for c, (s, n) in enumerate(chunks):
+                f = max(k for k in range(F) if first[k] <= s)
+                while f < F and first[f] < s + n:                   # one gather per frame that has tiles in this chunk
+                    a, b = max(first[f], s), min(first[f + 1], s + n)
+                    if b > a:
+                        L.check(lib.yolo_tile_gather(frames[f].data_ptr(), hw[2 * f], hw[2 * f + 1], d_origins.data_ptr() + 8 * a, b - a,
+                                                     th, tw, x.data_ptr() + 4 * (a - s) * 3 * th * tw, stream), "yolo_tile_gather")
+                    f += 1
+                eng._pending_flag = None
+                with torch.no_grad():
+                    preds = model(x[:n])
+                if eng._pending_flag is not None:
+                    L.check(lib.yolo_copy_d2d(tail.data_ptr() + 4 * (F + c), eng._pending_flag.data_ptr(), 4, stream), "nan flag copy")
+                preds = [p if p.dtype == torch.float32 else p.float() for p in preds]
+                n_per = sum(3 * p.shape[2] * p.shape[3] for p in preds)
+                if boxes is None:
+                    boxes = torch.empty((x.shape[0], n_per, 6), dtype=torch.float32, device=dev)
+                    ws = _workspace(max(int(lib.yolo_tile_collect_workspace_bytes(x.shape[0], n_per)), 256), dev)
+                pp = (C.c_void_p * 3)(*[p.data_ptr() for p in preds])
+                st = (C.c_int64 * 15)(*[v for p in preds for v in p.stride()])
+                ap = (C.c_void_p * 3)(*[a.data_ptr() for a in anc])
+                gg = (C.c_int * 6)(*[v for p in preds for v in (p.shape[2], p.shape[3])])
+                L.check(lib.yolo_decode3_hw(pp, st, ap, gg, n, preds[0].shape[4] - 5, 0, boxes.data_ptr(), n_per, stream), "yolo_decode3")
+                L.check(lib.yolo_tile_collect(boxes.data_ptr(), n, n_per, d_tiles.data_ptr() + 16 * s, d_hw.data_ptr(), F, th, tw,
+                                              float(obj_threshold), cand.data_ptr(), cap, tail.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              stream), "yolo_tile_collect")
+        finally:
+            eng._defer_nan, eng._pending_flag = False, None
+        for t in frames:
+            t.record_stream(torch.cuda.current_stream())
+        keep, count = nms_indices(cand, iou_threshold, obj_threshold, box_format)
+        tail_host = tail.tolist()                                   # the one host synchronisation
+    flag = 0
+    for v in tail_host[F:]:
+        flag |= v
+    eng._raise_flag(flag)
+    for f in range(F):
+        if tail_host[f] > cap:
+            raise ValueError(f"image {f} has {tail_host[f]} candidates above obj_threshold {obj_threshold}, max_candidates is {cap}")
+    return cand, keep, count, tail[:F]
 
 
 # ------------------------------------------------------------------------------ targets
