@@ -516,6 +516,37 @@ size_t yolo_tile_collect_workspace_bytes(int n_tiles, int n_per);
 int yolo_tile_collect(const float* boxes, int n_tiles, int n_per, const int32_t* tiles, const int32_t* img_hw, int n_images, int tile_h,
                       int tile_w, double obj_threshold, float* cand, int cap, int32_t* count, void* workspace, size_t workspace_bytes,
                       void* stream);
+/* ---- pyramid levels: the same frame tiled again at other scales, and boxes cut by an interior tile edge dropped ---- */
+/* HOST ONLY, no launch. The size of the level of an h x w frame at `scale`: level_h = max(1, (int) rint(h * scale)), level_w
+ * likewise (round half to even, the rounding of the letterbox's resized size); scale 1.0 gives exactly (h, w). YOLO_ERR_ARG for
+ * non-positive sizes, a scale that is not finite, <= 0 or > 8, and a result beyond int. The tiles of a level are
+ * yolo_tile_grid(level_h, level_w, ...). */
+int yolo_tile_level_hw(int h, int w, double scale, int* level_h, int* level_w);
+/* yolo_tile_gather on the (level_h, level_w) level of the frame, which is never materialised: output pixel (ty, tx) of tile t is
+ * level pixel (y0 + ty, x0 + tx); inside the level its three channels are the frame resized to the level by the library's one
+ * uint8 INTER_LINEAR (OpenCV's fixed point, the arithmetic of yolo_letterbox), then (float) u8 * (1.0f / 255.0f); 0.0f outside the
+ * level. With (level_h, level_w) == (h, w) the bytes are yolo_tile_gather's. Every output pixel reads a 2 x 2 neighbourhood of
+ * the frame, so a scale below 0.5 skips source pixels exactly as yolo_letterbox does on a whole frame: there is no area filter.
+ * Origins, limits and error codes as for yolo_tile_gather. */
+int yolo_tile_gather_scaled(const unsigned char* img_hwc, int h, int w, int level_h, int level_w, const int32_t* origins_yx, int n_tiles,
+                            int tile_h, int tile_w, float* out, void* stream);
+/* yolo_tile_collect for tiles of several levels. tiles: int32 [n_tiles][4] = {image, y0, x0, level}, (y0, x0) in pixels of the
+ * level; level_hw: int32 [n_levels][2] = {H, W} of every level (of all images: a level belongs to one image). A tile whose image
+ * is outside [0, n_images) or whose level is outside [0, n_levels) contributes nothing. The remap is yolo_tile_collect's with
+ * the level's size for the frame's (normalised coordinates do not depend on the scale): cx' = (cx tile_w + x0) / W,
+ * cy' = (cy tile_h + y0) / H, w' = (w tile_w) / W, h' = (h tile_h) / H.
+ * Seam test (off for edge_margin < 0; NaN is YOLO_ERR_ARG), fp32 with one rounding per operation, in tile pixels:
+ * px = cx tile_w, pw = w tile_w, hx = pw 0.5, left = px - hx, right = px + hx, and top / bottom likewise from cy, h, tile_h. A side
+ * of the tile is interior when it is not on the level's border: left iff x0 > 0, right iff x0 + tile_w < W, top iff y0 > 0,
+ * bottom iff y0 + tile_h < H. The row is cut iff left < edge_margin at an interior left side, or
+ * right > (float) tile_w - edge_margin at an interior right side, or the same for top / bottom. Equality is not cut and NaN
+ * coordinates are not cut. A row is a candidate iff (double) obj > obj_threshold, cx' <= 1 and cy' <= 1, and it is not cut.
+ * Order, the count protocol across calls, overflow, workspace (yolo_tile_collect_workspace_bytes), limits and "three launches, no
+ * atomics, no waiting" are yolo_tile_collect's; with edge_margin < 0 and level_hw[level of a tile] = img_hw[its image] so are
+ * the bytes. YOLO_ERR_ARG for n_levels <= 0. */
+int yolo_tile_collect_ex(const float* boxes, int n_tiles, int n_per, const int32_t* tiles, const int32_t* level_hw, int n_levels,
+                         int n_images, int tile_h, int tile_w, double obj_threshold, float edge_margin, float* cand, int cap,
+                         int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 
   python tools/tiles_bench.py                           3648 x 5472, one frame and four, fp32 and bf16, tile 416, overlap 0.2, batch 32
   python tools/tiles_bench.py --frames 1 --dtypes fp32 --rounds 5
+  python tools/tiles_bench.py --frames 1 --scales 1.0,0.5,0.25 --edge-margin 2.0      the pyramid and the seam test as well
 
 Per (dtype, frames):
   * the whole ``detect_tiled`` call on frames that are already on the device, against ``detect_images`` looped over the same tiles cut
@@ -12,6 +13,11 @@ Per (dtype, frames):
   * each stage alone, HIP events around --reps back-to-back launches on one full chunk: gather, forward, decode, collect, and the one NMS
     over (frames, max_candidates, 6). ``exposed`` is what the stages do not account for: (call - sum of the stages) per chunk, i.e. host
     time and idle gaps that the device sees.
+With --scales (more than the native level) or --edge-margin, per (dtype, frames) in addition:
+  * ``yolo_tile_gather_scaled`` on one chunk of tiles of every level that is not the frame itself, beside the plain gather (the
+    origins of the level's grid, repeated when the level has fewer tiles than a chunk);
+  * ``yolo_tile_collect_ex`` beside ``yolo_tile_collect`` on the same chunk, the seam test off and on;
+  * the whole call with ``scales=(1.0,)`` against the pyramid without and with ``edge_margin``, alternating round by round as above.
 The objectness threshold is taken from the model's own scores on the first chunk (--pass-rate of the rows pass), since synthetic
 weights have no meaningful 0.5."""
 import argparse
@@ -73,6 +79,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20, help="back-to-back launches per stage timing")
     ap.add_argument("--pass-rate", type=float, default=0.005, help="share of the decoded rows above the objectness threshold")
     ap.add_argument("--max-candidates", type=int, default=65536)
+    ap.add_argument("--scales", default="1.0", help="pyramid levels of detect_tiled, e.g. 1.0,0.5,0.25")
+    ap.add_argument("--edge-margin", type=float, default=None, help="seam test of detect_tiled, pixels of the tile")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -83,6 +91,8 @@ def main():
     lib = L.lib()
     dev = torch.device("cuda", torch.cuda.current_device())
     T_, B, cap = a.tile, a.batch, a.max_candidates
+    scales = [float(v) for v in a.scales.split(",")]
+    pyramid = scales != [1.0] or a.edge_margin is not None
     m = yt.YOLOv3(num_classes=a.classes)
     m.load_state_dict(onet.synth_state_dict(0, 3, a.classes, gain=0.8))
     m = m.cuda().eval()
@@ -149,6 +159,14 @@ def main():
             xg = torch.empty_like(x)
             gather = event_ms(lambda: L.check(lib.yolo_tile_gather(frame.data_ptr(), a.height, a.width, d_origins.data_ptr(), B, T_, T_,
                                                                    xg.data_ptr(), stream)), a.reps, torch)
+            gather_scaled = {}
+            for (lh, lw), org in (yt.tile_pyramid(a.height, a.width, T_, a.overlap, scales) if pyramid else []):
+                if (lh, lw) == (a.height, a.width):
+                    continue
+                d_org = org.repeat(-(-B // len(org)), 1)[:B].contiguous().cuda()
+                gather_scaled[f"{lh}x{lw}"] = event_ms(
+                    lambda: L.check(lib.yolo_tile_gather_scaled(frame.data_ptr(), a.height, a.width, lh, lw, d_org.data_ptr(), B, T_, T_,
+                                                                xg.data_ptr(), stream)), a.reps, torch)
             decode = event_ms(lambda: L.check(lib.yolo_decode3_hw(pp, st, ap_, gg, B, a.classes, 0, boxes.data_ptr(), n_per, stream)), a.reps, torch)
             d_tiles = torch.tensor([[0, int(y), int(x0), 0] for y, x0 in origins[:B].tolist()], dtype=torch.int32).cuda()
             d_hw = torch.tensor([[a.height, a.width]], dtype=torch.int32).cuda()
@@ -178,10 +196,54 @@ def main():
             print(f"  stages on a chunk of {B} tiles, ms per launch (per tile): gather {gather:.4f} ({gather / B:.5f})  forward {fwd:.4f} ({fwd / B:.5f})  "
                   f"decode {decode:.4f} ({decode / B:.5f})  collect {collect:.4f} ({collect / B:.5f})  | NMS over ({frames}, {cap}, 6): {nms:.4f}")
             print(f"  share of the forward: gather {100 * gather / fwd:.2f} %  collect {100 * collect / fwd:.2f} %   exposed per chunk {exposed:.4f} ms", flush=True)
-            print(json.dumps({"dtype": dt, "frames": frames, "tiles": tiles, "chunks": chunks, "threshold": thr, "candidates": ncand, "kept": kept,
-                              "ms_per_call": t, "host_frames_ms": host_ms,
-                              "stage_ms": {"gather": gather, "forward": fwd, "decode": decode, "collect": collect, "nms": nms},
-                              "exposed_ms_per_chunk": exposed}), file=sys.stderr, flush=True)
+            rec = {"dtype": dt, "frames": frames, "tiles": tiles, "chunks": chunks, "threshold": thr, "candidates": ncand, "kept": kept,
+                   "ms_per_call": t, "host_frames_ms": host_ms,
+                   "stage_ms": {"gather": gather, "forward": fwd, "decode": decode, "collect": collect, "nms": nms},
+                   "exposed_ms_per_chunk": exposed}
+            if pyramid:
+                # ---- the pyramid: the scaled gather beside the plain one, and whole calls against the native level alone
+                for k, v in gather_scaled.items():
+                    print(f"  gather of a chunk of {B} tiles of the {k} level: {v * 1e3:.1f} us (plain gather {gather * 1e3:.1f} us), "
+                          f"{100 * v / fwd:.2f} % of the forward")
+                per_frame_p = sum(len(o) for _, o in yt.tile_pyramid(a.height, a.width, T_, a.overlap, scales))
+
+                def tiled_p(margin):
+                    return yt.detect_tiled(m, imgs, sa, tile=T_, overlap=a.overlap, iou_threshold=0.45, obj_threshold=thr, batch=B,
+                                           max_candidates=cap, scales=scales, edge_margin=margin)
+                name = "pyramid" if scales != [1.0] else "scales=(1.0,)"
+                variants = {"scales=(1.0,)": (tiled, tiles)}
+                if scales != [1.0]:                             # with the native level alone this would be the first call again
+                    variants["pyramid"] = (lambda: tiled_p(None), frames * per_frame_p)
+                if a.edge_margin is not None:
+                    variants[f"{name}, edge_margin={a.edge_margin:g}"] = (lambda: tiled_p(a.edge_margin), frames * per_frame_p)
+                # yolo_tile_collect_ex beside yolo_tile_collect on the same chunk (level table = the frame), seam test off and on
+                collect_ex = {}
+                for mg in [-1.0] + ([a.edge_margin] if a.edge_margin is not None else []):
+                    def collect_ex_once(mg=mg):
+                        cnt.zero_()
+                        L.check(lib.yolo_tile_collect_ex(boxes.data_ptr(), B, n_per, d_tiles.data_ptr(), d_hw.data_ptr(), 1, 1, T_, T_, thr, mg,
+                                                         cand1.data_ptr(), cap, cnt.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+                    collect_ex["off" if mg < 0 else f"{mg:g}"] = event_ms(collect_ex_once, a.reps, torch)
+                print("  collect of the chunk: yolo_tile_collect %.1f us; yolo_tile_collect_ex %s" % (
+                    collect * 1e3, ", ".join(f"edge_margin {k}: {v * 1e3:.1f} us" for k, v in collect_ex.items())))
+                outs = {}
+                for k, (fn, _) in variants.items():
+                    for _ in range(2):
+                        outs[k] = fn()
+                tp = {k: [] for k in variants}
+                for _ in range(a.rounds):
+                    for k, (fn, _) in variants.items():
+                        tp[k].append(timed_round(fn, a.seconds, torch))
+                print(f"  levels {scales}: {per_frame_p} tiles per frame")
+                for k, (_, nt) in variants.items():
+                    md, lo, hi = summary(tp[k])
+                    print(f"  {k:28s} {md:9.3f} [{lo:9.3f}..{hi:9.3f}] ms per call   {md / nt:7.4f} [{lo / nt:7.4f}..{hi / nt:7.4f}] ms per tile"
+                          f"   candidates {outs[k][3].tolist()}, kept {outs[k][2].tolist()}")
+                rec.update({"scales": scales, "edge_margin": a.edge_margin, "gather_scaled_ms": gather_scaled, "collect_ex_ms": collect_ex,
+                            "pyramid_tiles": frames * per_frame_p, "pyramid_ms_per_call": tp,
+                            "pyramid_candidates": {k: o[3].tolist() for k, o in outs.items()},
+                            "pyramid_kept": {k: o[2].tolist() for k, o in outs.items()}})
+            print(json.dumps(rec), file=sys.stderr, flush=True)
     eng.compute_dtype = None
 
 

@@ -11,13 +11,14 @@ Two levels:
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib as L
 
 __all__ = ["iou_aligned", "calc_iou", "cells_to_boxes", "non_max_suppression", "decode_boxes", "nms_indices",
-           "detect", "detect_tiled", "tile_grid", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
+           "detect", "detect_tiled", "tile_grid", "tile_pyramid", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
            "augment_params", "augment_batch", "train_batch",
            "save_checkpoint", "load_checkpoint", "scaled_anchors"]
 
@@ -260,22 +261,70 @@ def tile_grid(h, w, tile=416, overlap=0.2):
     return torch.tensor(_tile_origins(int(h), int(w), th, tw, oh, ow), dtype=torch.int32).reshape(-1, 2)
 
 
+def _scales(scales):
+    """A non-empty sequence of distinct finite floats in (0, 8] -> list of float."""
+    try:
+        if isinstance(scales, (str, bytes)) or any(isinstance(v, (bool, str, bytes)) for v in scales):
+            raise TypeError
+        out = [float(v) for v in scales]
+    except (TypeError, ValueError):
+        raise ValueError(f"scales must be a non-empty sequence of numbers, got {scales!r}") from None
+    if not out or not all(math.isfinite(v) and 0.0 < v <= 8.0 for v in out):
+        raise ValueError(f"scales must be a non-empty sequence of finite numbers in (0, 8], got {scales!r}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"scales must not repeat a level, got {scales!r}")
+    return out
+
+
+def _level_hw(h, w, scale):
+    """yolo_tile_level_hw: (max(1, rint(h scale)), max(1, rint(w scale))), half to even."""
+    lh, lw = C.c_int(), C.c_int()
+    L.check(L.lib().yolo_tile_level_hw(int(h), int(w), float(scale), C.byref(lh), C.byref(lw)), "yolo_tile_level_hw")
+    return lh.value, lw.value
+
+
+def tile_pyramid(h, w, tile=416, overlap=0.2, scales=(1.0,)):
+    """The levels :func:`detect_tiled` cuts an h x w image into: a list with one ``((lh, lw), origins)`` entry per scale, in the
+    order given. ``(lh, lw)`` is the size of the image resized by that scale (``yolo_tile_level_hw``: ``max(1, rint(h * scale))``,
+    half to even; scale 1.0 is the image itself) and ``origins`` is ``tile_grid(lh, lw, tile, overlap)``, in pixels of the level.
+    ``scales``: distinct finite numbers in (0, 8]."""
+    out = []
+    for sc in _scales(scales):
+        lh, lw = _level_hw(h, w, sc)
+        out.append(((lh, lw), tile_grid(lh, lw, tile, overlap)))
+    return out
+
+
 def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_threshold=0.45, obj_threshold=0.5, box_format="center",
-                 batch=32, max_candidates=65536):
-    """Detection on frames that are larger than the network input, at native resolution: every frame is cut into overlapping
-    tiles (:func:`tile_grid`), the tiles of all frames run through ``model(x)`` in chunks of ``batch``, the decoded boxes
+                 batch=32, max_candidates=65536, scales=(1.0,), edge_margin=None):
+    """Detection on frames that are larger than the network input: every frame is cut into overlapping tiles
+    (:func:`tile_grid`), the tiles of all frames run through ``model(x)`` in chunks of ``batch``, the decoded boxes
     above ``obj_threshold`` are mapped back to their frame and compacted on the device (``yolo_tile_collect``), and one
     per-class NMS per frame merges the duplicates along the seams. ``images``: one uint8 (H, W, 3) tensor / array or a list of
     them (any sizes; on the host or already on the device). ``scaled_anchors``: for the TILE size, as for
-    :func:`detect_images` (``scaled_anchors(anchors, th, tw)``).
+    :func:`detect_images` (``scaled_anchors(anchors, th, tw)``), whatever the level.
+
+    ``scales``: the pyramid (:func:`tile_pyramid`), distinct finite numbers in (0, 8]. Every frame is tiled once per scale, on
+    the frame resized by it (``max(1, rint(side * scale))`` per side, half to even; the library's one uint8 INTER_LINEAR, sampled
+    by the gather, no resized frame is stored; a scale below 0.5 skips source pixels as :func:`letterbox` does), so an object
+    that no native tile sees whole is seen whole by a coarser level; the levels meet in the one NMS. The default ``(1.0,)`` is
+    native resolution only. A level that is no larger than the tile is a single zero-padded tile: with tile 416 a 5472 x 3648
+    frame is one at scale 416 / 5472 = 0.076 or below, and ``(1.0, 0.5, 0.25)`` ends at 1368 x 912, 4 x 3 tiles (187 + 48 + 12 tiles per frame).
+    ``edge_margin``: ``None`` (off) or pixels of the tile, >= 0. On, a box that reaches within ``edge_margin`` of a side of its
+    tile is dropped before the NMS when that side is interior, i.e. not on the level's border (``yolo_tile_collect_ex``): it is
+    the truncated copy of an object that a neighbouring tile or a coarser level reports whole, and its IoU with the whole box
+    is too low for the NMS to remove it. An object is lost if every tile of every level cuts it, so use it with an overlap
+    larger than the objects of the finest level or with a coarser level.
 
     Returns ``(boxes (F, max_candidates, 6), keep (F, max_candidates) int32, count (F,) int32, candidates (F,) int32)``:
-    ``boxes[f, :candidates[f]]`` are frame f's candidates ``[cx, cy, w, h, obj, cls]`` normalised to that frame, in (tile, row)
-    order, zero rows behind them; ``keep`` / ``count`` index them as from :func:`nms_indices`. Everything is stream-ordered
+    ``boxes[f, :candidates[f]]`` are frame f's candidates ``[cx, cy, w, h, obj, cls]`` normalised to that frame, in (level, tile,
+    row) order with the levels in the order of ``scales`` (the order :func:`nms_indices` breaks score ties by), zero rows behind
+    them; ``keep`` / ``count`` index them as from :func:`nms_indices`. ``max_candidates`` counts a frame's candidates over all its
+    levels. The tiles are in (frame, level, tile) order and a chunk runs across levels and frames. Everything is stream-ordered
     with ONE host synchronisation, which reads ``candidates`` and the forwards' NaN flags together; the forward's exceptions are
     raised as by :func:`detect_images`, and a frame with more than ``max_candidates`` candidates raises ``ValueError``.
     A last chunk shorter than ``batch`` runs at its own size (a second plan of the model, at most two per call).
-    Not built: resampled / multi-scale tiling, heuristics for boxes cut by an interior tile edge, class-agnostic merging."""
+    Not built: class-agnostic merging; area-filtered downscaling; merging the two halves of a box across a seam."""
     th, tw = _tile_hw(tile)
     oh, ow = _overlap_px(overlap, th, tw)
     if not float(obj_threshold) >= 0:
@@ -283,6 +332,15 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
     batch, cap = int(batch), int(max_candidates)
     if batch < 1 or cap < 1:
         raise ValueError(f"batch and max_candidates must be >= 1, got {batch} and {cap}")
+    scales = _scales(scales)
+    if edge_margin is not None:
+        try:
+            margin = float(edge_margin)
+        except (TypeError, ValueError):
+            margin = math.nan
+        if isinstance(edge_margin, bool) or not (math.isfinite(margin) and margin >= 0):
+            raise ValueError(f"edge_margin must be None or a finite number >= 0 (pixels of the tile), got {edge_margin!r}")
+    plain = scales == [1.0] and edge_margin is None             # today's launches: yolo_tile_gather, yolo_tile_collect
     if isinstance(images, torch.Tensor) and images.dim() == 3 or not isinstance(images, (list, tuple)):
         images = [images]
     ts = []
@@ -298,19 +356,25 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
         raise RuntimeError("detect_tiled runs on MI355X only (no CPU fallback)")
     F = len(ts)
     lib = L.lib()
-    # host tables: per tile [y0, x0] (gather) and {image, y0, x0, 0} (collect), per image [H, W]
-    origins, tiles, first = [], [], []
+    # host tables: per tile [y0, x0] (gather) and {image, y0, x0, level} (collect), per image [H, W], per level [H, W].
+    # A level is one (frame, scale) pair, numbered f * len(scales) + k; runs[r] = (first tile, frame, level H, level W).
+    origins, tiles, runs, lev = [], [], [], []
     for f, t in enumerate(ts):
-        o = _tile_origins(int(t.shape[0]), int(t.shape[1]), th, tw, oh, ow)
-        first.append(len(origins) // 2)
-        origins += o
-        for k in range(0, len(o), 2):
-            tiles += [f, o[k], o[k + 1], 0]
+        for sc in scales:
+            lh, lw = _level_hw(t.shape[0], t.shape[1], sc)
+            o = _tile_origins(lh, lw, th, tw, oh, ow)
+            runs.append((len(origins) // 2, f, lh, lw))
+            origins += o
+            for k in range(0, len(o), 2):
+                tiles += [f, o[k], o[k + 1], 0 if plain else len(lev) // 2]   # yolo_tile_collect's spare field stays 0
+            lev += [lh, lw]
     T = len(origins) // 2
-    first.append(T)
+    runs.append((T, F, 0, 0))
     hw = [int(v) for t in ts for v in t.shape[:2]]
-    host = _pinned(6 * T + 2 * F, torch.int32)
-    host.copy_(torch.tensor(origins + tiles + hw, dtype=torch.int32))
+    if plain:
+        lev = []
+    host = _pinned(6 * T + 2 * F + len(lev), torch.int32)
+    host.copy_(torch.tensor(origins + tiles + hw + lev, dtype=torch.int32))
     anc = [torch.as_tensor(a, dtype=torch.float32).reshape(3, 2) for a in scaled_anchors]
     if any(a.device != dev for a in anc):
         anc_host = _pinned(18, torch.float32)
@@ -320,7 +384,7 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
     with torch.cuda.device(dev):
         stream = L.current_stream()
         tab = host.to(dev, non_blocking=True)
-        d_origins, d_tiles, d_hw = tab[:2 * T], tab[2 * T:6 * T], tab[6 * T:]
+        d_origins, d_tiles, d_hw, d_lev = tab[:2 * T], tab[2 * T:6 * T], tab[6 * T:6 * T + 2 * F], tab[6 * T + 2 * F:]
         if any(a.device != dev for a in anc):
             anc = list(anc_host.to(dev, non_blocking=True).reshape(3, 3, 2))
         anc = [a.contiguous() for a in anc]
@@ -340,13 +404,18 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
         eng._defer_nan, eng._pending_flag = True, None
         try:
             for c, (s, n) in enumerate(chunks):
-                f = max(k for k in range(F) if first[k] <= s)
-                while f < F and first[f] < s + n:                   # one gather per frame that has tiles in this chunk
-                    a, b = max(first[f], s), min(first[f + 1], s + n)
-                    if b > a:
+                r = max(k for k in range(len(runs) - 1) if runs[k][0] <= s)
+                while runs[r][0] < s + n:                           # one gather per (frame, level) that has tiles in this chunk
+                    a, b = max(runs[r][0], s), min(runs[r + 1][0], s + n)
+                    f, lh, lw = runs[r][1:]
+                    if b > a and (lh, lw) == (hw[2 * f], hw[2 * f + 1]):
                         L.check(lib.yolo_tile_gather(frames[f].data_ptr(), hw[2 * f], hw[2 * f + 1], d_origins.data_ptr() + 8 * a, b - a,
                                                      th, tw, x.data_ptr() + 4 * (a - s) * 3 * th * tw, stream), "yolo_tile_gather")
-                    f += 1
+                    elif b > a:
+                        L.check(lib.yolo_tile_gather_scaled(frames[f].data_ptr(), hw[2 * f], hw[2 * f + 1], lh, lw,
+                                                            d_origins.data_ptr() + 8 * a, b - a, th, tw,
+                                                            x.data_ptr() + 4 * (a - s) * 3 * th * tw, stream), "yolo_tile_gather_scaled")
+                    r += 1
                 eng._pending_flag = None
                 with torch.no_grad():
                     preds = model(x[:n])
@@ -362,9 +431,15 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
                 ap = (C.c_void_p * 3)(*[a.data_ptr() for a in anc])
                 gg = (C.c_int * 6)(*[v for p in preds for v in (p.shape[2], p.shape[3])])
                 L.check(lib.yolo_decode3_hw(pp, st, ap, gg, n, preds[0].shape[4] - 5, 0, boxes.data_ptr(), n_per, stream), "yolo_decode3")
-                L.check(lib.yolo_tile_collect(boxes.data_ptr(), n, n_per, d_tiles.data_ptr() + 16 * s, d_hw.data_ptr(), F, th, tw,
-                                              float(obj_threshold), cand.data_ptr(), cap, tail.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              stream), "yolo_tile_collect")
+                if plain:
+                    L.check(lib.yolo_tile_collect(boxes.data_ptr(), n, n_per, d_tiles.data_ptr() + 16 * s, d_hw.data_ptr(), F, th, tw,
+                                                  float(obj_threshold), cand.data_ptr(), cap, tail.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  stream), "yolo_tile_collect")
+                else:
+                    L.check(lib.yolo_tile_collect_ex(boxes.data_ptr(), n, n_per, d_tiles.data_ptr() + 16 * s, d_lev.data_ptr(),
+                                                     len(lev) // 2, F, th, tw, float(obj_threshold),
+                                                     -1.0 if edge_margin is None else margin, cand.data_ptr(), cap,
+                                                     tail.data_ptr(), ws.data_ptr(), ws.numel(), stream), "yolo_tile_collect_ex")
         finally:
             eng._defer_nan, eng._pending_flag = False, None
         for t in frames:
