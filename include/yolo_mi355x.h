@@ -548,6 +548,49 @@ int yolo_tile_collect_ex(const float* boxes, int n_tiles, int n_per, const int32
                          int n_images, int tile_h, int tile_w, double obj_threshold, float edge_margin, float* cand, int cap,
                          int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- anchors of a dataset: IoU k-means++ with restarts, and the fitness of an anchor set (csrc/anchors.hip) ---------------- */
+/* wh: n rows (w, h) fp32 on the device, 8-byte aligned, every row with 0 < w, h <= 1 (the caller filters; the Python wrapper does).
+ * This comment is the contract: the kernels and the CPU restatement of the tests are both written from it.
+ *
+ * IoU(b, c) = inter / (bw bh + cw ch - inter), inter = min(bw, cw) min(bh, ch): fp32, every operation rounded once, no fused
+ * multiply-add. It is the expression yolo_build_targets_hw ranks the anchors of a box by, so the anchors optimise what the target
+ * builder uses.
+ *
+ * Seeding (k-means++), restart r, u = draws[r] (k doubles in [0, 1)): seed 0 is box min((int)(u[0] n), n - 1). For j = 1 .. k - 1,
+ * with best_i = max over the seeds chosen so far of IoU(b_i, seed) (fp32): d_i = (double)(1.0f - best_i), the weights are d_i d_i in
+ * fp64, T = sum of the weights, and seed j is the smallest i whose running sum of the weights (in index order) exceeds u[j] T,
+ * clamped to n - 1; if T == 0, seed j is min((int)(u[j] n), n - 1). The association of the fp64 sums is the implementation's (fixed,
+ * so a call repeats bit for bit); a draw that lands within a few ulp of T of a running-sum boundary may pick either neighbour.
+ *
+ * Lloyd step: label_i = argmax_j IoU(b_i, c_j), ties to the lowest j; the new c_j is the mean of its boxes' (w, h): sums in fp64,
+ * divided by the count, rounded once to fp32; a cluster with no box keeps its centroid. Stop when every new centroid is bit-equal
+ * to the old one (converged = 1, iterations = the steps taken, the one that changed nothing included) or after max_iter steps
+ * (converged = 0, iterations = max_iter).
+ *
+ * Fitness: the mean over the boxes of max_j IoU(b_i, c_j) against the final centroids, summed in fp64.
+ *
+ * Outputs (device): centroids [restarts][k][2] fp32 in seed order (not sorted), fitness [restarts] fp64 (8-byte aligned),
+ * iterations / converged [restarts] int32, picks [restarts][k] int32 = the box index of every seed (may be NULL). Nothing outside
+ * these extents is written and the inputs are not written.
+ * Deterministic: no floating-point atomics; every block writes its partial sums to the workspace and one block per restart adds
+ * them in ascending block order. The restarts run side by side, each with a done-flag in the workspace: max_iter steps are always
+ * enqueued on `stream`, and a restart that has converged leaves the later ones at once. The call does not wait for the device
+ * and copies nothing to the host. Every workspace byte that is read was written by the same call.
+ * Limits: 1 <= k <= 16, k <= n, 1 <= restarts <= 64, max_iter >= 1, no null pointer but picks, the alignments above: otherwise
+ * YOLO_ERR_ARG. A workspace that is NULL, not 16-byte aligned or smaller than yolo_anchor_kmeans_workspace_bytes (0 for
+ * shapes outside the limits; it does not decrease as n grows): YOLO_ERR_WORKSPACE. Both are returned before any launch. */
+size_t yolo_anchor_kmeans_workspace_bytes(int n, int k, int restarts);
+int yolo_anchor_kmeans(const float* wh, int n, int k, int restarts, const double* draws, int max_iter, float* centroids, double* fitness,
+                       int32_t* iterations, int32_t* converged, int32_t* picks, void* workspace, size_t workspace_bytes, void* stream);
+/* Any k anchors (k x 2 fp32, device) against the boxes, by the same IoU and the same first-maximum label:
+ * mean_iou_and_recall[0] = the fitness above, [1] = the share of boxes whose best IoU is > iou_threshold (fp32 comparison);
+ * counts [k] int32 = boxes won by every anchor; labels [n] int32 (may be NULL). Two launches, same rules: fixed-order fp64 sums, no
+ * waiting, workspace fully written before it is read. n >= 1, 1 <= k <= 16, a threshold that is not NaN, no null pointer but
+ * labels, wh and the result 8-byte aligned, else YOLO_ERR_ARG; workspace as above (8-byte aligned). */
+size_t yolo_anchor_fitness_workspace_bytes(int n, int k);
+int yolo_anchor_fitness(const float* wh, int n, const float* anchors, int k, float iou_threshold, double* mean_iou_and_recall,
+                        int32_t* counts, int32_t* labels, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

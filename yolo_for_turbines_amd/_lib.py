@@ -198,6 +198,12 @@ _SIGS = {
                                           C.c_void_p]),
     "yolo_tile_collect_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                        C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_anchor_kmeans_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "yolo_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_anchor_fitness_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "yolo_anchor_fitness": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -10,6 +10,7 @@ Two levels:
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -20,7 +21,7 @@ from . import _lib as L
 __all__ = ["iou_aligned", "calc_iou", "cells_to_boxes", "non_max_suppression", "decode_boxes", "nms_indices",
            "detect", "detect_tiled", "tile_grid", "tile_pyramid", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
            "augment_params", "augment_batch", "train_batch",
-           "save_checkpoint", "load_checkpoint", "scaled_anchors"]
+           "save_checkpoint", "load_checkpoint", "scaled_anchors", "anchor_draws", "kmeans_anchors", "anchor_fitness", "anchors_layout"]
 
 
 # -------------------------------------------------------------------------------- IoU
@@ -75,6 +76,134 @@ def _grid_hw(grid_size):
         gh, gw = grid_size
         return int(gh), int(gw)
     return int(grid_size), int(grid_size)
+
+
+# ------------------------------------------------------------------------------ anchors of a dataset
+AnchorResult = collections.namedtuple("AnchorResult", "anchors centroids fitness iterations converged picks best")
+AnchorFitness = collections.namedtuple("AnchorFitness", "mean_iou recall counts labels")
+ANCHOR_MAX_K, ANCHOR_MAX_RESTARTS = 16, 64
+
+
+def anchor_draws(restarts, k, generator=None):
+    """The random draws of :func:`kmeans_anchors` as a (restarts, k) float64 table in [0, 1): row r seeds restart r (k-means++, one
+    draw per seed). The same generator state gives the same table, as for :func:`augment_params`."""
+    return torch.rand((int(restarts), int(k)), generator=generator, dtype=torch.float64)
+
+
+def anchors_layout(centroids):
+    """k (w, h) pairs -> the ``config.ANCHORS`` layout: sorted ascending by fp32 area ``w * h`` (stable: equal areas keep their input
+    order), then, for k % 3 == 0, cut into three groups of k / 3 with the group of the largest anchors (the coarsest grid) first
+    and areas ascending inside each group, shape (3, k / 3, 2); any other k stays (k, 2), ascending. Pure tensor code, any device."""
+    c = torch.as_tensor(centroids, dtype=torch.float32).reshape(-1, 2)
+    s = c[torch.sort(c[:, 0] * c[:, 1], stable=True).indices]
+    k = s.shape[0]
+    return s.reshape(3, k // 3, 2).flip(0).contiguous() if k and k % 3 == 0 else s
+
+
+def _anchor_wh(boxes, image_size):
+    """(N, 2) wh | (N, >= 4) [x, y, w, h, ...] | per-image lists of [x, y, w, h, ...] rows (None / empty entries allowed) -> the valid
+    sizes as a contiguous (M, 2) fp32 tensor on the input's device: rows whose w or h is NaN, <= 0 or > 1 are dropped, the rest is
+    multiplied in fp32 by (W / L, H / L), L = max(H, W), when ``image_size = (H, W)`` is given (the factors of build_targets)."""
+    first = next((b for b in boxes if b is not None and len(b)), None) if isinstance(boxes, (list, tuple)) else None
+    if isinstance(boxes, (list, tuple)) and (any(b is None for b in boxes) or (first is not None and torch.as_tensor(first).dim() >= 2)):
+        per =[torch.as_tensor(b, dtype=torch.float32) for b in boxes if b is not None and len(b)]
+        per = [b.reshape(-1, b.shape[-1]) for b in per]
+        t = torch.cat(per) if per else torch.zeros((0, 4), dtype=torch.float32)
+    else:
+        t = torch.as_tensor(boxes, dtype=torch.float32)
+        if t.numel() == 0:
+            t = t.reshape(0, 2)
+    if t.dim() != 2 or not (t.shape[1] == 2 or t.shape[1] >= 4):
+        raise ValueError(f"boxes must be (N, 2) sizes or (N, >= 4) [x, y, w, h, ...] rows, got {tuple(t.shape)}")
+    wh = t if t.shape[1] == 2 else t[:, 2:4]
+    w, h = wh[:, 0], wh[:, 1]
+    wh = wh[(w > 0) & (w <= 1) & (h > 0) & (h <= 1)]
+    if image_size is not None:
+        H, W = _grid_hw(image_size)
+        L_ = max(H, W)
+        wh = wh * torch.tensor([W / L_, H / L_], dtype=torch.float32, device=wh.device)
+    return wh.contiguous()
+
+
+def kmeans_anchors(boxes, k=9, restarts=8, max_iter=300, image_size=None, generator=None, draws=None, device=None):
+    """The anchors of a dataset: k-means under the distance 1 - IoU(w, h) with k-means++ seeding, ``restarts`` seedings side by side
+    on the device, the best one kept (``yolo_anchor_kmeans``; the arithmetic is stated in include/yolo_mi355x.h). The IoU is the one
+    :func:`build_targets` ranks the anchors of a box by.
+
+    ``boxes``: an (N, 2) array of normalised (w, h), an (N, >= 4) array of ``[x, y, w, h, ...]`` rows, or the per-image list that
+    :func:`train_batch` takes. Rows whose w or h is NaN, <= 0 or > 1 are dropped; fewer than ``k`` left is a ``ValueError``.
+    ``image_size=(H, W)``: the sizes are first multiplied in fp32 by (W / L, H / L), L = max(H, W), as :func:`build_targets` does on
+    that canvas, so the anchors come out L-normalised and go straight into ``scaled_anchors(anchors, H, W)``. ``draws``: the
+    (restarts, k) table of :func:`anchor_draws` (drawn from ``generator`` when omitted). 1 <= k <= 16, 1 <= restarts <= 64.
+
+    Returns an ``AnchorResult`` of CPU tensors, read back in one copy (the only host synchronisation, apart from the row filter
+    when ``boxes`` is itself a device tensor): ``anchors`` - the centroids of the best restart in the ``config.ANCHORS`` layout
+    (:func:`anchors_layout`); ``centroids`` (R, k, 2) fp32 in seed order; ``fitness`` (R,) fp64, the mean over the boxes of the best
+    IoU; ``iterations`` / ``converged`` (R,) int32 (``max_iter`` Lloyd steps are enqueued, a converged restart leaves them at
+    once); ``picks`` (R, k) int32, the rows (of the filtered boxes) taken as seeds; ``best``, the restart with the highest
+    fitness, ties to the lowest index."""
+    k, R, max_iter = int(k), int(restarts), int(max_iter)
+    if not (1 <= k <= ANCHOR_MAX_K and 1 <= R <= ANCHOR_MAX_RESTARTS and max_iter >= 1):
+        raise ValueError(f"need 1 <= k <= {ANCHOR_MAX_K}, 1 <= restarts <= {ANCHOR_MAX_RESTARTS}, max_iter >= 1; got {k}, {R}, {max_iter}")
+    wh = _anchor_wh(boxes, image_size)
+    n = int(wh.shape[0])
+    if n < k:
+        raise ValueError(f"{n} valid boxes (0 < w, h <= 1) are fewer than k = {k}")
+    if draws is None:
+        draws = anchor_draws(R, k, generator)
+    draws = torch.as_tensor(draws, dtype=torch.float64)
+    if tuple(draws.shape) != (R, k) or not bool(((draws >= 0) & (draws < 1)).all()):
+        raise ValueError(f"draws must be a ({R}, {k}) table of numbers in [0, 1)")
+    dev = torch.device(device) if device is not None else (wh.device if wh.is_cuda else torch.device("cuda"))
+    if dev.type != "cuda":
+        raise RuntimeError("kmeans_anchors runs on MI355X only (no CPU fallback)")
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        wh, dd = wh.to(dev), draws.to(dev).contiguous()
+        # one buffer for every result, 8-byte sections: fitness f64 [R] | centroids f32 [R k 2] | iterations, converged i32 [R] each | picks i32 [R k]
+        out = torch.empty(16 * R + 12 * R * k, dtype=torch.uint8, device=dev)
+        fit, cen, itc, pk = out[:8 * R], out[8 * R:8 * R + 8 * R * k], out[8 * R + 8 * R * k:16 * R + 8 * R * k], out[16 * R + 8 * R * k:]
+        ws = torch.empty(int(lib.yolo_anchor_kmeans_workspace_bytes(n, k, R)), dtype=torch.uint8, device=dev)
+        L.check(lib.yolo_anchor_kmeans(wh.data_ptr(), n, k, R, dd.data_ptr(), max_iter, cen.data_ptr(), fit.data_ptr(), itc.data_ptr(),
+                                       itc.data_ptr() + 4 * R, pk.data_ptr(), ws.data_ptr(), ws.numel(), L.current_stream()),
+                "yolo_anchor_kmeans")
+        host = out.cpu()                                            # the one read-back
+    fitness = host[:8 * R].view(torch.float64).clone()
+    centroids = host[8 * R:8 * R + 8 * R * k].view(torch.float32).reshape(R, k, 2).clone()
+    ic = host[8 * R + 8 * R * k:16 * R + 8 * R * k].view(torch.int32).clone()
+    picks = host[16 * R + 8 * R * k:16 * R + 12 * R * k].view(torch.int32).reshape(R, k).clone()
+    fl = fitness.tolist()
+    best = max(range(R), key=lambda r: (fl[r], -r))
+    return AnchorResult(anchors_layout(centroids[best]), centroids, fitness, ic[:R], ic[R:], picks, best)
+
+
+def anchor_fitness(boxes, anchors, iou_threshold=0.5, image_size=None):
+    """How well any anchors fit a set of boxes (``yolo_anchor_fitness``), for instance the COCO anchors on the tiles of a new dataset.
+    ``boxes`` and ``image_size`` as for :func:`kmeans_anchors` (same filter, same factors); ``anchors``: up to 16 (w, h) pairs in
+    any shape, normalised as the boxes are after ``image_size``. Returns an ``AnchorFitness``: ``mean_iou``, the mean over the
+    boxes of the best IoU (the fitness of :func:`kmeans_anchors`), ``recall``, the share of boxes whose best IoU is
+    ``> iou_threshold`` (both Python floats), ``counts`` (k,) int32, the boxes every anchor wins (the first maximum), and ``labels``
+    (N,) int32, the winning anchor per valid box, in the flattened order of ``anchors``; CPU tensors, one read-back."""
+    wh = _anchor_wh(boxes, image_size)
+    n = int(wh.shape[0])
+    if n < 1:
+        raise ValueError("no valid box (0 < w, h <= 1)")
+    anc = torch.as_tensor(anchors, dtype=torch.float32).reshape(-1, 2)
+    k = int(anc.shape[0])
+    if not 1 <= k <= ANCHOR_MAX_K:
+        raise ValueError(f"need 1 <= k <= {ANCHOR_MAX_K} anchors, got {k}")
+    dev = wh.device if wh.is_cuda else torch.device("cuda")
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        wh, anc = wh.to(dev), anc.to(dev).contiguous()
+        out = torch.empty(16 + 4 * k + 4 * n, dtype=torch.uint8, device=dev)          # mean, recall f64 | counts i32 [k] | labels i32 [n]
+        ws = torch.empty(int(lib.yolo_anchor_fitness_workspace_bytes(n, k)), dtype=torch.uint8, device=dev)
+        L.check(lib.yolo_anchor_fitness(wh.data_ptr(), n, anc.data_ptr(), k, float(iou_threshold), out.data_ptr(), out.data_ptr() + 16,
+                                        out.data_ptr() + 16 + 4 * k, ws.data_ptr(), ws.numel(), L.current_stream()), "yolo_anchor_fitness")
+        host = out.cpu()
+    mr = host[:16].view(torch.float64).tolist()
+    ints = host[16:].view(torch.int32).clone()
+    return AnchorFitness(mr[0], mr[1], ints[:k], ints[k:])
 
 
 # ------------------------------------------------------------------------------ decode
