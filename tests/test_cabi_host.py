@@ -195,7 +195,7 @@ def test_checkpoint_format_matches_reference(golden, tmp_path):
 
 # ---- the A/B environment switches: one row per switch, in the order yolo_switches_describe prints them
 PRESENCE_SWITCHES = ("YOLO_NO_DMA", "YOLO_NO_S2_DMA", "YOLO_NO_S2G", "YOLO_NO_STAGGER", "YOLO_NO_WINOGRAD", "YOLO_NO_CONV3_WS",
-                     "YOLO_NO_CONV1_RS", "YOLO_NO_WGRAD_DMA", "YOLO_NO_STEM_WGRAD", "YOLO_STEM_VALU", "YOLO_NMS_ROCPRIM")
+                     "YOLO_NO_CONV1_RS", "YOLO_NO_WGRAD_DMA", "YOLO_NO_STEM_WGRAD", "YOLO_STEM_VALU")
 PRIO_SWITCHES = ("YOLO_F32_PRIO", "YOLO_DMA_PRIO")
 INT_SWITCHES = {"YOLO_WGRAD_LA": 3, "YOLO_WGRAD_PRIO": 0, "YOLO_STEM_WGRAD_BLOCKS": 256, "YOLO_WINO2_MAXPIX": 256}
 ALL_SWITCHES = PRESENCE_SWITCHES + PRIO_SWITCHES + tuple(INT_SWITCHES)

@@ -402,8 +402,9 @@ def test_nms_candidate_bounds_pairs_at_the_threshold(yt, thr, scale):
 def test_nms_ordering_kernels_chunk_counts(yt, n, nc):
     """The hand-written ordering (2,048-key chunks sorted in LDS + rank merge) for 1 .. 33 chunks per image, chunk
     boundaries exactly at n, the largest grid of a forward (22,743 boxes at 608x608) and sizes that need several ranking
-    rounds of 15 chunks (> 32,768 boxes: the library sort until round 3): kept indices bit-exact against the C oracle, images
-    with different numbers of candidates (none, all, ties in the scores)."""
+    rounds of 15 chunks (> 32,768 boxes; the class-sorted path and with it this ordering end at 163,456, which
+    test_nms_routing_edge covers): kept indices bit-exact against the C oracle, images with different numbers of candidates
+    (none, all, ties in the scores)."""
     rng = np.random.Generator(np.random.PCG64(n + nc))
     imgs = [gi.boxes_uniform(n, nc, 4000 + n), gi.boxes_clustered(n, nc, 4001 + n, jitter=0.15), gi.boxes_uniform(n, nc, 4002 + n)]
     imgs[1][:, 4] = 0.5 + 0.5 * rng.random(n).astype(F32)          # every box is a candidate
@@ -416,6 +417,43 @@ def test_nms_ordering_kernels_chunk_counts(yt, n, nc):
         want = opp.nms_indices_c(batch[b], 0.45, 0.5, "center")
         assert int(count[b]) == len(want)
         np.testing.assert_array_equal(keep[b, :int(count[b])].cpu().numpy(), want)
+
+
+# The class-sorted path needs one removed[] array of W = ceil(n / 64) words per wave beside the scan's fixed 16 W + 128 bytes
+# in 60 KiB of LDS (nms_host.hip): K = (61,440 - 16 W - 128) / (8 W) >= 1 <=> 24 W + 128 <= 61,440 <=> W <= 2,554 <=> n <= 163,456.
+NMS_LAST_CLASS_SORTED_N = ((60 * 1024 - 128) // 24) * 64
+
+
+@pytest.mark.parametrize("n", [NMS_LAST_CLASS_SORTED_N, NMS_LAST_CLASS_SORTED_N + 1])
+def test_nms_routing_edge(yt, n):
+    """The two sizes either side of the cut between the class-sorted and the score-only path: n = 163,456 (W = 2,554, one
+    wave per image in the class scan, 80 chunks, so the rank merges run six rounds of 15 chunks) and n = 163,457 (one
+    library sort, then the plain mask and scan at W = 2,555). One image, about 2 % candidates, a block of tied scores:
+    kept indices and count exactly the C oracle's. The workspace is the test's own (3.4 GB, freed at the end)."""
+    from yolo_for_turbines_amd import _lib as L
+    assert n in (163456, 163457)
+    rng = np.random.Generator(np.random.PCG64(n))
+    boxes = gi.boxes_uniform(n, 80, 5000 + n)
+    boxes[:, 4] = rng.random(n).astype(F32)
+    boxes[::100, 4] = 0.99                                         # equal scores: index order decides
+    obj_thr = 0.98
+    candidates = int(np.count_nonzero(boxes[:, 4].astype(np.float64) > obj_thr))
+    assert 2000 <= candidates <= 6000
+    want = opp.nms_indices_c(boxes, 0.45, obj_thr, "center")
+    t = torch.from_numpy(boxes).cuda().unsqueeze(0).contiguous()
+    keep = torch.empty((1, n), dtype=torch.int32, device="cuda")
+    count = torch.empty((1,), dtype=torch.int32, device="cuda")
+    lib = L.lib()
+    ws = torch.empty(lib.yolo_nms_workspace_bytes(1, n), dtype=torch.uint8, device="cuda")
+    try:
+        L.check(lib.yolo_nms(t.data_ptr(), 1, n, 0.45, obj_thr, 1, keep.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                             L.current_stream()), "yolo_nms")
+        got = keep[0, :int(count[0])].cpu().numpy()
+    finally:
+        del ws
+        torch.cuda.empty_cache()
+    assert int(count[0]) == len(want)
+    np.testing.assert_array_equal(got, want)
 
 
 def test_detect_pipeline_vs_oracle(yt):

@@ -10,7 +10,7 @@
 // Ordering (two stable sorts of 64-bit keys) is done by the caller; this file does the sequential-per-class matching
 // (one wave per class: lanes evaluate the IoUs of one detection in parallel, a wave-wide first-argmax picks the
 // ground truth) and the AP integration. IoU is calc_iou's arithmetic (utils.py:38-84), fp32, no FMA contraction
-// (this file is built with -ffp-contract=off like postprocess.hip).
+// (this file is built with -ffp-contract=off like the post-processing units).
 #include "common.h"
 
 namespace yolo {

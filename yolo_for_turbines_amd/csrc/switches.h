@@ -17,7 +17,6 @@ struct Switches {
     bool no_wgrad_dma;              // YOLO_NO_WGRAD_DMA    16-bit 3x3 stride-1 weight gradient: wgrad_h16 instead of wgrad3_dma_h16
     bool no_stem_wgrad;             // YOLO_NO_STEM_WGRAD   16-bit weight gradient of the first block: not wgrad_stem_h16
     bool stem_valu;                 // YOLO_STEM_VALU       16-bit first block: the vector kernel instead of stem_h16
-    bool nms_rocprim;               // YOLO_NMS_ROCPRIM     NMS: the library sorts instead of the chunk sort + rank merge
     // on by default, off only when the value's first character is '0'
     bool f32_prio;                  // YOLO_F32_PRIO        conv_f32_v2: prologue / epilogue at raised wave priority
     bool dma_prio;                  // YOLO_DMA_PRIO        conv3_dma_h16 / conv1_dma_h16: the same

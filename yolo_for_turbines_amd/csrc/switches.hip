@@ -20,7 +20,6 @@ namespace yolo {
     X(no_wgrad_dma,      "YOLO_NO_WGRAD_DMA",      Set,     0)     \
     X(no_stem_wgrad,     "YOLO_NO_STEM_WGRAD",     Set,     0)     \
     X(stem_valu,         "YOLO_STEM_VALU",         Set,     0)     \
-    X(nms_rocprim,       "YOLO_NMS_ROCPRIM",       Set,     0)     \
     X(f32_prio,          "YOLO_F32_PRIO",          NotZero, 1)     \
     X(dma_prio,          "YOLO_DMA_PRIO",          NotZero, 1)     \
     X(wgrad_la,          "YOLO_WGRAD_LA",          Int,     3)     \

@@ -102,7 +102,7 @@ __device__ __forceinline__ bool tile_cut(const float* __restrict__ row, const Ti
            (g.y0 > 0 && top < edge_margin) || ((long long)g.y0 + tile_h < g.H && bottom > (float)tile_h - edge_margin);
 }
 
-// A row is a candidate iff make_key of postprocess.hip would rank it ((double) obj > threshold: NaN and equality are out)
+// A row is a candidate iff make_key of nms.h would rank it ((double) obj > threshold: NaN and equality are out)
 // and its centre, remapped to the frame, is not in the zero padding of a tile that hangs over the edge.
 // EX: and no interior side of its tile has cut it (tile_cut). tile_count and tile_write both decide here, nowhere else.
 template <bool EX>
