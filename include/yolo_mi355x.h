@@ -390,6 +390,31 @@ int yolo_map_match(const float* dets_sorted, const int32_t* det_class_offsets, c
                    int num_classes, int n_gt, float iou_threshold, int center, int32_t* assigned, float* tp_flags, float* ap_per_class,
                    void* stream);
 
+/* The same matching at 1 .. 16 IoU thresholds in one pass (mAP@[.5:.95]), with the counts for precision / recall at a confidence
+ * threshold. dets_sorted [n_det] / gts_sorted [n_gt] and the class offsets as for yolo_map_match. iou_thresholds: n_thr floats ON THE
+ * HOST, each in [0, 1), any order, repeats allowed; every comparison with them is fp32.
+ *
+ * Per detection d (a row of dets_sorted): best_iou[d] = the first maximum IoU over the ground truths of its image and class in
+ * list order under a strict `>` against a running best that starts at 0 (yolo_map_match's choice, which does not depend on the
+ * threshold), best_gt[d] = that row of gts_sorted, or 0 and -1 when there is none. At threshold t, d is a true positive iff
+ * best_iou[d] > t and d is the lowest row among the detections d' with best_gt[d'] == best_gt[d] and best_iou[d'] > t: exactly the
+ * detections the sequential walk of yolo_map_match marks (the first one that reaches a ground truth with a passing IoU assigns it).
+ *
+ * Outputs (device): best_iou [n_det] fp32, best_gt [n_det] int32, tp [n_thr][n_det] bytes (1 = true positive), ap [n_thr][nc] fp32 =
+ * yolo_map_match's ap_per_class at that threshold, bit for bit (-1 for a class without ground truth, 0 for one with ground truth
+ * and no detection), tp_at_conf [n_thr][nc] int32 = the true positives among the detections with objectness > conf_threshold
+ * (strict, fp32), n_det_at_conf [nc] int32 = those detections. Integer atomics only, so a call repeats bit for bit. A memset and
+ * three launches (one launch for n_det == 0, which is legal, as is n_gt == 0); nothing is copied to the host and the call does not
+ * wait. Limits: n_det, n_gt >= 0, num_classes >= 1, 1 <= n_thr <= 16, thresholds in [0, 1), conf_threshold not NaN, center 0 or 1,
+ * no null pointer (dets_sorted / best_iou / best_gt / tp may be NULL for n_det == 0, gts_sorted for n_gt == 0): otherwise
+ * YOLO_ERR_ARG. A workspace that is NULL, not 4-byte aligned or smaller than yolo_eval_workspace_bytes (0 for shapes outside the
+ * limits): YOLO_ERR_WORKSPACE. Both are returned before any launch. */
+size_t yolo_eval_workspace_bytes(int n_det, int n_gt, int n_thr);
+int yolo_eval_detections(const float* dets_sorted, const int32_t* det_class_offsets, int n_det, const float* gts_sorted,
+                         const int32_t* gt_class_offsets, int n_gt, int num_classes, const float* iou_thresholds, int n_thr,
+                         float conf_threshold, int center, float* best_iou, int32_t* best_gt, unsigned char* tp, float* ap,
+                         int32_t* tp_at_conf, int32_t* n_det_at_conf, void* workspace, size_t workspace_bytes, void* stream);
+
 /* check_model_accuracy (utils.py:334-381) for one scale of one batch: counts5 += [class correct, n_obj, objectness correct
  * on object cells, objectness correct on no-object cells, n_noobj]; pred / target as for yolo_loss_fwd. */
 int yolo_accuracy_counts(const float* pred, const int64_t* strides5, const float* target, int b, int g, int nc, float obj_threshold,

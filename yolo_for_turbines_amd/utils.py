@@ -19,7 +19,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["iou_aligned", "calc_iou", "cells_to_boxes", "non_max_suppression", "decode_boxes", "nms_indices",
-           "detect", "detect_tiled", "tile_grid", "tile_pyramid", "build_targets", "calc_mAP", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
+           "detect", "detect_tiled", "tile_grid", "tile_pyramid", "build_targets", "calc_mAP", "evaluate_detections", "evaluate_model", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes",
            "augment_params", "augment_batch", "train_batch",
            "save_checkpoint", "load_checkpoint", "scaled_anchors", "anchor_draws", "kmeans_anchors", "anchor_fitness", "anchors_layout"]
 
@@ -684,6 +684,103 @@ def calc_mAP(pred_boxes, true_boxes, iou_threshold=0.5, box_format="center", num
     if not bool(valid.any()):
         raise ZeroDivisionError("division by zero")        # the reference divides by len([]) here
     return ap[valid].sum() / int(valid.sum())
+
+
+# ------------------------------------------------------------------------------ evaluation at several thresholds
+EvalResult = collections.namedtuple("EvalResult", "ap has_gt map map_50_95 n_gt n_det n_det_at_conf tp_at_conf precision recall f1")
+EvalMatches = collections.namedtuple("EvalMatches", "order tp best_iou best_gt")
+EVAL_MAX_THRESHOLDS = 16
+
+
+def evaluate_detections(pred_boxes, true_boxes, num_classes, iou_thresholds=None, conf_threshold=0.5, box_format="center",
+                        return_matches=False):
+    """The evaluation of a detector in one pass (``yolo_eval_detections``): :func:`calc_mAP` at every IoU threshold of
+    ``iou_thresholds`` (default 0.50, 0.55 .. 0.95, i.e. mAP@[.5:.95]; 1 to 16 values in [0, 1), any order), the AP of every class,
+    and precision / recall / F1 of every class at the objectness threshold ``conf_threshold`` (strict ``>``, as the object filter of
+    :func:`non_max_suppression`). Rows ``[image_id, cx, cy, w, h, obj, class]`` as lists or tensors, as for :func:`calc_mAP`; rows
+    whose class is not in ``range(num_classes)`` are dropped. One upload, one sort per list, one call, one read-back.
+
+    Returns an ``EvalResult`` of CPU tensors, T thresholds x nc classes: ``ap`` (T, nc) fp32, NaN where the class has no ground
+    truth; ``has_gt`` (nc,) bool; ``map`` (T,) fp32, ``map[t]`` bit-equal to ``calc_mAP(..., iou_thresholds[t], ...)``;
+    ``map_50_95`` = ``map.mean()``; ``n_gt`` / ``n_det`` / ``n_det_at_conf`` (nc,) int64: ground truths, detections, detections
+    above ``conf_threshold``; ``tp_at_conf`` (T, nc) int64, the true positives among the latter; ``precision`` = tp / n_det_at_conf
+    (0 without such a detection), ``recall`` = tp / n_gt (NaN without ground truth), ``f1`` = 2 p r / (p + r) (0 when p + r = 0),
+    (T, nc) fp64. No class with ground truth: ``ZeroDivisionError``, as :func:`calc_mAP`.
+
+    ``return_matches=True`` returns ``(result, EvalMatches)`` with device tensors for precision / recall curves and threshold
+    picking: ``order`` (D,) int64, the row of ``pred_boxes`` behind each kept detection in (class ascending, objectness descending,
+    stable) order; ``tp`` (T, D) bool; ``best_iou`` (D,) fp32 and ``best_gt`` (D,) int64, the ground truth every detection is
+    compared with (its first maximum IoU > 0 among the ground truths of its image and class) as a row of ``true_boxes``, -1 for none."""
+    thr = [0.5 + 0.05 * i for i in range(10)] if iou_thresholds is None else [float(v) for v in iou_thresholds]
+    T = len(thr)
+    if not 1 <= T <= EVAL_MAX_THRESHOLDS or not all(0.0 <= v < 1.0 for v in thr):
+        raise ValueError(f"iou_thresholds: 1 to {EVAL_MAX_THRESHOLDS} numbers in [0, 1), got {thr}")
+    conf = float(conf_threshold)
+    if math.isnan(conf):
+        raise ValueError("conf_threshold must be a number")
+    dev = torch.device("cuda")
+    dets = torch.as_tensor(pred_boxes, dtype=torch.float32).reshape(-1, 7).to(dev)
+    gts = torch.as_tensor(true_boxes, dtype=torch.float32).reshape(-1, 7).to(dev)
+    nc = int(num_classes)
+
+    def ordered(t, minor, descending):                     # calc_mAP's class filter and stable order; rows[i] = the input row of t[i]
+        c = t[:, 6]
+        rows = torch.nonzero((c >= 0) & (c < nc) & (c == torch.floor(c))).reshape(-1)
+        t = t[rows]
+        o = _stable_order(t[:, 6], t[:, minor], descending_minor=descending)
+        return t[o].contiguous(), rows[o]
+    dets, det_rows = ordered(dets, 5, True)
+    gts, gt_rows = ordered(gts, 0, False)
+
+    def offsets(t):
+        cnt = torch.bincount(t[:, 6].long(), minlength=nc)[:nc]
+        return torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(cnt, 0)]).to(torch.int32).contiguous()
+    d_off, g_off = offsets(dets), offsets(gts)
+    D, G = int(dets.shape[0]), int(gts.shape[0])
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        best_iou = torch.empty(D, dtype=torch.float32, device=dev)
+        best_gt = torch.empty(D, dtype=torch.int32, device=dev)
+        tp = torch.empty((T, D), dtype=torch.uint8, device=dev)
+        out = torch.empty(2 * T * nc + nc, dtype=torch.int32, device=dev)         # ap f32 [T nc] | tp_at_conf [T nc] | n_det_at_conf [nc]
+        ws = torch.empty(int(lib.yolo_eval_workspace_bytes(D, G, T)), dtype=torch.uint8, device=dev)
+        L.check(lib.yolo_eval_detections(dets.data_ptr(), d_off.data_ptr(), D, gts.data_ptr(), g_off.data_ptr(), G, nc, (C.c_float * T)(*thr), T,
+                                         conf, 1 if box_format == "center" else 0, best_iou.data_ptr(), best_gt.data_ptr(), tp.data_ptr(),
+                                         out.data_ptr(), out.data_ptr() + 4 * T * nc, out.data_ptr() + 8 * T * nc, ws.data_ptr(), ws.numel(),
+                                         L.current_stream()), "yolo_eval_detections")
+        host = torch.cat([out, d_off, g_off]).cpu()                                # the one read-back
+    ap = host[:T * nc].view(torch.float32).reshape(T, nc).clone()
+    tp_at_conf = host[T * nc:2 * T * nc].reshape(T, nc).to(torch.int64)
+    n_det_at_conf = host[2 * T * nc:2 * T * nc + nc].to(torch.int64)
+    offs = host[2 * T * nc + nc:].to(torch.int64)
+    n_det, n_gt = offs[1:nc + 1] - offs[:nc], offs[nc + 2:] - offs[nc + 1:-1]
+    has_gt = n_gt > 0
+    if not bool(has_gt.any()):
+        raise ZeroDivisionError("division by zero")        # as calc_mAP
+    mp = torch.stack([ap[t][ap[t] >= 0].sum() / int((ap[t] >= 0).sum()) for t in range(T)])      # calc_mAP's fp32 host arithmetic
+    ap[:, ~has_gt] = math.nan
+    tpd, nd = tp_at_conf.double(), n_det_at_conf.double()
+    precision = torch.where(nd > 0, tpd / nd.clamp(min=1), torch.zeros((), dtype=torch.float64)).expand(T, nc).clone()
+    recall = torch.where(has_gt, tpd / n_gt.double().clamp(min=1), torch.full((), math.nan, dtype=torch.float64)).expand(T, nc).clone()
+    pr = precision + recall
+    f1 = torch.where(pr == 0, torch.zeros((), dtype=torch.float64), 2 * precision * recall / torch.where(pr == 0, torch.ones_like(pr), pr))
+    res = EvalResult(ap, has_gt, mp, mp.mean(), n_gt, n_det, n_det_at_conf, tp_at_conf, precision, recall, f1)
+    if not return_matches:
+        return res
+    bg = best_gt.long()
+    bg = torch.where(bg >= 0, gt_rows[bg.clamp(min=0)], bg) if G else bg
+    return res, EvalMatches(det_rows, tp.bool(), best_iou, bg)
+
+
+def evaluate_model(loader, model, anchors, iou_threshold=0.45, obj_threshold=0.5, **kw):
+    """:func:`eval_boxes` (forward, decode, NMS at ``iou_threshold`` / ``obj_threshold``) and :func:`evaluate_detections` of its two
+    tensors, which never leave the device in between. ``kw`` goes to :func:`evaluate_detections`; ``num_classes`` defaults to
+    ``model.num_classes``, ``box_format`` is shared by both."""
+    kw = dict(kw)
+    nc = kw.pop("num_classes", None)
+    nc = model.num_classes if nc is None else nc
+    pred, true = eval_boxes(loader, model, iou_threshold, anchors, obj_threshold, kw.get("box_format", "center"))
+    return evaluate_detections(pred, true, nc, **kw)
 
 
 # ------------------------------------------------------------------------------ accuracy
