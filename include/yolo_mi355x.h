@@ -470,6 +470,26 @@ int yolo_sgd_check_finite(const void* items_dev, const int32_t* chunks_dev, int 
 int yolo_sgd_step_amp(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
                       const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, int nesterov, int maximize,
                       void* stream);
+/* Weight average (an exponential moving average of every parameter and BatchNorm statistic), fp32, bit for bit
+ * e.mul_(d).add_(p, alpha = 1 - d) of PyTorch on the GPU:
+ *   d = warmup ? min(decay, float(1 + updates) / float(10 + updates)) : decay;   e = fma(1 - d, p, e * d)
+ * The yolo_ema_state lives in device memory, 16-byte aligned, and is read when a kernel runs, never passed by value: a launch captured in a HIP
+ * graph follows the warm-up of the decay through its replays.
+ * yolo_sgd_step_hp_ema / yolo_sgd_step_amp_ema: the steps above with the average of every item that has a gradient moved in
+ * the same launch, towards the NEW parameter value. shadows_dev: n_items x float*, the average of each item's parameter
+ * (NULL entry: plain update). Neither advances `updates`: the caller finishes the update with yolo_ema_update.
+ * yolo_ema_update: one launch over n_chunks chunks of a table of yolo_ema_item rows (chunks as for the step); n > 0: n floats
+ * are averaged, n < 0: -n 32-bit words are copied (integer entries). advance != 0: a one-thread launch then adds 1 to
+ * `updates`. found_inf_dev (may be NULL) != 0: nothing is written and nothing is counted, like the skipped step. */
+typedef struct yolo_ema_state { int32_t updates; float decay; int32_t warmup; int32_t reserved; } yolo_ema_state;
+typedef struct yolo_ema_item { const void* src; void* dst; long long n; } yolo_ema_item;
+int yolo_sgd_step_hp_ema(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, const void* shadows_dev,
+                         const void* ema_state_dev, int nesterov, int maximize, void* stream);
+int yolo_sgd_step_amp_ema(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                          const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, const void* shadows_dev,
+                          const void* ema_state_dev, int nesterov, int maximize, void* stream);
+int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chunks, void* ema_state_dev, const float* found_inf_dev,
+                    int advance, void* stream);
 
 /* ---- post-processing ------------------------------------------------------------------- */
 /* Replaces cells_to_boxes (utils.py:86-148) for one scale.

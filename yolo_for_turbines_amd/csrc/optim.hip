@@ -18,6 +18,17 @@
 // gradient once and raises a device word; `sgd_step_amp_kernel` reads that word and the scale, returns untouched when the
 // word is set, and otherwise unscales in registers (g * inv_scale, rounded on its own like the separate unscale pass of
 // `_amp_foreach_non_finite_check_and_unscale_`) in front of the chain above. The gradient is not written back.
+//
+// Weight average (EMA of every parameter and BatchNorm statistic; `ema.py`). The step holds the new parameter value in a
+// register when it stores it, so the `*_ema` variants of the two step kernels move the average in the same launch: one more
+// read and one more write per element, 28 bytes where the plain step moves 20. What the optimizer does not own (running
+// statistics, parameters without a gradient, the integer counters) goes through `ema_update_kernel`, one launch over a table
+// of (src, dst, n) rows. The arithmetic, with t = the number of updates applied so far (a device word, read when the
+// kernel runs, so a captured launch follows the warm-up through its replays):
+//   d   = warmup ? min(decay, float(1 + t) / float(10 + t)) : decay        a correctly rounded fp32 division
+//   e   = fma(1 - d, p, e * d)                                             e.mul_(d).add_(p, alpha=1 - d)
+// t is advanced by a one-thread launch AFTER every entry has been updated (a later block must still see the old t), and -
+// like everything else - left alone when *found_inf is set: the average counts applied steps.
 #include "common.h"
 
 namespace yolo {
@@ -29,10 +40,32 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SGD_CHUNK = 4096;          // elements per block: 256 threads x 4 x float4
 
-template <bool VEC>
+struct EmaState { int updates; float decay; int warmup; int reserved; };
+static_assert(sizeof(EmaState) == 16, "matches yolo_ema_state in the header");
+struct EmaItem { const void* src; void* dst; long long n; };             // n < 0: copy -n 32-bit words (integer entries)
+static_assert(sizeof(EmaItem) == 24, "matches yolo_ema_item in the header");
+
+// {d, 1 - d} of this update, from the state as it is when the block runs
+__device__ __forceinline__ void ema_coeffs(const EmaState* __restrict__ st, float& d, float& omd) {
+    const u32x4 s = *reinterpret_cast<const u32x4*>(st);
+    const int t = (int)s[0];
+    d = __uint_as_float(s[1]);
+    if (s[2] != 0) {
+        const float q = (float)(1 + t) / (float)(10 + t);
+        if (q < d) d = q;
+    }
+    omd = 1.0f - d;
+}
+
+// e * d is an argument of the fused multiply-add, not a candidate for contraction: it is rounded on its own, like mul_
+__device__ __forceinline__ float ema_one(float e, float p, float d, float omd) { return __builtin_fmaf(omd, p, e * d); }
+
+// EMA: ema (the shadow of p) moves towards the NEW p with the coefficients {ema_d, ema_omd}
+template <bool VEC, bool EMA = false>
 __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ b, long long i0,
                                            int cnt, bool first, float neg_lr, float momentum, float omd, float wd, int nesterov,
-                                           int maximize, float inv_scale = 1.0f) {
+                                           int maximize, float inv_scale = 1.0f, float* __restrict__ ema = nullptr, float ema_d = 0.f,
+                                           float ema_omd = 0.f) {
     auto one = [&](float pv, float gv, float bv, float& pn, float& bn) {
         if (inv_scale != 1.0f) {                         // the unscale pass: a rounding of its own, never fused into what follows
 #pragma clang fp contract(off)
@@ -57,12 +90,19 @@ __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* _
         for (int e = 0; e < 4; ++e) { float a, c; one(pv[e], gv[e], bv[e], a, c); pn[e] = a; bn[e] = c; }
         *reinterpret_cast<f32x4*>(p + i0) = pn;
         if (momentum != 0.f) *reinterpret_cast<f32x4*>(b + i0) = bn;
+        if (EMA) {
+            f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ev[e] = ema_one(ev[e], pn[e], ema_d, ema_omd);
+            *reinterpret_cast<f32x4*>(ema + i0) = ev;
+        }
     } else {
         for (int e = 0; e < cnt; ++e) {
             float pn, bn;
             one(p[i0 + e], g[i0 + e], (momentum != 0.f && !first) ? b[i0 + e] : 0.f, pn, bn);
             p[i0 + e] = pn;
             if (momentum != 0.f) b[i0 + e] = bn;
+            if (EMA) ema[i0 + e] = ema_one(ema[i0 + e], pn, ema_d, ema_omd);
         }
     }
 }
@@ -175,6 +215,87 @@ __global__ __launch_bounds__(256) void sgd_mark_written_kernel(const SgdItem* __
     if (items[i].g != nullptr) written[i] = 1;
 }
 
+// The two steps above with the weight average moved in the same launch. AMP: the loss-scaled form (found_inf, grad_scale and
+// written as in sgd_step_amp_kernel); otherwise the form of sgd_step_kernel with the hyper-parameters in device memory.
+// shadows[item]: the average of that item's parameter (NULL: this parameter has none, plain update). An item without a
+// gradient is skipped here like everywhere; its average is the caller's business (ema_update_kernel).
+template <bool AMP>
+__global__ __launch_bounds__(256) void sgd_step_ema_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
+                                                           const float* __restrict__ hyper, const float* __restrict__ grad_scale,
+                                                           const float* __restrict__ found_inf, const int* __restrict__ written,
+                                                           float* const* __restrict__ shadows, const EmaState* __restrict__ state,
+                                                           int nesterov, int maximize) {
+    if (AMP && *found_inf != 0.f) return;
+    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
+    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
+    const float inv_scale = (AMP && grad_scale != nullptr) ? (float)(1.0 / (double)*grad_scale) : 1.0f;
+    const int2 ck = chunks[blockIdx.x];
+    const SgdItem it = items[ck.x];
+    if (it.g == nullptr) return;
+    const bool first = AMP ? written[ck.x] == 0 : it.n < 0;
+    const long long n = it.n < 0 ? -it.n : it.n;
+    float* const ema = shadows[ck.x];
+    float d, e_omd;
+    ema_coeffs(state, d, e_omd);
+    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)ema)) & 15) == 0;
+#pragma unroll
+    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
+        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
+        if (i0 >= n) break;
+        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+        const bool vec = aligned && cnt == 4;
+        if (ema != nullptr) {
+            if (vec) sgd_update<true, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd);
+            else sgd_update<false, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd);
+        } else {
+            if (vec) sgd_update<true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
+            else sgd_update<false>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
+        }
+    }
+}
+
+// The average on its own: chunks[c] = (row, first element) as for the step. found_inf may be NULL (no loss scale).
+__global__ __launch_bounds__(256) void ema_update_kernel(const EmaItem* __restrict__ items, const int2* __restrict__ chunks,
+                                                         const EmaState* __restrict__ state, const float* __restrict__ found_inf) {
+    if (found_inf != nullptr && *found_inf != 0.f) return;
+    const int2 ck = chunks[blockIdx.x];
+    const EmaItem it = items[ck.x];
+    if (it.n < 0) {                                      // integer entry: copied word by word (a handful of words in all)
+        const unsigned* __restrict__ src = reinterpret_cast<const unsigned*>(it.src);
+        unsigned* __restrict__ dst = reinterpret_cast<unsigned*>(it.dst);
+        const long long n = -it.n;
+        for (long long i = (long long)ck.y + threadIdx.x; i < n && i < (long long)ck.y + SGD_CHUNK; i += 256) dst[i] = src[i];
+        return;
+    }
+    const float* __restrict__ p = reinterpret_cast<const float*>(it.src);
+    float* __restrict__ e = reinterpret_cast<float*>(it.dst);
+    const long long n = it.n;
+    float d, omd;
+    ema_coeffs(state, d, omd);
+    const bool aligned = ((((size_t)p) | ((size_t)e)) & 15) == 0;
+#pragma unroll
+    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
+        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
+        if (i0 >= n) break;
+        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+        if (aligned && cnt == 4) {
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
+            f32x4 ev = *reinterpret_cast<const f32x4*>(e + i0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ev[k] = ema_one(ev[k], pv[k], d, omd);
+            *reinterpret_cast<f32x4*>(e + i0) = ev;
+        } else {
+            for (int k = 0; k < cnt; ++k) e[i0 + k] = ema_one(e[i0 + k], p[i0 + k], d, omd);
+        }
+    }
+}
+
+// One thread, after every entry has been updated: an applied update counts.
+__global__ void ema_advance_kernel(EmaState* __restrict__ state, const float* __restrict__ found_inf) {
+    if (found_inf != nullptr && *found_inf != 0.f) return;
+    state->updates += 1;
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -221,6 +342,44 @@ int yolo_sgd_step_amp(const void* items_dev, int n_items, const int32_t* chunks_
     hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const SgdItem*)items_dev, n_items, found_inf_dev, (int*)written_dev);
     return check_launch("sgd_step_amp");
+}
+
+int yolo_sgd_step_hp_ema(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, const void* shadows_dev,
+                         const void* ema_state_dev, int nesterov, int maximize, void* stream) {
+    if (n_chunks == 0) return YOLO_OK;
+    if (!items_dev || !chunks_dev || !hyper4_dev || !shadows_dev || !ema_state_dev || n_chunks < 0 || ((size_t)hyper4_dev & 15) ||
+        ((size_t)ema_state_dev & 15))
+        return fail(YOLO_ERR_ARG, "sgd_step_hp_ema: bad arguments");
+    hipLaunchKernelGGL(sgd_step_ema_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
+                       (const int2*)chunks_dev, hyper4_dev, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr,
+                       (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
+    return check_launch("sgd_step_hp_ema");
+}
+
+int yolo_sgd_step_amp_ema(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                          const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, const void* shadows_dev,
+                          const void* ema_state_dev, int nesterov, int maximize, void* stream) {
+    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
+    if (!items_dev || !chunks_dev || !hyper4_dev || !found_inf_dev || !written_dev || !shadows_dev || !ema_state_dev || n_chunks < 0 ||
+        n_items < 0 || ((size_t)hyper4_dev & 15) || ((size_t)ema_state_dev & 15))
+        return fail(YOLO_ERR_ARG, "sgd_step_amp_ema: bad arguments");
+    hipLaunchKernelGGL(sgd_step_ema_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
+                       (const int2*)chunks_dev, hyper4_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
+                       (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
+    hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const SgdItem*)items_dev, n_items, found_inf_dev, (int*)written_dev);
+    return check_launch("sgd_step_amp_ema");
+}
+
+int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chunks, void* ema_state_dev, const float* found_inf_dev,
+                    int advance, void* stream) {
+    if (!ema_state_dev || ((size_t)ema_state_dev & 15) || n_chunks < 0 || (n_chunks > 0 && (!items_dev || !chunks_dev)))
+        return fail(YOLO_ERR_ARG, "ema_update: bad arguments");
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const EmaItem*)items_dev,
+                           (const int2*)chunks_dev, (const EmaState*)ema_state_dev, found_inf_dev);
+    if (advance) hipLaunchKernelGGL(ema_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (EmaState*)ema_state_dev, found_inf_dev);
+    return check_launch("ema_update");
 }
 
 }  // extern "C"

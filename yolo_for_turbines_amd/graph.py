@@ -30,10 +30,16 @@ class GraphedTrainStep:
     scale, the growth tracker and the skip decision are device memory read at replay time, so a replay whose gradients
     overflow skips its update and halves the scale like an eager step. The warm-up steps go through the scaler too. The
     returned loss is the unscaled one; ``grad_scaler.get_scale()`` reads the live value (and waits for the device).
+
+    ``ema`` (a :class:`yolo_for_turbines_amd.ModelEMA` of ``model``): the weight average moves inside the captured step. With a
+    :class:`yolo_for_turbines_amd.SGD` it is attached to the optimizer (if it is not already) and rides in the step's own
+    launch; with any other optimizer the step ends with ``ema.update()``. The warm-up steps go through it like everything
+    else, its decay follows the device counter through the replays, and every replay invalidates the packed weights of
+    ``ema.module`` along with the live model's.
     """
 
     def __init__(self, model, optimizer, scaled_anchors, x, targets, autocast_dtype=None, loss_fn=None, warmup=3,
-                 zero_grad=True, allow_data_parallel=None, grad_scaler=None):
+                 zero_grad=True, allow_data_parallel=None, grad_scaler=None, ema=None):
         if not x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors (no CPU fallback)")
         if grad_scaler is not None:
@@ -46,6 +52,16 @@ class GraphedTrainStep:
             if not grad_scaler.is_enabled():
                 raise ValueError("GraphedTrainStep: grad_scaler is disabled; pass grad_scaler=None instead")
         self.scaler = grad_scaler
+        self.ema = ema
+        self._ema_update = False                        # the step body ends with ema.update() (the optimizer cannot carry it)
+        if ema is not None:
+            from .optim import SGD
+            if isinstance(optimizer, SGD):
+                ema.attach(optimizer)                   # raises if it is attached elsewhere
+            elif ema._attached is not None:
+                raise RuntimeError("GraphedTrainStep: ema is attached to another optimizer than the one this step runs")
+            else:
+                self._ema_update = True
         if allow_data_parallel is None:
             allow_data_parallel = os.environ.get("YOLO_DP_GRAPH", "0") == "1"
         self._dp = getattr(model._engine, "ddp", None) is not None and model._engine.ddp[0] is not None
@@ -107,6 +123,8 @@ class GraphedTrainStep:
         else:
             loss.backward()
             self.opt.step()
+        if self._ema_update:
+            self.ema.update()
         return loss.detach()
 
     def _hyper_snapshot(self):
@@ -133,6 +151,8 @@ class GraphedTrainStep:
         # the replay rewrote every parameter and BatchNorm statistic without dispatching a torch op: version counters did
         # not move, so every packed weight / BN fold cached for eval is stale by construction
         self.model._engine.invalidate()
+        if self.ema is not None and hasattr(self.ema.module, "_engine"):
+            self.ema.module._engine.invalidate()        # the averaged tensors were rewritten the same way
         return self.loss
 
     def release(self):

@@ -10,6 +10,9 @@ Under a loss scale (`yolo_for_turbines_amd.GradScaler`, or anything that sets th
 optimizers use, `optimizer.grad_scale` and `optimizer.found_inf`) the step unscales in registers and is skipped on the device
 when `found_inf` is set: no host wait, capturable. Whether a momentum buffer has been written yet is then a device fact
 (a skipped first step leaves it unwritten), kept as one int32 word per parameter next to the tables.
+
+With a weight average attached (`ema.ModelEMA.attach`) the same launch also moves the average of every parameter it updates
+(the `_ema` entry points); without one the step is the launches it always was.
 """
 import torch
 
@@ -55,6 +58,10 @@ class _GroupTable:
         self.written = torch.zeros(len(params), dtype=torch.int32, device=dev)
         self.device_first = False
         self.no_inf = torch.zeros(1, dtype=torch.float32, device=dev)
+        # weight average (ema.ModelEMA.attach): one float* per parameter, the averaged tensor the step moves along with it
+        # (0: none). The averaged tensors never move, so this is uploaded once per (table, average).
+        self.shadows = None
+        self.shadows_of = None
 
     def _pinned(self):
         return torch.zeros((len(self.params), 4), dtype=torch.int64).pin_memory()
@@ -107,6 +114,7 @@ class SGD(torch.optim.SGD):
                          maximize=maximize)
         self._tables = {}                                   # group index -> _GroupTable
         self._word = {}                                     # parameter -> its 1-element view of a table's `written`
+        self._ema = None                                    # ema.ModelEMA.attach: step() moves that average in its own launch
 
     def _table(self, gi, params):
         t = self._tables.get(gi)
@@ -181,7 +189,7 @@ class SGD(torch.optim.SGD):
 
     def _prepare(self, gi, group, scaled):
         """Fill and (if it changed) upload the row table of one group for the gradients as they are now. Returns
-        (table, indices of momentum buffers the host marked new)."""
+        (table, indices of momentum buffers the host marked new, parameters this step updates)."""
         tab = self._table(gi, group["params"])
         mom = float(group["momentum"])
         capturing = torch.cuda.is_current_stream_capturing()
@@ -191,6 +199,12 @@ class SGD(torch.optim.SGD):
         if not capturing or hyper != tab.hyper_host:      # inside a capture an unchanged value needs no node at all
             tab.push_hyper(hyper)
         scaled = scaled or tab.device_first
+        if self._ema is not None and tab.shadows_of is not self._ema:
+            if capturing:
+                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing (the first step with a "
+                                   "weight average attached uploads its pointer table)")
+            tab.shadows = torch.tensor([L.ptr(self._ema.shadow_of(p)) for p in tab.params], dtype=torch.int64).to(tab.items.device)
+            tab.shadows_of = self._ema
         host, slot = tab.host_buffer(capturing)
         rows = host.numpy()                              # [p, g, momentum buffer, n] per parameter (yolo_sgd_item)
         updated, fresh = [], []
@@ -235,7 +249,7 @@ class SGD(torch.optim.SGD):
             if slot is not None:
                 slot[1] = torch.cuda.Event()
                 slot[1].record()
-        return tab, fresh
+        return tab, fresh, updated
 
     @staticmethod
     def _flag(t, dev, what):
@@ -248,7 +262,9 @@ class SGD(torch.optim.SGD):
         """One launch per parameter group. With the tensor attributes ``self.grad_scale`` / ``self.found_inf`` set (what
         ``GradScaler.step`` hands PyTorch's fused optimizers) the gradients are unscaled in registers (``p.grad`` keeps the
         scaled values) and nothing is touched when ``found_inf`` is non-zero; without them nothing changes. ``check_into``
-        (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it."""
+        (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it. With a weight
+        average attached (``ModelEMA.attach``) the same launches also move the average of every parameter they update; one
+        more launch does the entries left over (BatchNorm statistics, parameters without a gradient) and counts the update."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -260,30 +276,38 @@ class SGD(torch.optim.SGD):
         ready = [(g,) + self._prepare(gi, g, scaled) for gi, g in groups]
         if check_into is not None:                           # every group is checked before any group is stepped
             self._check(ready, check_into)
-        for group, tab, fresh in ready:
+        ema = self._ema
+        if ema is not None:                                  # what these launches leave over, decided (and uploaded) before them
+            rest = ema._rest({id(p) for r in ready for p in r[3]})
+        # with a weight average attached: the `_ema` twins of the two entry points, which take {shadow table, EMA state} too
+        step_amp, step_hp = (lib.yolo_sgd_step_amp, lib.yolo_sgd_step_hp) if ema is None else (lib.yolo_sgd_step_amp_ema, lib.yolo_sgd_step_hp_ema)
+        for group, tab, fresh, _ in ready:
             dev = tab.hyper.device
             nest, maxi = int(bool(group["nesterov"])), int(bool(group["maximize"]))
+            avg = () if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
+            what = "yolo_sgd_step" + ("_amp" if scaled or tab.device_first else "_hp") + ("" if ema is None else "_ema")
             if scaled or tab.device_first:
                 flag = self._flag(found_inf, dev, "found_inf")
-                L.check(lib.yolo_sgd_step_amp(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0],
-                                              tab.hyper.data_ptr(), L.ptr(self._flag(grad_scale, dev, "grad_scale")),
-                                              (flag if flag is not None else tab.no_inf).data_ptr(), tab.written.data_ptr(), nest, maxi,
-                                              L.current_stream()), "yolo_sgd_step_amp")
+                L.check(step_amp(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(),
+                                 L.ptr(self._flag(grad_scale, dev, "grad_scale")), (flag if flag is not None else tab.no_inf).data_ptr(),
+                                 tab.written.data_ptr(), *avg, nest, maxi, L.current_stream()), what)
                 continue
-            L.check(lib.yolo_sgd_step_hp(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(),
-                                         nest, maxi, L.current_stream()), "yolo_sgd_step_hp")
+            L.check(step_hp(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(), *avg, nest, maxi,
+                            L.current_stream()), what)
             if len(fresh) == len(tab.params):                # the host marked these buffers new and this step wrote them
                 tab.written.fill_(1)
             else:
                 for i in fresh:
                     tab.written[i:i + 1].fill_(1)
+        if ema is not None:                                  # the entries left over, then the counter; both skipped with the step
+            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
         return loss
 
     def _check(self, ready, found_inf):
         lib = L.lib()
         if not ready:
             found_inf.zero_()
-        for k, (_, tab, _) in enumerate(ready):
+        for k, (_, tab, _, _) in enumerate(ready):
             L.check(lib.yolo_sgd_check_finite(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0],
                                               self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
                                               L.current_stream()), "yolo_sgd_check_finite")
