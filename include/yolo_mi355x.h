@@ -42,6 +42,14 @@ enum { YOLO_ACT_NONE = 0, YOLO_ACT_LEAKY = 1, YOLO_ACT_MISH = 2 };
 enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
 /* YOLO_FLAG_FILTERS_READY (layers of the Winograd F(4x4) family, tile 15, only): w_packed is not the packed weight buffer but the
  * transformed filters U4 that yolo_wino4_filters made of it.
+ * YOLO_FLAG_FILTERS_APPENDED (the same layers): w_packed is the packed weight buffer, and U4 lies behind the packed weights in the
+ * same buffer, at yolo_packed_weight_bytes(cout, cin, 3, YOLO_F32) rounded up to 16 (yolo_wino4_appended_bytes of room in all);
+ * yolo_wino4_filters(d, w, (char*)w + that offset) made it in place. Same bits as the launch without the flag. It is also the one
+ * flag the tile heuristic reads: a caller that brings finished filters gets tile 15 on the small maps that measured faster that
+ * way (yolo_conv_pick_tile, yolo_conv_workspace_bytes and the launch agree; without the flag nothing changes). Accepted on fp32
+ * descriptors that run as tile 15 with its workspace (a forced tile 15 honours it on any shape tile 15 supports), else an
+ * argument error; together with YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16, YOLO_FLAG_SPLIT_WEIGHTS_READY or YOLO_FLAG_SPLIT_K
+ * it is refused with YOLO_ERR_UNSUPPORTED.
  * YOLO_FLAG_SPLIT_BF16 (fp32 layers of the direct kernels only: ksize 1 or 3, stride 1 or 2, cin a multiple of 32, no Winograd
  * workspace in play): the products run on the bf16 matrix cores. Each fp32 operand is split exactly into three bf16 values and six
  * of the nine partial products are accumulated in fp32, in one fixed order: the result has the accuracy of the fp32 kernel
@@ -59,11 +67,11 @@ enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
  * do not depend on its batch; fp32 accuracy, but not the bits of the launch without the flag (the sum is ordered differently). It
  * runs whatever Winograd or the bf16 split would have chosen, through yolo_conv_fwd_ws / yolo_conv_fwd_batch with the workspace
  * yolo_conv_workspace_bytes asks for (16-byte aligned), else YOLO_ERR_WORKSPACE (always from yolo_conv_fwd, which has none).
- * Together with YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, with a forced tile, on a 16-bit
+ * Together with YOLO_FLAG_FILTERS_READY, YOLO_FLAG_FILTERS_APPENDED, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, with a forced tile, on a 16-bit
  * descriptor or with cin of 3 or 4 the flag is refused with YOLO_ERR_UNSUPPORTED and nothing is launched. Without the flag nothing
  * changes. */
 enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8,
-       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32 };
+       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32, YOLO_FLAG_FILTERS_APPENDED = 64 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -205,9 +213,19 @@ int yolo_split3_weights(const yolo_conv_desc* d, const void* w_packed, void* out
  * w_packed (yolo_pack_weights, or yolo_pack_weights_dgrad with flip = 1): the very values a launch without the flag leaves behind
  * V4 in its workspace. A descriptor with YOLO_FLAG_FILTERS_READY then takes that U4 as the w_packed of yolo_conv_fwd_ws /
  * yolo_conv_fwd_batch; the workspace size stays what yolo_conv_workspace_bytes reports, its U4 part is left alone. The flag
- * on a descriptor that does not run as tile 15 is an argument error. */
+ * on a descriptor that does not run as tile 15 is an argument error.
+ * yolo_wino4_filters works in place: it reads only the row-major section at the start of w_packed (cout rows of K_pad32 floats),
+ * so U4 may lie anywhere behind that section in the same buffer, in particular behind the packed bytes rounded up to 16, where
+ * YOLO_FLAG_FILTERS_APPENDED expects it; a U4 that overlaps the section itself is an argument error.
+ * yolo_wino4_appended_bytes: the room such a buffer needs, packed bytes rounded up to 16 plus yolo_wino4_filter_bytes (0: the
+ * descriptor cannot run as tile 15). yolo_wino4_appended_wanted: 1 when the heuristic admits some small map of a layer with
+ * these channel counts once YOLO_FLAG_FILTERS_APPENDED is set (cin, cout, ksize, stride, dtype only: the layers worth the room).
+ * A descriptor with tile forced to 15 may have any cin that is a multiple of 4 (the transforms pad an odd count of channel quads
+ * with a zero plane); the heuristic and every other tile keep the rule of the direct kernels, cin <= 4 or a multiple of 32. */
 size_t yolo_wino4_filter_bytes(const yolo_conv_desc* d);
 int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, void* stream);
+size_t yolo_wino4_appended_bytes(const yolo_conv_desc* d);
+int yolo_wino4_appended_wanted(const yolo_conv_desc* d);
 /* How a tile-15 launch is cut on the current device: *whole tile blocks (64 tiles each) run as one workgroup per channel block;
  * *half tile blocks, those of a last round that would fill at most half the compute units, run as two workgroups of 32 tiles.
  * The result of a tile does not depend on the cut. */

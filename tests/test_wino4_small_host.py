@@ -1,0 +1,188 @@
+"""Host side of Winograd F(4x4) on the small maps: the picks with and without YOLO_FLAG_FILTERS_APPENDED, the refused flag
+combinations, yolo_wino4_appended_bytes, and the eval plan's route (plans built on the CPU device: no launch)."""
+import copy
+import ctypes as C
+import pickle
+
+import pytest
+import torch
+
+
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as g
+    g.build()
+    from yolo_for_turbines_amd import _lib
+    return _lib
+
+
+def _desc(L, n, hw, cin, cout, flags=0, tile=0, ksize=3, stride=1, dtype=None, w=None):
+    return L.ConvDesc(n=n, h=hw, w=w or hw, cin=cin, cout=cout, ksize=ksize, stride=stride, x_ld=cin, y_ld=cout, act=L.ACT_LEAKY,
+                      out_mode=L.OUT_NHWC, dtype=L.F32 if dtype is None else dtype, flags=flags, tile=tile)
+
+
+def test_picks_with_and_without_appended_filters(built):
+    """Without the flag the picks are today's at every shape; with it the 13 x 13 and 19 x 19 maps of 512 -> 1024 pick tile 15, at
+    n = 1 and n = 32 alike (shape only), and the workspace is that of tile 15. Every other small map stays on F(2x2)."""
+    L = built
+    lib = L.lib()
+    A = L.FLAG_FILTERS_APPENDED
+    for hw, cin, cout, plain, flagged in ((13, 512, 1024, 13, 15), (19, 512, 1024, 13, 15), (26, 256, 512, 15, 15), (52, 128, 256, 15, 15),
+                                          (13, 256, 512, 13, 13), (13, 1024, 512, 13, 13), (13, 512, 512, 13, 13), (7, 512, 1024, 13, 13),
+                                          (10, 512, 1024, 13, 13), (14, 512, 1024, 13, 13), (20, 512, 1024, 13, 13)):
+        for n in (1, 32):
+            assert lib.yolo_conv_pick_tile(_desc(L, n, hw, cin, cout)) == plain, (hw, cin, cout, n)
+            d = _desc(L, n, hw, cin, cout, flags=A)
+            assert lib.yolo_conv_pick_tile(d) == flagged, (hw, cin, cout, n)
+            if flagged == 15:
+                tiles = n * ((hw + 3) // 4) ** 2
+                assert lib.yolo_conv_workspace_bytes(d) == 36 * (cin // 4) * ((tiles + 63) // 64 * 64 + (cout + 63) // 64 * 64) * 16
+    assert lib.yolo_conv_pick_tile(_desc(L, 32, 13, 512, 1024, flags=A, w=19)) == 13             # a 13 x 19 map was not measured
+    # the channel counts whose blocks are worth the room: (cin, cout, ksize, stride, dtype) alone
+    assert lib.yolo_wino4_appended_wanted(_desc(L, 1, 8, 512, 1024)) == 1
+    for other in (_desc(L, 1, 8, 256, 512), _desc(L, 1, 8, 1024, 512), _desc(L, 1, 8, 512, 1024, ksize=1),
+                  _desc(L, 1, 8, 512, 1024, stride=2), _desc(L, 1, 8, 512, 1024, dtype=L.BF16)):
+        assert lib.yolo_wino4_appended_wanted(other) == 0
+
+
+def test_appended_bytes(built):
+    """Packed bytes rounded up to 16 plus the filter bytes, from (cin, cout) alone; 0 where tile 15 is unsupported."""
+    L = built
+    lib = L.lib()
+    for cin, cout in ((512, 1024), (64, 64), (68, 84), (4, 64)):
+        off = (lib.yolo_packed_weight_bytes(cout, cin, 3, L.F32) + 15) // 16 * 16
+        u4 = 36 * ((cin // 4 + 1) // 2 * 2) * ((cout + 63) // 64 * 64) * 16
+        for n, hw in ((1, 13), (32, 13), (2, 52)):
+            d = _desc(L, n, hw, cin, cout)
+            assert lib.yolo_wino4_filter_bytes(d) == u4
+            assert lib.yolo_wino4_appended_bytes(d) == off + u4
+    assert lib.yolo_wino4_filter_bytes(_desc(L, 32, 13, 512, 1024)) == 75_497_472               # 7 such blocks: +528 MB per model
+    for bad in (_desc(L, 1, 13, 512, 1024, ksize=1), _desc(L, 1, 13, 512, 1024, stride=2), _desc(L, 1, 13, 510, 1024),
+                _desc(L, 1, 13, 512, 1024, dtype=L.BF16)):
+        assert lib.yolo_wino4_appended_bytes(bad) == 0
+
+
+def test_refused_flag_combinations(built):
+    """The flag is refused before anything is launched (the pointers are never dereferenced): together with another kernel flag
+    (unsupported), and on a descriptor that does not run as tile 15 (an argument error, like YOLO_FLAG_FILTERS_READY). A forced
+    tile 15 honours it on a shape the heuristic does not admit: the launch then gets as far as its workspace check."""
+    L = built
+    lib = L.lib()
+    A = L.FLAG_FILTERS_APPENDED
+
+    def launch(d, ws_bytes=1 << 40):
+        return lib.yolo_conv_fwd_ws(d, 16, 16, 16, 16, 0, 16, 16, ws_bytes, 0, 0)
+
+    for other in (L.FLAG_FILTERS_READY, L.FLAG_SPLIT_BF16, L.FLAG_SPLIT_BF16 | L.FLAG_SPLIT_WEIGHTS_READY, L.FLAG_SPLIT_WEIGHTS_READY,
+                  L.FLAG_SPLIT_K):
+        for tile in (0, 15):
+            d = _desc(L, 32, 13, 512, 1024, flags=A | other, tile=tile)
+            assert launch(d) == -2, (other, tile)
+            assert b"FILTERS_APPENDED" in lib.yolo_last_error()
+    assert lib.yolo_conv_workspace_bytes(_desc(L, 32, 13, 512, 1024, flags=A | L.FLAG_SPLIT_K)) == 0
+    for d in (_desc(L, 1, 13, 1024, 512, flags=A, ksize=1),           # 1x1
+              _desc(L, 1, 13, 512, 1024, flags=A, tile=5),            # forced to a direct tile
+              _desc(L, 1, 13, 512, 1024, flags=A, tile=13),           # forced to F(2x2)
+              _desc(L, 1, 13, 256, 512, flags=A),                     # a small map the rule does not admit: F(2x2)
+              _desc(L, 1, 13, 512, 1024, flags=A, dtype=L.BF16)):     # 16-bit
+        assert launch(d) == -1
+        assert b"FILTERS_APPENDED" in lib.yolo_last_error()
+    assert launch(_desc(L, 32, 13, 512, 1024, flags=A), ws_bytes=0) == -1         # no workspace: the heuristic cannot pick tile 15
+    assert launch(_desc(L, 1, 13, 256, 512, flags=A, tile=15), ws_bytes=16) == -4  # forced: honoured, the workspace is too small
+    assert b"workspace" in lib.yolo_last_error()
+
+
+def test_forced_tile_15_takes_any_multiple_of_four_channels(built):
+    """cin = 68 (an odd count of channel quads: the transforms pad a zero plane) is a shape of tile 15 alone: accepted with the tile
+    forced, refused as before for the heuristic, for every other tile and with a stride the kernel does not have."""
+    L = built
+    lib = L.lib()
+    assert lib.yolo_conv_workspace_bytes(_desc(L, 3, 13, 68, 84, tile=15)) == 36 * 18 * (64 + 128) * 16
+    assert lib.yolo_conv_fwd_ws(_desc(L, 3, 13, 68, 84, tile=15), 16, 16, 16, 16, 0, 16, 16, 16, 0, 0) == -4      # as far as the workspace check
+    for d in (_desc(L, 3, 13, 68, 84), _desc(L, 3, 13, 68, 84, tile=13), _desc(L, 3, 13, 68, 84, tile=4),
+              _desc(L, 3, 13, 68, 84, tile=15, stride=2), _desc(L, 3, 13, 68, 84, tile=15, ksize=1)):
+        assert lib.yolo_conv_fwd_ws(d, 16, 16, 16, 16, 0, 16, 16, 1 << 40, 0, 0) == -2
+        assert lib.yolo_conv_workspace_bytes(d) == 0 and lib.yolo_conv_pick_tile(d) == -2
+
+
+def test_packed_block_keeps_room_for_appended_filters(built):
+    """The 512 -> 1024 3x3 stride-1 block gets the room at creation (the buffer cannot grow later); the filters are a view of w,
+    start stale, and `invalidate` makes them stale again. Other blocks have no room and want_u4a says so."""
+    import yolo_for_turbines_amd as yt
+    from yolo_for_turbines_amd import engine
+    L = built
+    lib = L.lib()
+    st = engine.ModelState()
+    blk = yt.model.CNNBlock(512, 1024, kernel_size=3, padding=1)
+    pk = st.packed(blk, torch.device("cpu"))
+    d = _desc(L, 32, 13, 512, 1024)
+    assert pk.w.numel() == lib.yolo_wino4_appended_bytes(d) and pk.u4a is None and pk.u4 is None
+    u = pk.want_u4a(d)
+    off = (lib.yolo_packed_weight_bytes(1024, 512, 3, L.F32) + 15) // 16 * 16
+    assert u.data_ptr() == pk.w.data_ptr() + off and u.numel() == 75_497_472 and pk.u4a_stamp is None
+    assert pk.want_u4a(_desc(L, 1, 19, 512, 1024)) is u
+    pk.u4a_stamp = pk.stamp = engine.PackedBlock.stamp_of(blk)[0]
+    st.invalidate()
+    assert pk.stamp is None and pk.u4a_stamp is None
+    small = st.packed(yt.model.CNNBlock(256, 512, kernel_size=3, padding=1), torch.device("cpu"))
+    assert small.w.numel() == lib.yolo_packed_weight_bytes(512, 256, 3, L.F32)
+    assert small.want_u4a(_desc(L, 1, 13, 256, 512)) is None
+    assert st.packed(blk, torch.device("cpu"), "bf16").w.numel() == lib.yolo_packed_weight_bytes(1024, 512, 3, L.BF16)   # fp32 only
+
+
+def test_eval_plan_routes_the_13x13_layers(built):
+    """At batch 32, 416 x 416, 80 classes: 7 launches carry YOLO_FLAG_FILTERS_APPENDED, all 512 -> 1024 at 13 x 13, their w_packed
+    is the block's w, their workspace covers tile 15's request; the 24 YOLO_FLAG_FILTERS_READY launches are as before. With
+    ModelState.wino4_small off, in latency mode, with a forced tile, on a bf16 plan and on a train plan nothing carries the flag."""
+    import yolo_for_turbines_amd as yt
+    from yolo_for_turbines_amd import engine, train_engine
+    L = built
+    lib = L.lib()
+    A = L.FLAG_FILTERS_APPENDED
+    m = yt.YOLOv3(num_classes=80).eval()
+    dev = torch.device("cpu")
+    prog = engine.build_network_program(m, 32, 416)
+    st = engine.ModelState()
+    assert st.wino4_small is True
+    plan = engine.Plan(prog, st, dev)
+    flagged = [i for i in range(len(plan.table)) if plan.table[i].d.flags & A]
+    assert len(flagged) == 7
+    for i in flagged:
+        e = plan.table[i]
+        pk = st.packed(plan.blocks[i], dev)
+        assert (e.d.h, e.d.w, e.d.cin, e.d.cout, e.d.ksize, e.d.stride, e.d.tile) == (13, 13, 512, 1024, 3, 1, 0)
+        assert e.w_packed == pk.w.data_ptr() and pk.u4a is not None and pk.u4 is None and pk.u4a_stamp is None
+        assert not e.d.flags & (L.FLAG_FILTERS_READY | L.FLAG_SPLIT_BF16 | L.FLAG_SPLIT_WEIGHTS_READY | L.FLAG_SPLIT_K)
+        assert lib.yolo_conv_pick_tile(C.byref(e.d)) == 15
+        assert e.workspace and e.workspace_bytes >= lib.yolo_conv_workspace_bytes(C.byref(e.d)) > 0
+    ready = [i for i in range(len(plan.table)) if plan.table[i].d.flags & L.FLAG_FILTERS_READY]
+    assert len(ready) == 24 and not set(ready) & set(flagged)
+    plan608 = engine.Plan(engine.build_network_program(m, 2, 608), st, dev)             # 19 x 19: the same seven blocks, the same room
+    f608 = [i for i in range(len(plan608.table)) if plan608.table[i].d.flags & A]
+    assert len(f608) == 7 and all(plan608.table[i].d.h == 19 for i in f608)
+    assert [plan608.table[i].w_packed for i in f608] == [plan.table[i].w_packed for i in flagged]
+    st_off = engine.ModelState()
+    st_off.wino4_small = False
+    st_lat = engine.ModelState()
+    st_lat.latency = True
+    tprog = engine.build_network_program(m, 2, 416)
+    plans = [engine.Plan(prog, st_off, dev), engine.Plan(engine.build_network_program(m, 1, 416), st_lat, dev),
+             engine.Plan(prog, engine.ModelState(), dev, tile_override=13), engine.Plan(prog, engine.ModelState(), dev, tile_override=15),
+             engine.Plan(engine.build_network_program(m, 32, 416, ch_align=8), engine.ModelState(), dev, dtype="bf16")]
+    for p in plans:
+        assert not any(p.table[i].d.flags & A for i in range(len(p.table)))
+    off13 = [i for i in range(len(plans[0].table)) if plans[0].table[i].d.h == 13 and plans[0].table[i].d.ksize == 3 and plans[0].table[i].d.stride == 1]
+    assert len(off13) == 7 and all(lib.yolo_conv_pick_tile(C.byref(plans[0].table[i].d)) == 13 for i in off13)
+    # the train path builds its descriptors from the program's flags alone (train_engine._desc): the program carries no such flag
+    assert not any(op["flags"] & A for op in tprog.ops)
+    assert "FLAG_FILTERS_APPENDED" not in open(train_engine.__file__).read()
+
+
+def test_model_state_carries_wino4_small(built):
+    from yolo_for_turbines_amd import engine
+    st = engine.ModelState()
+    assert pickle.loads(pickle.dumps(st)).wino4_small is True and copy.deepcopy(st).wino4_small is True
+    st.wino4_small = False
+    assert pickle.loads(pickle.dumps(st)).wino4_small is False and copy.deepcopy(st).wino4_small is False
+    st.__setstate__({"nan_check": False})                 # a state pickled before the attribute existed
+    assert st.wino4_small is True

@@ -4,6 +4,8 @@
   python tools/conv_bench.py --layer c52_3x3 --tile 0 --reps 20
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3 --rounds 5      (YOLO_FLAG_SPLIT_BF16; median and spread of 5 rounds)
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3-ready --rounds 5    (the same on weights split once: yolo_split3_weights)
+  python tools/conv_bench.py --layer c13_3x3 --filters-ready --rounds 7 --reps 20    (tile 15 on filters transformed once: yolo_wino4_filters)
+  python tools/conv_bench.py --layer c13_3x3,c19_3x3 --tile 0 --filters-appended --rounds 7    (the eval plan's route on the small maps)
   python tools/conv_bench.py --splitk --rounds 7 --reps 100      (batch 1: every fp32 conv shape of the 416 and 608 networks on the
                                                                   default plan's launch and as YOLO_FLAG_SPLIT_K, alternating)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
@@ -38,6 +40,7 @@ LAYERS = {   # name: (H, cin, cout, k, stride)
     "c13_1x1": (13, 1024, 512, 1, 1),
     "c13_3x3": (13, 512, 1024, 3, 1),
     "c13_head": (13, 1024, 255, 1, 1),
+    "c19_3x3": (19, 512, 1024, 3, 1),          # the 13x13 layer's place in the 608 network
     # the remaining 1x1 shapes of the neck and the other two heads
     "c52_1x1_384": (52, 384, 128, 1, 1),
     "c26_1x1_768": (26, 768, 256, 1, 1),
@@ -49,7 +52,7 @@ LAYERS = {   # name: (H, cin, cout, k, stride)
 OUT_MODES = {"nhwc": L.OUT_NHWC, "up2x": L.OUT_UPSAMPLE2X, "head": L.OUT_HEAD}
 
 
-def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False):
+def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False, filters_ready=False, filters_appended=False):
     H, cin, cout, k, s = LAYERS[name]
     lib = L.lib()
     cpad = (cin + 3) // 4 * 4
@@ -73,6 +76,18 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
         ws3 = torch.empty(lib.yolo_split3_weight_bytes(d), dtype=torch.uint8, device=dev)
         L.check(lib.yolo_split3_weights(d, wp.data_ptr(), ws3.data_ptr(), stream), "yolo_split3_weights")
         wp = ws3
+    if filters_ready:                                             # Winograd F(4x4) on filters transformed once, in place of wp
+        d.flags |= L.FLAG_FILTERS_READY
+        d.tile = 15
+        u4 = torch.empty(lib.yolo_wino4_filter_bytes(d), dtype=torch.uint8, device=dev)
+        L.check(lib.yolo_wino4_filters(d, wp.data_ptr(), u4.data_ptr(), stream), "yolo_wino4_filters")
+        wp = u4
+    if filters_appended:                                         # the route of the eval plan: U4 in place behind the packed weights, tile as given
+        d.flags |= L.FLAG_FILTERS_APPENDED
+        wa = torch.empty(lib.yolo_wino4_appended_bytes(d), dtype=torch.uint8, device=dev)
+        wa[:wp.numel()] = wp
+        L.check(lib.yolo_wino4_filters(d, wa.data_ptr(), wa.data_ptr() + wa.numel() - lib.yolo_wino4_filter_bytes(d), stream), "yolo_wino4_filters")
+        wp = wa
 
     need = lib.yolo_conv_workspace_bytes(d)                       # > 0: Winograd (tile 13, or the heuristic's choice for tile 0)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -96,7 +111,7 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     ms = times[len(times) // 2]                                   # median round
     run.rounds = list(times)                                      # (for drivers that want the spread as numbers)
     gflop = 2.0 * batch * Ho * Ho * cout * cin * k * k / 1e9
-    picked = (lib.yolo_conv_pick_tile(d) if dtype == "fp32" else 0) if tile == 0 else tile
+    picked = (lib.yolo_conv_pick_tile(d) if dtype == "fp32" else 0) if d.tile == 0 else d.tile
     cut = ""
     if split3 or ready:
         cut += f"  split3{'-ready' if ready else ''} (tile {tile})"
@@ -107,7 +122,7 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     if picked == 15:                                              # Winograd F(4x4): how the launch is cut on this device
         whole, half = C.c_int(), C.c_int()
         L.check(lib.yolo_conv_wino4_blocks(d, C.byref(whole), C.byref(half)), "yolo_conv_wino4_blocks")
-        cut = f"  tile blocks: {whole.value} whole + {half.value} in halves"
+        cut += f"  tile blocks: {whole.value} whole + {half.value} in halves" + ("  filters ready" if filters_ready else "") + ("  filters appended" if filters_appended else "")
     print(f"{name:12s} tile={picked} {ms * 1e3:8.1f} us  {gflop / ms:7.2f} TFLOP/s  ({gflop:.1f} GFLOP){cut}", flush=True)
     return ms
 
@@ -188,6 +203,8 @@ def main():
     ap.add_argument("--dtype", default="fp32")
     ap.add_argument("--split3", action="store_true", help="set YOLO_FLAG_SPLIT_BF16 (tile 0, 1, 2 or 4)")
     ap.add_argument("--split3-ready", action="store_true", help="YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY on prepared weights")
+    ap.add_argument("--filters-ready", action="store_true", help="tile 15 with YOLO_FLAG_FILTERS_READY on filters made once (yolo_wino4_filters)")
+    ap.add_argument("--filters-appended", action="store_true", help="YOLO_FLAG_FILTERS_APPENDED: U4 made in place behind the packed weights (tile 0: the eval plan's route)")
     ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
     ap.add_argument("--splitk", action="store_true", help="batch-1 table: the default plan's launch against YOLO_FLAG_SPLIT_K, per conv shape")
@@ -201,7 +218,7 @@ def main():
     tiles = list(range(1, nt + 1)) if a.tile == "all" else [int(t) for t in a.tile.split(",")]
     for n in names:
         for t in tiles:
-            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready)
+            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready, a.filters_ready, a.filters_appended)
 
 
 if __name__ == "__main__":

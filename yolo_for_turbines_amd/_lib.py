@@ -16,6 +16,7 @@ ACT_NONE, ACT_LEAKY, ACT_MISH = 0, 1, 2
 OUT_NHWC, OUT_UPSAMPLE2X, OUT_HEAD = 0, 1, 2
 FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY, FLAG_SPLIT_BF16, FLAG_SPLIT_WEIGHTS_READY = 1, 2, 4, 8, 16
 FLAG_SPLIT_K = 32
+FLAG_FILTERS_APPENDED = 64
 
 
 class PackItem(C.Structure):
@@ -110,6 +111,8 @@ _SIGS = {
     "yolo_conv_num_tiles": (C.c_int, []),
     "yolo_wino4_filter_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "yolo_wino4_filters": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_wino4_appended_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "yolo_wino4_appended_wanted": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_wino4_blocks": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "yolo_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_bn_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,

@@ -238,11 +238,13 @@ int conv_wino_launch(const yolo_conv_desc* d, const void* x, const float* U, con
                      const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // conv_wino4_f32.hip (fp32 3x3 stride 1 by Winograd F(4x4, 3x3), tile 15: transform pass (input and filters, from the row-major
 // section of the packed weights, unless the caller brings them transformed: U4_ready) into a caller-owned workspace + 36 GEMMs
-// in six passes)
+// in six passes). wino4_eligible reads d->flags: a caller that brings finished filters behind the packed weights
+// (YOLO_FLAG_FILTERS_APPENDED) is also admitted on the small maps that measured faster that way
 bool wino4_supported(const yolo_conv_desc* d);
 bool wino4_eligible(const yolo_conv_desc* d);
 size_t wino4_workspace_bytes(const yolo_conv_desc* d);
 size_t wino4_filter_bytes(const yolo_conv_desc* d);
+size_t wino4_appended_offset(const yolo_conv_desc* d);   // YOLO_FLAG_FILTERS_APPENDED: where U4 begins in the packed buffer
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)

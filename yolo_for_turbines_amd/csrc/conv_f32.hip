@@ -179,7 +179,8 @@ static int pick_direct_tile(const yolo_conv_desc* d) {
 
 // Which kernel family runs an fp32 descriptor: the one place that knows. `ws_avail` is the workspace the caller brings (0: none,
 // SIZE_MAX: whatever yolo_conv_workspace_bytes asks for). A forced tile names its family whether or not the layer fits it - the
-// launch then fails with that family's message; tile 0 is the heuristic, which looks at the layer's shape only, never at the batch.
+// launch then fails with that family's message; tile 0 is the heuristic, which looks at the layer's shape only, never at the batch
+// (and, in wino4_eligible, at whether the caller brings finished filters: YOLO_FLAG_FILTERS_APPENDED).
 enum class F32Family { Direct, Rs, Wino, Wino4 };
 
 static F32Family f32_family(const yolo_conv_desc* d, const void* residual, size_t ws_avail) {
@@ -220,7 +221,9 @@ static int validate(const yolo_conv_desc* d) {
     if (d->stride != 1 && d->stride != 2) return fail(YOLO_ERR_UNSUPPORTED, "conv: stride %d", d->stride);
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0) return fail(YOLO_ERR_ARG, "conv: bad shape");
     const int cp = cin_pad_of(d->cin);
-    if (cp != 4 && cp % 32 != 0) return fail(YOLO_ERR_UNSUPPORTED, "conv: cin %d (need <= 4 or a multiple of 32)", d->cin);
+    // (a forced tile 15 reaches conv_wino4_f32 or nothing: its transforms take any multiple of 4, wino4_supported checks that)
+    const bool forced_wino4 = d->dtype == YOLO_F32 && d->tile == kTileF32Wino4 && d->ksize == 3 && d->stride == 1;
+    if (cp != 4 && cp % 32 != 0 && !forced_wino4) return fail(YOLO_ERR_UNSUPPORTED, "conv: cin %d (need <= 4 or a multiple of 32)", d->cin);
     if (d->x_ld < cp + 0 || (d->x_ld & 3) || (d->x_off & 3)) return fail(YOLO_ERR_ARG, "conv: x_ld/x_off must be multiples of 4 and x_ld >= cin_pad");
     if (d->out_mode == YOLO_OUT_HEAD && d->cout % 3 != 0) return fail(YOLO_ERR_ARG, "conv: head cout %% 3 != 0");
     if (d->out_mode < 0 || d->out_mode > 2) return fail(YOLO_ERR_ARG, "conv: out_mode");
@@ -238,9 +241,9 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     // the split-K pair runs whatever Winograd or the bf16 split would have chosen: it goes with none of their flags, with no forced tile
     const bool splitk = d->flags & YOLO_FLAG_SPLIT_K;
     if (splitk) {
-        if (d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY))
-            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_K goes with none of YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16, "
-                                              "YOLO_FLAG_SPLIT_WEIGHTS_READY");
+        if (d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_K goes with none of YOLO_FLAG_FILTERS_READY, YOLO_FLAG_FILTERS_APPENDED, "
+                                              "YOLO_FLAG_SPLIT_BF16, YOLO_FLAG_SPLIT_WEIGHTS_READY");
         if (d->tile != 0 || !splitk_supported(d))
             return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_K needs an fp32 layer with ksize 1 or 3, stride 1 or 2, cin %% 32 == 0 and tile 0");
         if (!ws || ws_bytes < splitk_workspace_bytes(d))
@@ -250,6 +253,13 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     const bool filters_ready = d->flags & YOLO_FLAG_FILTERS_READY;
     if (filters_ready && (d->dtype != YOLO_F32 || f32_family(d, residual, ws ? ws_bytes : 0) != F32Family::Wino4))
         return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_READY on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
+    // ... or the packed weights with U4 behind them: the same launch, and the only flag that wino4_eligible looks at
+    const bool filters_appended = d->flags & YOLO_FLAG_FILTERS_APPENDED;
+    if (filters_appended && (d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY)))
+        return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_FILTERS_APPENDED goes with none of YOLO_FLAG_FILTERS_READY, YOLO_FLAG_SPLIT_BF16, "
+                                          "YOLO_FLAG_SPLIT_WEIGHTS_READY, YOLO_FLAG_SPLIT_K");
+    if (filters_appended && (d->dtype != YOLO_F32 || f32_family(d, residual, ws ? ws_bytes : 0) != F32Family::Wino4))
+        return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_APPENDED on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
     // the three-way bf16 split runs what the direct kernels would run (conv_igemm_f32, conv_f32_v2, conv1_rs_f32) and nothing else
     const bool split3 = d->flags & YOLO_FLAG_SPLIT_BF16;
     if (split3 && !split3_honoured(d, residual, ws ? ws_bytes : 0))
@@ -282,10 +292,12 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     }
     switch (f32_family(d, residual, ws ? ws_bytes : 0)) {
     case F32Family::Rs: return conv1_rs_launch(d, x, w, scale, shift, residual, y, nan_flag, s);
-    case F32Family::Wino4:          // the filters are transformed per launch from the row-major section, unless w is their transform
+    case F32Family::Wino4: {        // the filters are transformed per launch from the row-major section, unless w is their transform
         if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
-        return conv_wino4_launch(d, x, filters_ready ? nullptr : (const float*)w, filters_ready ? (const float*)w : nullptr, scale, shift,
-                                 residual, y, ws, ws_bytes, nan_flag, s);
+        const float* U4 = filters_ready ? (const float*)w                                                      // ... or has it behind it
+                        : filters_appended ? (const float*)((const char*)w + wino4_appended_offset(d)) : nullptr;
+        return conv_wino4_launch(d, x, U4 ? nullptr : (const float*)w, U4, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
+    }
     case F32Family::Wino: {
         if (!wino_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 13 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         const float* U = (const float*)w + v0_packed_elems(d->cout, d->cin, d->ksize) + v2_frag_elems(d->cout, d->cin, d->ksize);
@@ -353,7 +365,7 @@ int yolo_conv_fwd(const yolo_conv_desc* d, const void* x, const void* w_packed, 
 size_t yolo_conv_workspace_bytes(const yolo_conv_desc* d) {
     if (yolo::validate(d)) return 0;
     if (d->flags & YOLO_FLAG_SPLIT_K)               // 0 wherever the launch refuses the flag: another kernel flag, a forced tile, the shape
-        return !(d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY)) && d->tile == 0 &&
+        return !(d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY)) && d->tile == 0 &&
                        yolo::splitk_supported(d)
                    ? yolo::splitk_workspace_bytes(d)
                    : 0;

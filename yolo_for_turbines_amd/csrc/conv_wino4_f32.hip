@@ -204,7 +204,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, kq = lane >> 4;
     // block map: 8 tile blocks (one per XCD) x all channel blocks per row, so the channel blocks of a tile block share an L2. The
-    // rows of the whole tile blocks come first; each row of 8 tail blocks then comes twice, once per half
+    // rows of the whole tile blocks come first; each row of 8 tail blocks then comes twice, once per half.
+    // (Measured at 13 x 13, 512 -> 1024, batch 32, where all 256 workgroups are halves and U4 is the larger operand: a map that gives
+    // an XCD 4 tile blocks x 4 channel blocks x both halves halves the launch's FETCH_SIZE and changes its time by less than the
+    // spread of the rounds, profiles/r08: not kept)
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int nt = q % p.n_nt, row = q / p.n_nt;
     const int wrows = (p.n_whole + 7) >> 3;
@@ -496,10 +499,18 @@ bool wino4_supported(const yolo_conv_desc* d) {
 // F(4x4) 252 / 222 / 196 us against F(2x2)'s best 415 / 330 / 270 at 104 x 104, 52 x 52, 26 x 26 (which pads to 28 x 28: 16 % of
 // the tiles' pixels wasted), 351 against 297 at 13 x 13 (padded to 16 x 16: 51 % wasted). So: maps of at least 26 x 26 pixels whose
 // padding to whole 4 x 4 tiles adds at most a fifth.
+// That 13 x 13 figure was 128 whole workgroups on 256 CUs, each launch transforming its filters. A caller that brings the filters
+// finished (YOLO_FLAG_FILTERS_APPENDED) gets a launch without filter blocks, and wino4_whole_blocks cuts it into one round of half
+// workgroups: 512 -> 1024 at batch 32 (profiles/r08/conv_bench_c13.txt, medians of 7 rounds of 20) 219 / 223 us (with residual)
+// against F(2x2)'s best 277 / 290 at 13 x 13, 339 / 349 against 555 / 580 at 19 x 19 (13 whole tile blocks: 208 workgroups). With
+// the flag the rule admits those two shapes too, each on its own measurement; every other small map stays on F(2x2).
+bool wino4_small_channels(const yolo_conv_desc* d) { return d->cin == 512 && d->cout == 1024; }
+
 bool wino4_eligible(const yolo_conv_desc* d) {
     if (switches().no_winograd || !wino_eligible(d) || !wino4_supported(d)) return false;
     const long long area = (long long)d->h * d->w, padded = 16LL * ((d->h + 3) / 4) * ((d->w + 3) / 4);
-    return area >= 26 * 26 && 5 * padded <= 6 * area;
+    if (area >= 26 * 26 && 5 * padded <= 6 * area) return true;
+    return (d->flags & YOLO_FLAG_FILTERS_APPENDED) && wino4_small_channels(d) && d->h == d->w && (d->h == 13 || d->h == 19);
 }
 
 size_t wino4_workspace_bytes(const yolo_conv_desc* d) {
@@ -548,6 +559,11 @@ static int wino4_filter_blocks(const Wino4XArgs& xa) {
 size_t wino4_filter_bytes(const yolo_conv_desc* d) {
     if (!wino4_supported(d)) return 0;
     return (size_t)36 * round_up(d->cin / 4, 2) * round_up(d->cout, 64) * 4 * sizeof(float);
+}
+
+// YOLO_FLAG_FILTERS_APPENDED: U4 lies in the packed buffer itself, behind the packed weights
+size_t wino4_appended_offset(const yolo_conv_desc* d) {
+    return (yolo_packed_weight_bytes(d->cout, d->cin, d->ksize, YOLO_F32) + 15) & ~(size_t)15;
 }
 
 // w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad); U4_ready: the
@@ -600,11 +616,24 @@ extern "C" {
 
 size_t yolo_wino4_filter_bytes(const yolo_conv_desc* d) { return d ? yolo::wino4_filter_bytes(d) : 0; }
 
+size_t yolo_wino4_appended_bytes(const yolo_conv_desc* d) {
+    return d && yolo::wino4_supported(d) ? yolo::wino4_appended_offset(d) + yolo::wino4_filter_bytes(d) : 0;
+}
+
+int yolo_wino4_appended_wanted(const yolo_conv_desc* d) {
+    return d && !yolo::switches().no_winograd && yolo::wino4_supported(d) && yolo::wino4_small_channels(d);
+}
+
 int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, void* stream) {
     using namespace yolo;
     if (!d || !w_packed || !U4) return fail(YOLO_ERR_ARG, "wino4 filters: null pointer");
     if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filters: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
     if ((size_t)U4 & 15) return fail(YOLO_ERR_ARG, "wino4 filters: U4 must be 16-byte aligned");
+    // in place (U4 behind the packed weights of the same buffer, YOLO_FLAG_FILTERS_APPENDED) is fine: only the row-major section at
+    // the start of w_packed is read. U4 may not begin inside that section
+    const char *rm = (const char*)w_packed, *u = (const char*)U4;
+    const size_t rm_bytes = (size_t)d->cout * kpad_of(d->cin, 3) * sizeof(float);
+    if (u < rm + rm_bytes && rm < u + wino4_filter_bytes(d)) return fail(YOLO_ERR_ARG, "wino4 filters: U4 overlaps the weights it is made from");
     Wino4XArgs xa{};
     wino4_filter_args(xa, d, (const float*)w_packed, (float*)U4);
     hipLaunchKernelGGL(wino4_filters_f32, dim3((unsigned)wino4_filter_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);

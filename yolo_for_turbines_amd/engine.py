@@ -202,6 +202,13 @@ class PackedBlock:
             d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=cv.kernel_size[0], stride=cv.stride[0],
                            x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=self.code)
             room = lib.yolo_split3_weight_bytes(C.byref(d))
+        # ... and the fp32 3x3 stride-1 blocks whose small maps run as Winograd F(4x4) once their filters lie behind the packed
+        # weights (want_u4a; the library names them by their channel counts: the seven 512 -> 1024 blocks of YOLOv3, 75.5 MB each)
+        elif dtype == "fp32" and n and cv.kernel_size[0] == 3 and cv.stride[0] == 1:
+            d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=3, stride=1,
+                           x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=self.code)
+            if lib.yolo_wino4_appended_wanted(C.byref(d)):
+                room = lib.yolo_wino4_appended_bytes(C.byref(d))
         self.w = torch.empty(max(n, room, 16), dtype=torch.uint8, device=device)
         self.scale = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.shift = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
@@ -222,6 +229,11 @@ class PackedBlock:
         self.s3 = None
         self.s3_desc = None
         self.s3_stamp = None
+        # The same filters U4 behind the packed weights in w (yolo_wino4_filters in place), for the eval plans whose launch of this
+        # block carries YOLO_FLAG_FILTERS_APPENDED: a view of w once a plan wants them; they follow the stamp like u4 and s3.
+        self.u4a = None
+        self.u4a_desc = None
+        self.u4a_stamp = None
         self.fold_stamp = None            # same for the tensors behind scale / shift; None = not folded
         self.folded = False
 
@@ -293,6 +305,23 @@ class PackedBlock:
         L.check(L.lib().yolo_split3_weights(C.byref(self.s3_desc), self.w.data_ptr(), self.w.data_ptr(), stream), "yolo_split3_weights")
         self.s3_stamp = self.stamp
 
+    def want_u4a(self, desc):
+        """An eval plan runs this block as Winograd F(4x4) with YOLO_FLAG_FILTERS_APPENDED: the filters are made in place, behind
+        the packed weights in ``w`` (the launch keeps its ``w_packed``). None: ``w`` has no room for them."""
+        if self.u4a is None:
+            n = L.lib().yolo_wino4_appended_bytes(C.byref(desc))
+            if n == 0 or n > self.w.numel():
+                return None
+            self.u4a_desc = L.ConvDesc.from_buffer_copy(desc)
+            self.u4a = self.w[n - L.lib().yolo_wino4_filter_bytes(C.byref(desc)):n]
+            self.u4a_stamp = None
+        return self.u4a
+
+    def refresh_u4a(self, stream):
+        """U4 behind the packed weights as they are now (call after the pack on the same stream)."""
+        L.check(L.lib().yolo_wino4_filters(C.byref(self.u4a_desc), self.w.data_ptr(), self.u4a.data_ptr(), stream), "yolo_wino4_filters")
+        self.u4a_stamp = self.stamp
+
     def refresh(self, block, stream, fold_bn=True, conv_packed=False, pack=True):
         """fold_bn=False (training: batch statistics are used, not the running ones) skips the BN fold.
         conv_packed: the conv weights were already written by a batched pack (ModelState.refresh_weights).
@@ -305,6 +334,7 @@ class PackedBlock:
         if pack:
             self.u4_stamp = None          # (the training path re-packs every step and never reads U4: it is re-made on the eval side)
             self.s3_stamp = None          # (likewise the bf16 planes)
+            self.u4a_stamp = None         # (and the filters behind the packed weights)
             if self.packs_conv and not conv_packed:
                 L.check(lib.yolo_pack_weights(w.data_ptr(), self.w.data_ptr(), cv.out_channels, cv.in_channels,
                                               cv.kernel_size[0], self.code, stream), "yolo_pack_weights")
@@ -416,6 +446,12 @@ class Plan:
                     and (d.tile == 15 or L.lib().yolo_conv_pick_tile(C.byref(d)) == 15)):
                 e.w_packed = pk.want_u4(d).data_ptr()
                 d.flags |= L.FLAG_FILTERS_READY
+            # ... so do the small maps that measured faster as F(4x4) once nothing transforms their filters per launch: the
+            # library picks tile 15 for them when the filters lie behind the packed weights, where the block keeps room for them
+            # (ModelState.wino4_small = False keeps F(2x2))
+            elif (dtype == "fp32" and state.wino4_small and not state.latency and i >= self.first and not tile_override
+                    and op["k"] == 3 and op["s"] == 1 and self._picks_wino4_appended(d) and pk.want_u4a(d) is not None):
+                d.flags |= L.FLAG_FILTERS_APPENDED
             # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
             # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
             elif (dtype == "fp32" and state.split3 and i >= self.first and not tile_override
@@ -441,6 +477,13 @@ class Plan:
         self.blocks0 = self.blocks[:1]    # the stem block alone (its own freshness check, see ModelState.forward)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.dropped = False
+
+    @staticmethod
+    def _picks_wino4_appended(d):
+        """Does the library run this launch as tile 15 once YOLO_FLAG_FILTERS_APPENDED is set?"""
+        probe = L.ConvDesc.from_buffer_copy(d)
+        probe.flags |= L.FLAG_FILTERS_APPENDED
+        return L.lib().yolo_conv_pick_tile(C.byref(probe)) == 15 and L.lib().yolo_conv_workspace_bytes(C.byref(probe)) > 0
 
     def load_input(self, xin, stream):
         """NCHW fp32 input -> first activation: stem kernel, or the NHWC boundary copy."""
@@ -489,6 +532,11 @@ class ModelState:
         # weights split into their bf16 planes once per weight update (YOLO_FLAG_SPLIT_WEIGHTS_READY, PackedBlock.want_s3);
         # "inflight": the launches of True, every one splitting the packed weights itself (same bits; A/B runs).
         self.split3 = True
+        # fp32 inference: the 3x3 stride-1 layers on small maps that measured faster as Winograd F(4x4) with their filters made
+        # once run that way (YOLO_FLAG_FILTERS_APPENDED; the 13 x 13 and 19 x 19 layers 512 -> 1024). False: plans made from then
+        # on keep F(2x2) there (A/B runs; the rule cannot look at the batch, and a small batch fills fewer CUs with half
+        # workgroups than with F(2x2) blocks: DESIGN 4.12).
+        self.wino4_small = True
         # fp32 inference at small batches (single-image detection, demo.py:41-42): True = eval plans made from then on run the
         # layers that measured faster that way at batch 1 cut along K (YOLO_FLAG_SPLIT_K: fp32 accuracy, other bits; the plan's
         # workspace grows linearly with the batch). "all": every layer the library can run that way (A/B runs, tests).
@@ -520,8 +568,11 @@ class ModelState:
         return plan
 
     def __getstate__(self):
-        return {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3,
-                "latency": self.latency}
+        st = {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3,
+              "latency": self.latency}
+        if not self.wino4_small:          # (an A/B setting: written only where it is not the default)
+            st["wino4_small"] = False
+        return st
 
     def __setstate__(self, st):
         self.__init__()
@@ -529,6 +580,7 @@ class ModelState:
         self.autocast_heads = st.get("autocast_heads", True)
         self.split3 = st.get("split3", True)
         self.latency = st.get("latency", False)
+        self.wino4_small = st.get("wino4_small", True)
 
     def __deepcopy__(self, memo):
         new = ModelState()
@@ -536,6 +588,7 @@ class ModelState:
         new.autocast_heads = self.autocast_heads
         new.split3 = self.split3
         new.latency = self.latency
+        new.wino4_small = self.wino4_small
         return new
 
     def head_dtype(self):
@@ -552,6 +605,7 @@ class ModelState:
                 pk.stamp = None
                 pk.u4_stamp = None
                 pk.s3_stamp = None
+                pk.u4a_stamp = None
                 pk.fold_stamp = None
                 pk.folded = False
         if drop_plans:
@@ -634,6 +688,8 @@ class ModelState:
                     pk.refresh_u4(stream)
                 if pk.s3 is not None and (pk.s3_stamp is None or pk.s3_stamp != pk.stamp):
                     pk.refresh_s3(stream)
+                if pk.u4a is not None and (pk.u4a_stamp is None or pk.u4a_stamp != pk.stamp):
+                    pk.refresh_u4a(stream)
 
     def mark_unfolded(self, blocks):
         """The BatchNorm running statistics of ``blocks`` were just written by a kernel (train-mode forward): every folded
