@@ -459,6 +459,27 @@ int yolo_loss_fwd_hw(const float* pred, const int64_t* strides5, const float* ta
                      int nc, float* losses4, float* counts2, void* workspace, size_t workspace_bytes, void* stream);
 int yolo_loss_bwd_hw(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
                      int nc, const float* counts2, const float* grad_losses4, float* dpred, void* stream);
+/* The same three launches with other terms (NOT the reference's; csrc/loss_iou.hip). Decoded boxes in cell / grid
+ * units: b = (sig(p0), sig(p1), exp(p2) aw, exp(p3) ah), g = t0..3; IoU as above (detached wherever it is a target).
+ *   box_kind   MSE: the reference's term. GIOU / DIOU / CIOU: mean over the object cells of 1 - XIoU(b, g), gradient into p0..3
+ *              (CIoU's alpha is a constant of the gradient)
+ *   obj_kind   MSE: (p4 - IoU)^2. BCE: BCEWithLogits(p4, IoU)
+ *   focal_gamma >= 0: no-object cells cost sig(p4)^gamma * softplus(p4); 0 is the reference's BCE
+ *   label_smoothing in [0, 1): torch.nn.CrossEntropyLoss(label_smoothing=...)
+ *   lambda_*   the weights of losses4 = [box, object, noobj, class] (the reference: 5, 1, 0.5, 1), finite
+ * Anything else: YOLO_ERR_ARG before a launch. Workspace, counts2, determinism and graph capture as for yolo_loss_fwd_hw. */
+enum { YOLO_LOSS_BOX_MSE = 0, YOLO_LOSS_BOX_GIOU = 1, YOLO_LOSS_BOX_DIOU = 2, YOLO_LOSS_BOX_CIOU = 3 };
+enum { YOLO_LOSS_OBJ_MSE = 0, YOLO_LOSS_OBJ_BCE = 1 };
+typedef struct yolo_loss_opts {
+    int box_kind, obj_kind;
+    float focal_gamma, label_smoothing;
+    float lambda_box, lambda_obj, lambda_noobj, lambda_class;
+} yolo_loss_opts;                                            /* 32 bytes */
+int yolo_loss_fwd_opts(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                       int nc, float* losses4, float* counts2, void* workspace, size_t workspace_bytes, const yolo_loss_opts* opts,
+                       void* stream);
+int yolo_loss_bwd_opts(const float* pred, const int64_t* strides5, const float* target, const float* anchors_3x2, int b, int gh, int gw,
+                       int nc, const float* counts2, const float* grad_losses4, float* dpred, const yolo_loss_opts* opts, void* stream);
 
 /* ---- optimizer step (code/train.py:171-172 torch.optim.SGD(model.parameters(), lr, momentum, weight_decay); :68 step) ---- */
 /* One launch over every parameter tensor; the same bits as torch.optim.SGD's default implementation (each of its passes

@@ -17,6 +17,8 @@ OUT_NHWC, OUT_UPSAMPLE2X, OUT_HEAD = 0, 1, 2
 FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY, FLAG_SPLIT_BF16, FLAG_SPLIT_WEIGHTS_READY = 1, 2, 4, 8, 16
 FLAG_SPLIT_K = 32
 FLAG_FILTERS_APPENDED = 64
+LOSS_BOX_KINDS = {"mse": 0, "giou": 1, "diou": 2, "ciou": 3}          # YOLO_LOSS_BOX_* / YOLO_LOSS_OBJ_* of the header
+LOSS_OBJ_KINDS = {"mse": 0, "bce": 1}
 
 
 class PackItem(C.Structure):
@@ -34,6 +36,12 @@ class ConvDesc(C.Structure):
 class ConvOp(C.Structure):
     _fields_ = [("d", ConvDesc)] + [(n, C.c_uint64) for n in ("x", "w_packed", "scale", "shift", "residual", "y",
                                                               "workspace", "workspace_bytes")]
+
+
+class LossOpts(C.Structure):
+    """`yolo_loss_opts` (include/yolo_mi355x.h): the terms of yolo_loss_fwd_opts / yolo_loss_bwd_opts."""
+    _fields_ = [("box_kind", C.c_int), ("obj_kind", C.c_int), ("focal_gamma", C.c_float), ("label_smoothing", C.c_float),
+                ("lambda_box", C.c_float), ("lambda_obj", C.c_float), ("lambda_noobj", C.c_float), ("lambda_class", C.c_float)]
 
 
 CALL_MAX_ARGS = 24
@@ -180,6 +188,10 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_loss_bwd_hw": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_loss_fwd_opts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(LossOpts), C.c_void_p]),
+    "yolo_loss_bwd_opts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LossOpts), C.c_void_p]),
     "yolo_loss_fwd": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_loss_bwd": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -72,12 +72,102 @@ class _FusedLossFn(torch.autograd.Function):
         return dpred, None, None
 
 
+class _FusedLossOptsFn(torch.autograd.Function):
+    """The same three launches through ``yolo_loss_fwd_opts`` / ``yolo_loss_bwd_opts`` (`csrc/loss_iou.hip`); ``opts`` is a
+    `_lib.LossOpts`, read by the host when the kernels are launched."""
+
+    @staticmethod
+    def forward(ctx, pred, target, anchors, opts):
+        import ctypes as C
+        from . import _lib as L
+        lib = L.lib()
+        B, A, gh, gw, D = pred.shape
+        dev = pred.device
+        with torch.cuda.device(dev):
+            out = torch.empty(4, dtype=torch.float32, device=dev)
+            counts = torch.empty(2, dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.yolo_loss_workspace_bytes_hw(B, gh, gw), dtype=torch.uint8, device=dev)
+            strides = (C.c_int64 * 5)(*pred.stride())
+            L.check(lib.yolo_loss_fwd_opts(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, gh, gw, D - 5, out.data_ptr(),
+                                           counts.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(opts), L.current_stream()),
+                    "yolo_loss_fwd_opts")
+        ctx.save_for_backward(pred, target, anchors, counts)
+        ctx.opts = opts
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        import ctypes as C
+        from . import _lib as L
+        pred, target, anchors, counts = ctx.saved_tensors
+        B, A, gh, gw, D = pred.shape
+        with torch.cuda.device(pred.device):
+            dpred = torch.empty((B, A, gh, gw, D), dtype=torch.float32, device=pred.device)
+            gout = gout.float().contiguous()
+            strides = (C.c_int64 * 5)(*pred.stride())
+            L.check(L.lib().yolo_loss_bwd_opts(pred.data_ptr(), strides, target.data_ptr(), anchors.data_ptr(), B, gh, gw, D - 5,
+                                               counts.data_ptr(), gout.data_ptr(), dpred.data_ptr(), C.byref(ctx.opts), L.current_stream()),
+                    "yolo_loss_bwd_opts")
+        return dpred, None, None, None
+
+
+_BOX_LOSSES = ("mse", "giou", "diou", "ciou")
+_OBJ_LOSSES = ("mse", "bce")
+_DEFAULT_LAMBDAS = (5.0, 1.0, 0.5, 1.0)                       # loss.py:24-27
+
+
 class FusedYOLOLoss(nn.Module):
     """Same values and gradients as :class:`YOLOLoss` (reference `loss.py:29-81`) from three fused HIP
     kernels per scale instead of ~35 boolean-mask / reduction launches: no data-dependent shapes, no host
     sync, deterministic sums — so a whole fine-tune step can be captured in a HIP graph
     (``tools/train_bench.py --graph``). Same call signature and return value; it does NOT mutate
-    ``predictions`` / ``targets`` (the reference overwrites ``predictions[...,1:3]`` and ``targets[...,2:4]``)."""
+    ``predictions`` / ``targets`` (the reference overwrites ``predictions[...,1:3]`` and ``targets[...,2:4]``).
+
+    Every argument at its default is the reference's loss, through the same kernels as before. Anything else is NOT
+    the reference's loss (`csrc/loss_iou.hip`); it keeps the call signature, the four returned parts and the
+    graph capture:
+
+    * ``box_loss``: ``"mse"`` (the reference), or ``"giou"`` / ``"diou"`` / ``"ciou"``: the mean over the object cells of
+      ``1 - XIoU`` between the decoded box ``(sig(p0), sig(p1), exp(p2) aw, exp(p3) ah)`` and the target
+    * ``obj_loss``: ``"mse"`` (the reference: ``(p4 - IoU)^2``) or ``"bce"`` (``BCEWithLogits(p4, IoU)``), IoU detached
+    * ``focal_gamma`` >= 0: no-object cells cost ``sig(p4)^gamma * softplus(p4)``; 0 is the reference's BCE
+    * ``label_smoothing`` in [0, 1): as ``torch.nn.CrossEntropyLoss(label_smoothing=...)``
+    * ``lambdas``: the weights ``(box, obj, noobj, class)`` of the four parts
+    """
+
+    def __init__(self, box_loss="mse", obj_loss="mse", focal_gamma=0.0, label_smoothing=0.0, lambdas=_DEFAULT_LAMBDAS):
+        super().__init__()
+        import math
+        if box_loss not in _BOX_LOSSES:
+            raise ValueError(f"box_loss must be one of {_BOX_LOSSES}, not {box_loss!r}")
+        if obj_loss not in _OBJ_LOSSES:
+            raise ValueError(f"obj_loss must be one of {_OBJ_LOSSES}, not {obj_loss!r}")
+        try:
+            focal_gamma, label_smoothing = float(focal_gamma), float(label_smoothing)
+            lambdas = tuple(float(v) for v in lambdas)
+        except TypeError as e:
+            raise ValueError(f"focal_gamma, label_smoothing and the four lambdas must be numbers: {e}") from e
+        if not (math.isfinite(focal_gamma) and focal_gamma >= 0.0):
+            raise ValueError(f"focal_gamma must be a finite number >= 0, not {focal_gamma}")
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1), not {label_smoothing}")
+        if len(lambdas) != 4 or not all(math.isfinite(v) for v in lambdas):
+            raise ValueError(f"lambdas must be four finite numbers (box, obj, noobj, class), not {lambdas}")
+        self.box_loss, self.obj_loss, self.focal_gamma, self.label_smoothing, self.lambdas = (
+            box_loss, obj_loss, focal_gamma, label_smoothing, lambdas)
+        self._default = (box_loss, obj_loss, focal_gamma, label_smoothing, lambdas) == ("mse", "mse", 0.0, 0.0, _DEFAULT_LAMBDAS)
+        self._opts = None
+
+    def extra_repr(self):
+        return (f"box_loss={self.box_loss!r}, obj_loss={self.obj_loss!r}, focal_gamma={self.focal_gamma}, "
+                f"label_smoothing={self.label_smoothing}, lambdas={self.lambdas}")
+
+    def _c_opts(self):
+        if self._opts is None:
+            from . import _lib as L
+            self._opts = L.LossOpts(L.LOSS_BOX_KINDS[self.box_loss], L.LOSS_OBJ_KINDS[self.obj_loss], self.focal_gamma,
+                                    self.label_smoothing, *self.lambdas)
+        return self._opts
 
     def forward(self, predictions, targets, anchors):
         if not predictions.is_cuda:
@@ -92,7 +182,7 @@ class FusedYOLOLoss(nn.Module):
         if t.dtype != torch.float32 or not t.is_contiguous():
             t = t.float().contiguous()
         a = anchors.detach().reshape(3, 2).to(device=predictions.device, dtype=torch.float32).contiguous()
-        out = _FusedLossFn.apply(predictions, t, a)
+        out = _FusedLossFn.apply(predictions, t, a) if self._default else _FusedLossOptsFn.apply(predictions, t, a, self._c_opts())
         # ONE backward node for the four parts (unbind -> stack): indexing out[0] .. out[3] gave four SelectBackward nodes, each a
         # zero-fill + a 4-byte blit copy + an accumulate - 36 tiny launches per step over the three scales
         return list(out.unbind(0))
