@@ -529,6 +529,36 @@ int yolo_sgd_step_amp_ema(const void* items_dev, int n_items, const int32_t* chu
                           const void* ema_state_dev, int nesterov, int maximize, void* stream);
 int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chunks, void* ema_state_dev, const float* found_inf_dev,
                     int advance, void* stream);
+/* Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type, error_if_nonfinite=False)
+ * between the unscale and the step, over the same tables as the step.
+ *   total_norm = the norm of every gradient of every group (items with g != NULL), after the unscale g * (float)(1.0 /
+ *                (double)*grad_scale_dev) (a rounding of its own; grad_scale_dev == NULL: none), before maximize / weight decay.
+ *                YOLO_NORM_L2: squares summed in fp64 in a fixed order, square root, one rounding to fp32. YOLO_NORM_INF: the
+ *                largest |g|, NaN-propagating.
+ *   coef       = min(fl(fl(1 / fl(total_norm + 1e-6f)) * max_norm), 1) in fp32, the reciprocal correctly rounded: the bits of
+ *                torch.clamp(max_norm / (total_norm + 1e-6), max=1.0).
+ * The yolo_clip_state lives in device memory, 16-byte aligned. max_norm is the caller's to write and is read when the
+ * finalize kernel runs, never passed by value: a launch captured in a HIP graph follows a changed value. The other three
+ * words are written by yolo_clip_finalize.
+ * yolo_clip_norm_partials: one block per chunk writes one double to partials_dev[chunk] (n_chunks slots, 8-byte aligned; a
+ *   chunk of an item without a gradient writes 0). found_inf_dev != NULL: the same read of the gradients also does the check of
+ *   yolo_sgd_check_finite into it (clear as there). No atomics: the same bits every run.
+ * yolo_clip_finalize: one block reduces n_partials doubles (every group's, laid out one after the other) in a fixed order and
+ *   writes total_norm, coef and norm_type. n_partials == 0: total_norm = 0.
+ * yolo_sgd_step_clip: the update of yolo_sgd_step_hp with g * coef (a rounding of its own, applied also when coef == 1) directly
+ *   after the unscale. Every option of the other entry points is a pointer that may be NULL: grad_scale_dev, found_inf_dev
+ *   (set: nothing is touched), written_dev (as in yolo_sgd_step_amp, needs found_inf_dev; NULL: the sign of n says "first
+ *   step"), shadows_dev + ema_state_dev (as in the *_ema entry points; both or neither).
+ * yolo_clip_scale_grads: g *= coef in place for every item with a gradient (p and buf of the items are not looked at). */
+enum { YOLO_NORM_L2 = 0, YOLO_NORM_INF = 1 };
+typedef struct yolo_clip_state { float max_norm; float total_norm; float coef; int32_t norm_type; } yolo_clip_state;
+int yolo_clip_norm_partials(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* grad_scale_dev, int norm_type,
+                            double* partials_dev, float* found_inf_dev, int clear, void* stream);
+int yolo_clip_finalize(const double* partials_dev, int n_partials, int norm_type, void* clip_state_dev, void* stream);
+int yolo_sgd_step_clip(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                       const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
+                       const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream);
+int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const void* clip_state_dev, void* stream);
 
 /* ---- post-processing ------------------------------------------------------------------- */
 /* Replaces cells_to_boxes (utils.py:86-148) for one scale.

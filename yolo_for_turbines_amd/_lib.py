@@ -44,6 +44,13 @@ class LossOpts(C.Structure):
                 ("lambda_box", C.c_float), ("lambda_obj", C.c_float), ("lambda_noobj", C.c_float), ("lambda_class", C.c_float)]
 
 
+class ClipState(C.Structure):
+    """`yolo_clip_state` (include/yolo_mi355x.h): four 32-bit words in device memory; the host writes max_norm only."""
+    _fields_ = [("max_norm", C.c_float), ("total_norm", C.c_float), ("coef", C.c_float), ("norm_type", C.c_int32)]
+
+
+NORM_KINDS = {2.0: 0, float("inf"): 1}                                 # YOLO_NORM_L2 / YOLO_NORM_INF of the header
+
 CALL_MAX_ARGS = 24
 
 
@@ -98,6 +105,11 @@ _SIGS = {
     "yolo_sgd_step_amp_ema": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "yolo_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "yolo_clip_norm_partials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "yolo_clip_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "yolo_sgd_step_clip": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_clip_scale_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_stem_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "yolo_stem_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_stem_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -26,8 +26,9 @@ class GradScaler(torch.amp.GradScaler):
         scaler.update()
 
     After a native ``step`` the ``.grad`` tensors still hold the SCALED gradients (PyTorch's ``step`` leaves them unscaled):
-    the unscale happens in registers and is not written back. Call ``unscale_(optimizer)`` first, as for clipping, to get
-    unscaled gradients in memory; ``step`` then uses them as they are. A skipped step still skips on the device, so
+    the unscale happens in registers and is not written back. Call ``unscale_(optimizer)`` first to get unscaled gradients
+    in memory; ``step`` then uses them as they are. Clipping needs neither: ``yt.SGD(max_grad_norm=...)`` takes the norm in
+    the same read as the non-finite check and clips in registers. A skipped step still skips on the device, so
     ``step`` always returns ``None`` for a ``yt.SGD`` and never reports whether it was applied.
     """
 

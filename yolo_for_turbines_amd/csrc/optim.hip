@@ -61,15 +61,21 @@ __device__ __forceinline__ void ema_coeffs(const EmaState* __restrict__ st, floa
 __device__ __forceinline__ float ema_one(float e, float p, float d, float omd) { return __builtin_fmaf(omd, p, e * d); }
 
 // EMA: ema (the shadow of p) moves towards the NEW p with the coefficients {ema_d, ema_omd}
-template <bool VEC, bool EMA = false>
+// CLIP: g * coef directly after the unscale, a rounding of its own like it (the grad.mul_(clip_coef) pass of clip_grad_norm_),
+// applied whatever coef is
+template <bool VEC, bool EMA = false, bool CLIP = false>
 __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ b, long long i0,
                                            int cnt, bool first, float neg_lr, float momentum, float omd, float wd, int nesterov,
                                            int maximize, float inv_scale = 1.0f, float* __restrict__ ema = nullptr, float ema_d = 0.f,
-                                           float ema_omd = 0.f) {
+                                           float ema_omd = 0.f, float coef = 1.0f) {
     auto one = [&](float pv, float gv, float bv, float& pn, float& bn) {
         if (inv_scale != 1.0f) {                         // the unscale pass: a rounding of its own, never fused into what follows
 #pragma clang fp contract(off)
             gv = gv * inv_scale;
+        }
+        if (CLIP) {
+#pragma clang fp contract(off)
+            gv = gv * coef;
         }
         if (maximize) gv = -gv;
         if (wd != 0.f) gv = __builtin_fmaf(wd, pv, gv);
@@ -296,6 +302,193 @@ __global__ void ema_advance_kernel(EmaState* __restrict__ state, const float* __
     state->updates += 1;
 }
 
+// ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_ between the unscale and the step) ----
+// The norm is a reduction over the chunk table, the coefficient a device word, the clip one more multiply in sgd_update.
+//   partials: one block per chunk, each element unscaled in fp32 like the step does it, squared and summed in fp64 (the square of
+//             3e19 overflows fp32 and the square of 1e-30 vanishes in it; 6.2e7 fp64 terms err by 7e-9 relative), per thread in
+//             a fixed order, then over the block in a fixed tree: one double per chunk in a slot that chunk owns, no atomics,
+//             the same bits every run. CHECK: the non-finite test of sgd_check_finite_kernel from the same registers, so a
+//             loss-scaled step reads its gradients once for both. INF: the largest |g| in place of the sum, NaN-propagating.
+//   finalize: one block over every group's partials in a fixed order, sqrt, one rounding to fp32, then
+//             coef = min(fl(fl(1 / fl(total + 1e-6f)) * max_norm), 1): torch turns `max_norm / tensor` into reciprocal() * max_norm.
+struct ClipState { float max_norm; float total_norm; float coef; int norm_type; };
+static_assert(sizeof(ClipState) == 16, "matches yolo_clip_state in the header");
+
+template <bool INF>
+__device__ __forceinline__ double clip_combine(double a, double b) {
+    if (INF) return (b != b || b > a) ? b : a;           // a NaN on either side stays
+    return a + b;
+}
+
+// every thread's value -> thread 0, in the same order every run: down the wave, then the waves left to right
+template <bool INF, int WAVES>
+__device__ __forceinline__ double clip_block_reduce(double acc) {
+    __shared__ double per_wave[WAVES];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc = clip_combine<INF>(acc, __shfl_down(acc, off));
+    if ((threadIdx.x & 63) == 0) per_wave[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double all = per_wave[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) all = clip_combine<INF>(all, per_wave[w]);
+    return all;
+}
+
+template <bool CHECK, bool INF>
+__global__ __launch_bounds__(256) void clip_norm_partials_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
+                                                                 const float* __restrict__ grad_scale, double* __restrict__ partials,
+                                                                 float* __restrict__ found_inf) {
+    const int2 ck = chunks[blockIdx.x];
+    const SgdItem it = items[ck.x];
+    if (it.g == nullptr) {                               // uniform over the block; the slot is still this chunk's to write
+        if (threadIdx.x == 0) partials[blockIdx.x] = 0.0;
+        return;
+    }
+    const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
+    const long long n = it.n < 0 ? -it.n : it.n;
+    const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(it.g);
+    const bool aligned = (((size_t)g) & 15) == 0;
+    constexpr unsigned EXP = 0x7f800000u;
+    int bad = 0;
+    double acc = 0.0;
+    auto take = [&](unsigned bits) {
+        if (CHECK) bad |= (bits & EXP) == EXP;           // on the value as it lies in memory, like the check launch
+        float v = __uint_as_float(bits);
+        if (inv_scale != 1.0f) {
+#pragma clang fp contract(off)
+            v = v * inv_scale;
+        }
+        if (INF) acc = clip_combine<true>(acc, (double)__builtin_fabsf(v));
+        else { const double d = (double)v; acc = __builtin_fma(d, d, acc); }
+    };
+    const long long base = (long long)ck.y + threadIdx.x * 4;
+    if (aligned && (long long)ck.y + SGD_CHUNK <= n) {   // full chunk: four independent 16-byte loads in flight
+        u32x4 v[SGD_CHUNK / 1024];
+#pragma unroll
+        for (int r = 0; r < SGD_CHUNK / 1024; ++r) v[r] = *reinterpret_cast<const u32x4*>(g + base + r * 1024);
+#pragma unroll
+        for (int r = 0; r < SGD_CHUNK / 1024; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) take(v[r][e]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
+            const long long i0 = base + r * 1024;
+            if (i0 >= n) break;
+            const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+            if (aligned && cnt == 4) {
+                const u32x4 v = *reinterpret_cast<const u32x4*>(g + i0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) take(v[e]);
+            } else {
+                for (int e = 0; e < cnt; ++e) take(g[i0 + e]);
+            }
+        }
+    }
+    const double sum = clip_block_reduce<INF, 4>(acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+    if (CHECK) {
+        if (__syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.0f;
+    }
+}
+
+// One block of FIN_THREADS. A thread takes partials t, t + FIN_THREADS, ... in that order, FIN_BATCH independent loads in flight
+// at a time (one dependent load after the other made this launch cost as much as the pass over the gradients). Past the end a
+// thread adds 0, the identity of both the sum of squares and the maximum of magnitudes.
+constexpr int FIN_THREADS = 1024, FIN_BATCH = 8;
+
+template <bool INF>
+__global__ __launch_bounds__(FIN_THREADS) void clip_finalize_kernel(const double* __restrict__ partials, int n, ClipState* __restrict__ state) {
+    double acc = 0.0;
+    for (int i0 = 0; i0 < n; i0 += FIN_THREADS * FIN_BATCH) {
+        double v[FIN_BATCH];
+#pragma unroll
+        for (int k = 0; k < FIN_BATCH; ++k) {
+            const int i = i0 + k * FIN_THREADS + (int)threadIdx.x;
+            v[k] = i < n ? partials[i] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < FIN_BATCH; ++k) acc = clip_combine<INF>(acc, v[k]);
+    }
+    const double all = clip_block_reduce<INF, FIN_THREADS / 64>(acc);
+    if (threadIdx.x != 0) return;
+    const float total = (float)(INF ? all : __builtin_sqrt(all));
+    const float max_norm = state->max_norm;              // read when the kernel runs: a captured step follows a changed value
+    const float recip = 1.0f / (total + 1e-6f);          // correctly rounded; the product below is rounded on its own
+    const float scaled = recip * max_norm;
+    state->total_norm = total;
+    state->coef = scaled > 1.0f ? 1.0f : scaled;         // clamp(max=1): a NaN stays a NaN
+    state->norm_type = INF ? 1 : 0;
+}
+
+// The step with every option behind a pointer that may be NULL: found_inf (set: nothing is touched), grad_scale (unscale in
+// registers), written (who decides "first step": these device words, or the sign of n), shadows + ema (the weight average in
+// the same launch; EMA says whether they are given). coef is the word the finalize launch left in the clip state.
+template <bool EMA>
+__global__ __launch_bounds__(256) void sgd_step_clip_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
+                                                            const float* __restrict__ hyper, const ClipState* __restrict__ clip,
+                                                            const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                                                            const int* __restrict__ written, float* const* __restrict__ shadows,
+                                                            const EmaState* __restrict__ state, int nesterov, int maximize) {
+    if (found_inf != nullptr && *found_inf != 0.f) return;
+    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
+    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
+    const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
+    const float coef = clip->coef;
+    const int2 ck = chunks[blockIdx.x];
+    const SgdItem it = items[ck.x];
+    if (it.g == nullptr) return;
+    const bool first = written != nullptr ? written[ck.x] == 0 : it.n < 0;
+    const long long n = it.n < 0 ? -it.n : it.n;
+    float* ema = nullptr;
+    float d = 0.f, e_omd = 0.f;
+    if (EMA) {
+        ema = shadows[ck.x];
+        ema_coeffs(state, d, e_omd);
+    }
+    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)ema)) & 15) == 0;
+#pragma unroll
+    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
+        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
+        if (i0 >= n) break;
+        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+        const bool vec = aligned && cnt == 4;
+        if (EMA && ema != nullptr) {
+            if (vec) sgd_update<true, true, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
+            else sgd_update<false, true, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
+        } else {
+            if (vec) sgd_update<true, false, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
+            else sgd_update<false, false, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
+        }
+    }
+}
+
+// g *= coef in place over a chunk table (clip_grad_norm_ for other optimizers): the item's p and buf are not looked at
+__global__ __launch_bounds__(256) void clip_scale_grads_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
+                                                               const ClipState* __restrict__ clip) {
+    const float coef = clip->coef;
+    const int2 ck = chunks[blockIdx.x];
+    const SgdItem it = items[ck.x];
+    if (it.g == nullptr) return;
+    const long long n = it.n < 0 ? -it.n : it.n;
+    float* __restrict__ g = const_cast<float*>(it.g);
+    const bool aligned = (((size_t)g) & 15) == 0;
+#pragma unroll
+    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
+        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
+        if (i0 >= n) break;
+        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+        if (aligned && cnt == 4) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(g + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] * coef;
+            *reinterpret_cast<f32x4*>(g + i0) = v;
+        } else {
+            for (int e = 0; e < cnt; ++e) g[i0 + e] = g[i0 + e] * coef;
+        }
+    }
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -380,6 +573,74 @@ int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chun
                            (const int2*)chunks_dev, (const EmaState*)ema_state_dev, found_inf_dev);
     if (advance) hipLaunchKernelGGL(ema_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (EmaState*)ema_state_dev, found_inf_dev);
     return check_launch("ema_update");
+}
+
+static bool clip_norm_known(int norm_type) { return norm_type == YOLO_NORM_L2 || norm_type == YOLO_NORM_INF; }
+
+int yolo_clip_norm_partials(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* grad_scale_dev, int norm_type,
+                            double* partials_dev, float* found_inf_dev, int clear, void* stream) {
+    if (n_chunks < 0 || !clip_norm_known(norm_type) || (n_chunks > 0 && (!items_dev || !chunks_dev || !partials_dev)) ||
+        ((size_t)partials_dev & 7))
+        return fail(YOLO_ERR_ARG, "clip_norm_partials: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (found_inf_dev && clear) hipLaunchKernelGGL(sgd_clear_flag_kernel, dim3(1), dim3(1), 0, st, found_inf_dev);
+    if (n_chunks == 0) return check_launch("clip_norm_partials");
+    const SgdItem* items = (const SgdItem*)items_dev;
+    const int2* chunks = (const int2*)chunks_dev;
+    const dim3 grid((unsigned)n_chunks), block(256);
+    const bool inf = norm_type == YOLO_NORM_INF;
+    if (found_inf_dev) {
+        if (inf) hipLaunchKernelGGL((clip_norm_partials_kernel<true, true>), grid, block, 0, st, items, chunks, grad_scale_dev, partials_dev, found_inf_dev);
+        else hipLaunchKernelGGL((clip_norm_partials_kernel<true, false>), grid, block, 0, st, items, chunks, grad_scale_dev, partials_dev, found_inf_dev);
+    } else {
+        if (inf) hipLaunchKernelGGL((clip_norm_partials_kernel<false, true>), grid, block, 0, st, items, chunks, grad_scale_dev, partials_dev, found_inf_dev);
+        else hipLaunchKernelGGL((clip_norm_partials_kernel<false, false>), grid, block, 0, st, items, chunks, grad_scale_dev, partials_dev, found_inf_dev);
+    }
+    return check_launch("clip_norm_partials");
+}
+
+int yolo_clip_finalize(const double* partials_dev, int n_partials, int norm_type, void* clip_state_dev, void* stream) {
+    if (!clip_state_dev || ((size_t)clip_state_dev & 15) || n_partials < 0 || !clip_norm_known(norm_type) || (n_partials > 0 && !partials_dev) ||
+        ((size_t)partials_dev & 7))
+        return fail(YOLO_ERR_ARG, "clip_finalize: bad arguments");
+    if (norm_type == YOLO_NORM_INF)
+        hipLaunchKernelGGL(clip_finalize_kernel<true>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, partials_dev, n_partials, (ClipState*)clip_state_dev);
+    else
+        hipLaunchKernelGGL(clip_finalize_kernel<false>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, partials_dev, n_partials, (ClipState*)clip_state_dev);
+    return check_launch("clip_finalize");
+}
+
+int yolo_sgd_step_clip(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                       const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
+                       const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream) {
+    if (!clip_state_dev || ((size_t)clip_state_dev & 15) || n_chunks < 0 || n_items < 0) return fail(YOLO_ERR_ARG, "sgd_step_clip: bad arguments");
+    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
+    // the "written" words are advanced by a launch that reads *found_inf; the average needs its table and its state together
+    if (!items_dev || !chunks_dev || !hyper4_dev || ((size_t)hyper4_dev & 15) || (written_dev && !found_inf_dev) ||
+        (!shadows_dev != !ema_state_dev) || ((size_t)ema_state_dev & 15))
+        return fail(YOLO_ERR_ARG, "sgd_step_clip: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (shadows_dev)
+        hipLaunchKernelGGL(sgd_step_clip_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, st, (const SgdItem*)items_dev, (const int2*)chunks_dev,
+                           hyper4_dev, (const ClipState*)clip_state_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
+                           (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
+    else
+        hipLaunchKernelGGL(sgd_step_clip_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, st, (const SgdItem*)items_dev, (const int2*)chunks_dev,
+                           hyper4_dev, (const ClipState*)clip_state_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
+                           (float* const*)nullptr, (const EmaState*)nullptr, nesterov, maximize);
+    if (written_dev)
+        hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, (const SgdItem*)items_dev, n_items,
+                           found_inf_dev, (int*)written_dev);
+    return check_launch("sgd_step_clip");
+}
+
+int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const void* clip_state_dev, void* stream) {
+    if (!clip_state_dev || ((size_t)clip_state_dev & 15) || n_chunks < 0 || (n_chunks > 0 && (!items_dev || !chunks_dev)))
+        return fail(YOLO_ERR_ARG, "clip_scale_grads: bad arguments");
+    if (n_chunks == 0) return YOLO_OK;
+    hipLaunchKernelGGL(clip_scale_grads_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
+                       (const int2*)chunks_dev, (const ClipState*)clip_state_dev);
+    return check_launch("clip_scale_grads");
 }
 
 }  // extern "C"

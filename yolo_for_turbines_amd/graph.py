@@ -105,6 +105,9 @@ class GraphedTrainStep:
             # once eagerly; inside the capture the buckets issue synchronous all-reduces on the capturing stream
             # (dist.GradBuckets.fire), and capture errors stay local to this thread
             kw = {"capture_error_mode": "thread_local"} if self._dp else {}
+            # Clipping (`yt.SGD(max_grad_norm=...)`): the number is device memory like the learning rate, but whether the step
+            # clips at all, and by which norm, decides WHICH launches were captured.
+            self._clip = self._clip_kind()
             with torch.cuda.graph(self.graph, **kw):
                 self.loss = self._step_body(zero=False)
         finally:
@@ -131,9 +134,19 @@ class GraphedTrainStep:
         keys = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize", "betas", "eps")
         return [tuple((k, g[k]) for k in keys if k in g and not isinstance(g[k], torch.Tensor)) for g in self.opt.param_groups]
 
+    def _clip_kind(self):
+        """None when the optimizer does not clip, else its norm type (what the captured launches depend on)."""
+        if getattr(self.opt, "max_grad_norm", None) is None:
+            return None
+        return float(self.opt.grad_norm_type)
+
     def __call__(self, x, targets):
         if tuple(x.shape) != tuple(self.x.shape):
             raise ValueError(f"this graph was captured for input shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
+        if self._clip_kind() != self._clip:
+            raise RuntimeError("GraphedTrainStep: the optimizer's gradient clipping was switched since the capture "
+                               f"(norm type {self._clip} -> {self._clip_kind()}, None = no clipping): the graph holds the launches of "
+                               "the capture; change max_grad_norm between numbers only, or capture a new GraphedTrainStep")
         if self._plan.dropped:
             raise RuntimeError("GraphedTrainStep: the model dropped its plans after this graph was captured (model.to(...) / "
                                ".float() / .half() move the parameters the graph points at): capture a new GraphedTrainStep")

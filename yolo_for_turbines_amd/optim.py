@@ -13,7 +13,14 @@ when `found_inf` is set: no host wait, capturable. Whether a momentum buffer has
 
 With a weight average attached (`ema.ModelEMA.attach`) the same launch also moves the average of every parameter it updates
 (the `_ema` entry points); without one the step is the launches it always was.
+
+With ``max_grad_norm`` set the step clips by global norm, `torch.nn.utils.clip_grad_norm_` between the unscale and the step,
+without writing a gradient: one launch per group leaves fp64 partial sums (and, under a loss scale, does the non-finite check
+from the same read), one block turns them into ``total_norm`` and the coefficient in a device struct, and the step multiplies
+by that word in registers. :func:`clip_grad_norm_` is the same reduction followed by an in-place scale, for other optimizers.
 """
+import math
+
 import torch
 
 from . import _lib as L
@@ -104,9 +111,64 @@ class _GroupTable:
         return slot[0], slot
 
 
+def _clip_args(max_norm, norm_type, who):
+    """None (no clipping) or (max_norm as a float, YOLO_NORM_* of the header); ValueError for anything else."""
+    if max_norm is None:
+        return None
+    m = float(max_norm)
+    if math.isnan(m) or m < 0.0:
+        raise ValueError(f"{who}: the maximal norm must be a number >= 0 (math.inf is allowed), got {max_norm}")
+    kind = L.NORM_KINDS.get(float(norm_type))
+    if kind is None:
+        raise ValueError(f"{who}: norm_type must be 2.0 or inf, got {norm_type}")
+    return m, kind
+
+
+class _ClipState:
+    """`yolo_clip_state` in device memory, the pinned ring ``max_norm`` travels through, and the fp64 workspace of the
+    partial sums. The struct never moves: ``grad_norm`` / ``clip_coef`` are views of it and a captured graph points at it."""
+
+    def __init__(self, dev):
+        self.words = torch.zeros(4, dtype=torch.float32, device=dev)        # {max_norm, total_norm, coef, norm_type}
+        self.words[2:3].fill_(1.0)
+        self.grad_norm, self.clip_coef = self.words[1], self.words[2]
+        self.max_host = None                                                # the value last pushed
+        self.ring = [[torch.zeros(1, dtype=torch.float32).pin_memory(), None] for _ in range(4)]
+        self.slot = 0
+        self.partials = None
+        self.retired = []                                                   # outgrown workspaces: a captured graph may point at one
+
+    def push(self, max_norm):
+        """Enqueue max_norm -> device on the current stream if it changed (the three words the device writes are left alone)."""
+        if max_norm == self.max_host:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: max_grad_norm changed inside a stream capture; call "
+                               "optimizer.sync_hyper() (GraphedTrainStep does) before the replay instead")
+        slot = self.ring[self.slot]
+        self.slot = (self.slot + 1) % len(self.ring)
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0][0] = max_norm
+        self.words[0:1].copy_(slot[0], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        self.max_host = max_norm
+
+    def workspace(self, n):
+        """One double per chunk of every group."""
+        if self.partials is None or self.partials.numel() < n:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step with max_grad_norm set before capturing")
+            if self.partials is not None:
+                self.retired.append(self.partials)
+            self.partials = torch.zeros(max(n, 1), dtype=torch.float64, device=self.words.device)
+        return self.partials
+
+
 class SGD(torch.optim.SGD):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
-                 foreach=None, differentiable=False, fused=None):
+                 foreach=None, differentiable=False, fused=None, max_grad_norm=None, grad_norm_type=2.0):
         # foreach / fused select among PyTorch's own implementations: accepted for signature compatibility, irrelevant here
         if differentiable:
             raise ValueError("yolo_for_turbines_amd.optim.SGD: differentiable=True is not supported")
@@ -115,6 +177,10 @@ class SGD(torch.optim.SGD):
         self._tables = {}                                   # group index -> _GroupTable
         self._word = {}                                     # parameter -> its 1-element view of a table's `written`
         self._ema = None                                    # ema.ModelEMA.attach: step() moves that average in its own launch
+        # clipping by global norm: plain attributes, looked at by every step() / sync_hyper() (None: today's launches)
+        _clip_args(max_grad_norm, grad_norm_type, "yolo_for_turbines_amd.optim.SGD")
+        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
+        self._clip = None                                   # _ClipState, with the first clipped step (or the first look at grad_norm)
 
     def _table(self, gi, params):
         t = self._tables.get(gi)
@@ -186,6 +252,30 @@ class SGD(torch.optim.SGD):
             tab = self._tables.get(gi)
             if tab is not None:
                 tab.push_hyper(self._hyper_of(group))
+        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, "yolo_for_turbines_amd.optim.SGD")
+        if clip is not None and self._clip is not None:
+            self._clip.push(clip[0])
+
+    def _clip_state(self):
+        if self._clip is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step with max_grad_norm set before capturing")
+            first = next((p for g in self.param_groups for p in g["params"]), None)
+            if first is None or not first.is_cuda:
+                raise TypeError("yolo_for_turbines_amd.optim.SGD: parameters must be contiguous fp32 tensors on one GPU")
+            self._clip = _ClipState(first.device)
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """``total_norm`` of the last clipped step: a 0-dim fp32 device tensor at a fixed address (a view of the clip state),
+        written by the step's own launches; reading it enqueues nothing and waits for nothing."""
+        return self._clip_state().grad_norm
+
+    @property
+    def clip_coef(self):
+        """The coefficient the last clipped step multiplied its gradients by (1 when the norm was within ``max_grad_norm``)."""
+        return self._clip_state().clip_coef
 
     def _prepare(self, gi, group, scaled):
         """Fill and (if it changed) upload the row table of one group for the gradients as they are now. Returns
@@ -264,16 +354,22 @@ class SGD(torch.optim.SGD):
         scaled values) and nothing is touched when ``found_inf`` is non-zero; without them nothing changes. ``check_into``
         (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it. With a weight
         average attached (``ModelEMA.attach``) the same launches also move the average of every parameter they update; one
-        more launch does the entries left over (BatchNorm statistics, parameters without a gradient) and counts the update."""
+        more launch does the entries left over (BatchNorm statistics, parameters without a gradient) and counts the update.
+        With ``self.max_grad_norm`` set, the gradients are clipped by their global norm over all groups (``grad_norm_type`` 2 or
+        inf) between the unscale and everything else, in registers: ``check_into`` then comes from the same read as the norm."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, "yolo_for_turbines_amd.optim.SGD")   # refused before anything moves
         lib = L.lib()
         grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         scaled = grad_scale is not None or found_inf is not None
         groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
         ready = [(g,) + self._prepare(gi, g, scaled) for gi, g in groups]
+        if clip is not None:
+            self._step_clipped(ready, clip, grad_scale, found_inf, scaled, check_into)
+            return loss
         if check_into is not None:                           # every group is checked before any group is stepped
             self._check(ready, check_into)
         ema = self._ema
@@ -303,6 +399,50 @@ class SGD(torch.optim.SGD):
             ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
         return loss
 
+    def _step_clipped(self, ready, clip, grad_scale, found_inf, scaled, check_into):
+        """step() with ``max_grad_norm`` set: partial sums per group (with the non-finite check in the same read when
+        ``check_into`` is given), one finalize over all of them, then the clip variant of every group's step."""
+        lib, st = L.lib(), L.current_stream()
+        max_norm, kind = clip
+        cs = self._clip_state()
+        dev = cs.words.device
+        cs.push(max_norm)
+        total = sum(tab.chunks.shape[0] for _, tab, _, _ in ready)
+        ws = cs.workspace(total)
+        scale, check = self._flag(grad_scale, dev, "grad_scale"), self._flag(check_into, dev, "found_inf")
+        if check is not None and not ready:
+            check.zero_()
+        off = 0
+        for k, (_, tab, _, _) in enumerate(ready):           # every group's norm (and check) before any group is stepped
+            if tab.hyper.device != dev:
+                raise TypeError("yolo_for_turbines_amd.optim.SGD: max_grad_norm needs every parameter group on one GPU")
+            n = tab.chunks.shape[0]
+            L.check(lib.yolo_clip_norm_partials(tab.items.data_ptr(), tab.chunks.data_ptr(), n, L.ptr(scale), kind, ws.data_ptr() + 8 * off,
+                                                L.ptr(check), int(k == 0), st), "yolo_clip_norm_partials")
+            off += n
+        L.check(lib.yolo_clip_finalize(ws.data_ptr(), total, kind, cs.words.data_ptr(), st), "yolo_clip_finalize")
+        ema = self._ema
+        if ema is not None:
+            rest = ema._rest({id(p) for r in ready for p in r[3]})
+        flag = self._flag(found_inf, dev, "found_inf")
+        for group, tab, fresh, _ in ready:
+            nest, maxi = int(bool(group["nesterov"])), int(bool(group["maximize"]))
+            avg = (0, 0) if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
+            on_device = scaled or tab.device_first           # "first step" is then the device's to say, as in yolo_sgd_step_amp
+            words = ((flag if flag is not None else tab.no_inf).data_ptr(), tab.written.data_ptr()) if on_device else (0, 0)
+            L.check(lib.yolo_sgd_step_clip(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0],
+                                           tab.hyper.data_ptr(), cs.words.data_ptr(), L.ptr(scale), *words, *avg, nest, maxi, st),
+                    "yolo_sgd_step_clip")
+            if on_device:
+                continue
+            if len(fresh) == len(tab.params):
+                tab.written.fill_(1)
+            else:
+                for i in fresh:
+                    tab.written[i:i + 1].fill_(1)
+        if ema is not None:
+            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
+
     def _check(self, ready, found_inf):
         lib = L.lib()
         if not ready:
@@ -311,3 +451,50 @@ class SGD(torch.optim.SGD):
             L.check(lib.yolo_sgd_check_finite(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0],
                                               self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
                                               L.current_stream()), "yolo_sgd_check_finite")
+
+
+_FREE_TABLES = {}                                           # (device, ((address, elements), ...)) -> (rows, chunks, partials)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """Drop-in for ``torch.nn.utils.clip_grad_norm_`` on the GPU, for other optimizers and for the ``scaler.unscale_`` pattern:
+    the partial sums, the finalize and one in-place ``g *= coef`` over every gradient (three launches, whatever the number of
+    tensors). Returns ``total_norm`` as a 0-dim fp32 device tensor without waiting for the host; ``error_if_nonfinite=True``
+    does wait, as in PyTorch. Only dense contiguous fp32 gradients on one GPU (``TypeError`` otherwise: there is no fallback);
+    ``foreach`` is accepted for signature compatibility."""
+    who = "yolo_for_turbines_amd.clip_grad_norm_"
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    max_norm, kind = _clip_args(max_norm, norm_type, who)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    for g in grads:
+        if not (g.is_cuda and g.device == dev and not g.is_sparse and g.dtype == torch.float32 and g.is_contiguous()):
+            raise TypeError(f"{who}: gradients must be dense contiguous fp32 tensors on one GPU")
+    lib, st = L.lib(), L.current_stream()
+    key = (dev, tuple((g.data_ptr(), g.numel()) for g in grads))
+    tabs = _FREE_TABLES.get(key)
+    if tabs is None:                                        # addresses repeat step after step (buckets, the caching allocator)
+        if len(_FREE_TABLES) >= 8:
+            _FREE_TABLES.pop(next(iter(_FREE_TABLES)))
+        ce = lib.yolo_sgd_chunk_elems()
+        rows = torch.tensor([[0, a, 0, n] for a, n in key[1]], dtype=torch.int64).to(dev)          # yolo_sgd_item: g and n only
+        chunks = torch.tensor([(i, s) for i, (_, n) in enumerate(key[1]) for s in range(0, n, ce)], dtype=torch.int32).reshape(-1, 2).to(dev)
+        tabs = _FREE_TABLES[key] = (rows, chunks, torch.zeros(max(chunks.shape[0], 1), dtype=torch.float64, device=dev))
+    rows, chunks, partials = tabs
+    state = torch.zeros(4, dtype=torch.float32, device=dev)             # yolo_clip_state of this call; the result is a view of it
+    state[0:1].fill_(max_norm)
+    n = chunks.shape[0]
+    L.check(lib.yolo_clip_norm_partials(rows.data_ptr(), chunks.data_ptr(), n, 0, kind, partials.data_ptr(), 0, 0, st), "yolo_clip_norm_partials")
+    L.check(lib.yolo_clip_finalize(partials.data_ptr(), n, kind, state.data_ptr(), st), "yolo_clip_finalize")
+    total = state[1]
+    if error_if_nonfinite and not bool(torch.isfinite(total)):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    L.check(lib.yolo_clip_scale_grads(rows.data_ptr(), chunks.data_ptr(), n, state.data_ptr(), st), "yolo_clip_scale_grads")
+    torch.autograd.graph.increment_version(grads)
+    return total
