@@ -84,6 +84,11 @@ typedef struct yolo_conv_desc {
     int32_t x_ld, x_off;    /* input channel stride / offset (elements)                    */
     int32_t y_ld, y_off;    /* output  "   (ignored for YOLO_OUT_HEAD)                     */
     int32_t r_ld, r_off;    /* residual "  (YOLO_FLAG_RESIDUAL), same spatial size as y    */
+                            /* YOLO_F16 / YOLO_BF16: x_ld and x_off must be multiples of 8 (16-byte input rows), else      */
+                            /* YOLO_ERR_ARG. y_ld, y_off, r_ld and r_off may have any value: with all of them multiples    */
+                            /* of 8 the stores move 8 channels at a time and the faster kernel families are open; any      */
+                            /* other view is written element by element, same values. Base pointers: 16-byte aligned.      */
+                            /* The same holds for dz (as x) and dx / residual (as y / r) of yolo_conv_dgrad_s2.            */
     int32_t act;            /* YOLO_ACT_*                                                  */
     int32_t out_mode;       /* YOLO_OUT_*                                                  */
     int32_t dtype;          /* YOLO_F32, YOLO_F16 or YOLO_BF16: activations (x, residual, y) and   */

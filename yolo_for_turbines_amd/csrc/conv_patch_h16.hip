@@ -465,7 +465,7 @@ __device__ __forceinline__ void conv_patch_h16_body(const ConvHArgs& p) {
     const bool nan_chk = p.flags & YOLO_FLAG_NANCHECK;
     constexpr int OLD = 68;
     float* ost = reinterpret_cast<float*>(patch);                     // [128][68] fp32 = 34,816 B
-    const bool vec_ok = (p.out_mode != YOLO_OUT_HEAD) && (p.Cout % 8 == 0);
+    const bool vec_ok = p.flags & H_FLAG_VEC_EPILOGUE;               // 16-byte rows of y (and of the residual): patch_vec_epilogue
     bool saw_nan = false;
     __syncthreads();                                                  // every wave is done reading the patch
     const int c8 = tid & 7;
@@ -640,9 +640,20 @@ void pick_tile_h(int Hin, int Hout, int Wout, int ks, int stride, int* th, int* 
     (void)Hin;
 }
 
+// The epilogue's vector path moves 8 channels per 16-byte store (and residual load): every address it forms must be 16-byte
+// aligned, i.e. whole groups of 8 channels, and y (with a residual: r as well) with row stride and channel offset on 16 bytes
+// (tensor base pointers are). Any other view takes the element-wise path. The heads (fp32 output) have a store of their own.
+static void patch_vec_epilogue(ConvHArgs& a) {
+    auto rows16 = [](int ld, int off) { return (ld & 7) == 0 && (off & 7) == 0; };
+    const bool ok = a.out_mode != YOLO_OUT_HEAD && a.Cout % 8 == 0 && rows16(a.y_ld, a.y_off) &&
+                    (!(a.flags & YOLO_FLAG_RESIDUAL) || rows16(a.r_ld, a.r_off));
+    a.flags = ok ? a.flags | H_FLAG_VEC_EPILOGUE : a.flags & ~H_FLAG_VEC_EPILOGUE;
+}
+
 template <typename T, int KS, int STRIDE, int BN>
 static int launch_h_t(ConvHArgs& a, hipStream_t s) {
     tile_grid_h(a, BN);
+    patch_vec_epilogue(a);
     // Stride-2 3x3: the patch of 128 output pixels is ~500 input pixels, and two buffers of it (82 KB) leave ONE block per
     // CU (measured: >= 82 KB -> 1, 42-52 KB -> 3), i.e. nothing to overlap a block's staging and epilogue with. One buffer
     // + one more barrier per 32-channel chunk instead; the region also holds the epilogue's 128 x 68 fp32 staging tile.
@@ -659,6 +670,7 @@ static int launch_h_t(ConvHArgs& a, hipStream_t s) {
 template <typename T, int BN, int MASK>
 static int launch_cls(ConvHArgs& a, hipStream_t s) {
     tile_grid_h(a, BN);
+    patch_vec_epilogue(a);
     a.bufmask = 1;
     a.mtab_off = 2 * a.patch_cap * H_PIX_BYTES;
     const size_t lds = (size_t)a.mtab_off + 256 * sizeof(int);

@@ -40,7 +40,7 @@ struct ConvHArgs {
     int bufmask, mtab_off;   // bufmask 1: two patch buffers; 0: one (stride-2 3x3, see launch_h). mtab_off: byte offset of mtab in LDS
     int tiles_w, tiles_n, nblocks;
     int KT, nchunks;
-    int act, out_mode, flags, nc5;
+    int act, out_mode, flags, nc5;       // flags: YOLO_FLAG_* of the descriptor, and H_FLAG_VEC_EPILOGUE from the patch kernel's launchers
     int Ho, Wo;
     int first_wave, stagger;
     int prio;                            // conv3_dma_h16: prologue / epilogue at s_setprio 2 (A/B switch YOLO_DMA_PRIO=0)
@@ -59,6 +59,11 @@ struct ConvHArgs {
     // ~20 of them per thread were most of a 10k-cycle prologue in front of 9k cycles of matrix work)
     unsigned mg_H, mg_TW, mg_PC, mg_tn, mg_tw, mg_Hp;
 };
+
+// conv_patch_h16 only, a bit of ConvHArgs::flags above the public YOLO_FLAG_*: the epilogue may move 8 channels per 16-byte
+// load / store. Decided on the host (patch_vec_epilogue), because it depends on the alignment of every address the epilogue
+// forms and not on the channel count alone; without it the element-wise path runs.
+constexpr int H_FLAG_VEC_EPILOGUE = 1 << 30;
 
 // x / d for 0 <= x < 2^31 with mg = ceil(2^32 / d) (d >= 2) or 0 (d == 1): the estimate is q or q + 1, one fix-up
 __device__ __forceinline__ int fdiv(int x, unsigned mg, int d) {
