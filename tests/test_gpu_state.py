@@ -21,7 +21,7 @@ def yt():
     return pkg
 
 
-def _case(seed):
+def _case(seed, S=S):
     anchors = gi.TRAIN_CASE["anchors"]
     sd = onet.synth_state_dict(seed, 3, NC, gain=gi.NET_GAIN)
     x = onet.synth_input(seed + 1, B, S).cuda()
@@ -308,3 +308,145 @@ def test_rccl_all_reduce_inside_a_graph_capture_one_rank():
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "workers", "dp_graph_check.py")], env=env, capture_output=True, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0 and "DP_GRAPH_OK" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+
+
+# ---- the train plan's launch tables against a model whose tensors or settings are replaced between steps (S = 64)
+
+def _model(yt, sd, activation="leaky_relu"):
+    m = yt.YOLOv3(num_classes=NC, activation=activation)
+    m.load_state_dict({k: v.detach().clone() for k, v in sd.items()})
+    return m.cuda().train()
+
+
+def _train_step(yt, m, opt, x, tg, sa, autocast):
+    """One eager fine-tune step; returns the predictions of its forward (detached fp32 copies: nothing of the graph lives on)."""
+    lf = yt.FusedYOLOLoss()
+    opt.zero_grad(set_to_none=True)
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        po = m(x)
+        loss = sum(sum(lf(po[i], tg[i], sa[i])) for i in range(3))
+    loss.backward()
+    opt.step()
+    return [p.detach().float().clone() for p in po]
+
+
+def _sgd(m):
+    return torch.optim.SGD(m.parameters(), lr=1e-3, momentum=0.9, weight_decay=5e-4)
+
+
+def _train_plan(m):
+    plans = [pl for k, pl in m._engine._plans.items() if k[0] == "train"]
+    assert len(plans) == 1
+    return plans[0]
+
+
+@pytest.mark.parametrize("autocast", [False, True])
+def test_replaced_parameter_and_buffer_objects_reach_the_recorded_train_step(yt, autocast):
+    """After two steps the forward and backward tables are recorded and replayed. A BatchNorm weight replaced by a new
+    Parameter and a running_mean replaced by a clone must be what the next step reads, differentiates and updates - the
+    old objects, whose addresses never moved, must be neither used nor kept alive."""
+    import gc
+    import weakref
+    sd, x, tg, sa = _case(371, 64)
+    m = _model(yt, sd)
+    opt = _sgd(m)
+    for _ in range(2):
+        _train_step(yt, m, opt, x, tg, sa, autocast)
+    bn = m.layers[0].batch_norm
+    old_w, old_rm = weakref.ref(bn.weight), bn.running_mean
+    bn.weight = torch.nn.Parameter(bn.weight.detach() * 1.5 + 0.25)
+    bn.running_mean = old_rm.clone()
+    old_rm_values = old_rm.clone()
+    new_w, new_rm = bn.weight, bn.running_mean
+    fresh = _model(yt, m.state_dict())
+    del opt                                                         # (an optimizer keeps its parameters alive)
+    got = _train_step(yt, m, _sgd(m), x, tg, sa, autocast)
+    want = _train_step(yt, fresh, _sgd(fresh), x, tg, sa, autocast)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    assert bn.weight is new_w and new_w.grad is not None and bool(new_w.grad.abs().sum() > 0)
+    assert bn.running_mean is new_rm and not torch.equal(new_rm, old_rm_values)
+    assert torch.equal(old_rm, old_rm_values)                       # nothing wrote through the old pointer
+    for (k, a), (_, b) in zip(m.state_dict().items(), fresh.state_dict().items()):
+        assert torch.equal(a, b), k
+    gc.collect()
+    assert old_w() is None
+
+
+@pytest.mark.parametrize("autocast", [False, True])
+def test_changed_batchnorm_momentum_reaches_the_recorded_train_forward(yt, autocast):
+    """momentum (like eps and track_running_stats) is an argument of the recorded BatchNorm launches."""
+    sd, x, tg, sa = _case(381, 64)
+    m = _model(yt, sd)
+    opt = _sgd(m)
+    for _ in range(2):
+        _train_step(yt, m, opt, x, tg, sa, autocast)
+    fresh = _model(yt, m.state_dict())
+    default =_model(yt, m.state_dict())
+    for mm, momentum in ((m, 0.5), (fresh, 0.5), (default, 0.1)):
+        mm.layers[0].batch_norm.momentum = momentum
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):      # (a train-mode forward needs autograd on)
+            mm(x)
+    got = m.layers[0].batch_norm.running_mean
+    assert torch.equal(got, fresh.layers[0].batch_norm.running_mean)
+    assert not torch.equal(got, default.layers[0].batch_norm.running_mean)      # and 0.5 really differs from 0.1 here
+    for (k, a), (_, b) in zip(m.state_dict().items(), fresh.state_dict().items()):
+        assert torch.equal(a, b), k
+
+
+@pytest.mark.parametrize("autocast", [False, True])
+def test_load_state_dict_assign_between_train_steps_drops_the_tables(yt, autocast):
+    """load_state_dict(assign=True) replaces every Parameter and buffer object: no table of the plan survives it."""
+    sd, x, tg, sa = _case(391, 64)
+    m = _model(yt, sd)
+    opt = _sgd(m)
+    for _ in range(2):
+        _train_step(yt, m, opt, x, tg, sa, autocast)
+    plan = _train_plan(m)
+    tape0, btapes0 = plan.fwd_tape, [t[0] for t in plan.bwd_tapes.values()]
+    assert tape0 is not None and btapes0
+    m.load_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()}, assign=True)
+    fresh = _model(yt, m.state_dict())
+    got = _train_step(yt, m, _sgd(m), x, tg, sa, autocast)
+    want = _train_step(yt, fresh, _sgd(fresh), x, tg, sa, autocast)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    for (k, a), (_, b) in zip(m.state_dict().items(), fresh.state_dict().items()):
+        assert torch.equal(a, b), k
+    assert _train_plan(m) is plan and plan.fwd_tape is not None and plan.fwd_tape is not tape0
+    assert all(t[0] not in btapes0 for t in plan.bwd_tapes.values())
+
+
+@pytest.mark.parametrize("ac", [None, torch.bfloat16])
+def test_eager_step_after_a_graph_replay_uploads_its_own_optimizer_table(yt, ac):
+    """A replay copies the captured step's row table (parameter, gradient, momentum addresses) into the device table that
+    yt.SGD's eager steps share with it. eager(96), replay(64), eager(96): the second eager step must step with its own
+    gradient addresses although its rows equal the ones it uploaded last."""
+    sd, x, tg, sa = _case(401, 64)
+    _, x2, tg2, sa2 = _case(411, 96)
+    lf = yt.FusedYOLOLoss()
+
+    def make():
+        m = _model(yt, sd, "mish")
+        return m, yt.SGD(m.parameters(), lr=1e-3, momentum=0.9, weight_decay=5e-4)
+
+    def eager(m, o, xx, tt, ss):
+        o.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=ac or torch.bfloat16, enabled=ac is not None):
+            po = m(xx)
+            loss = sum(sum(lf(po[i], tt[i], ss[i])) for i in range(3))
+        loss.backward()
+        o.step()
+    m1, o1 = make()
+    m2, o2 = make()
+    step = yt.GraphedTrainStep(m2, o2, sa, x, tg, autocast_dtype=ac, warmup=3)
+    for _ in range(3):
+        eager(m1, o1, x, tg, sa)
+    eager(m1, o1, x2, tg2, sa2)
+    eager(m1, o1, x, tg, sa)
+    eager(m1, o1, x2, tg2, sa2)
+    eager(m2, o2, x2, tg2, sa2)
+    step(x, tg)
+    eager(m2, o2, x2, tg2, sa2)
+    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
+        assert torch.equal(a, b), k

@@ -52,7 +52,7 @@ layers)
   echo "layers done";;
 stats)
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fwd -o bench -- $PY bench.py --full --no-cpu-baseline --train-steps 0 > $O/bench_forward_legs_under_rocprof.json 2> $O/bench_forward_legs_under_rocprof.log
-  YOLO_TRAIN_TAPE=0 YOLO_WGRAD_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_train_bf16 -o train -- $PY tools/train_bench.py --dtype bf16 --fused-loss --steps 5 > $O/train_bf16.txt 2>&1
+  YOLO_TRAIN_TAPE=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_train_bf16 -o train -- $PY tools/train_bench.py --dtype bf16 --fused-loss --steps 5 > $O/train_bf16.txt 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_nms80 -o nms -- $PY tools/nms_bench.py 80 uniform > $O/nms80.txt 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_nms2 -o nms -- $PY tools/nms_bench.py 2 uniform > $O/nms2.txt 2>&1
   echo "stats done";;

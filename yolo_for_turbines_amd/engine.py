@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .guards import SlotGuard
 
 _DT = {"fp32": (L.F32, torch.float32), "fp16": (L.F16, torch.float16), "bf16": (L.BF16, torch.bfloat16)}
 
@@ -517,7 +518,7 @@ class ModelState:
         self._defer_nan = False           # detect_images(): the forward leaves its NaN flag for the caller to read
         self._pending_flag = None
         self._gen = 0                     # bumped whenever packed state is declared out of date by hand (invalidate, mark_unfolded)
-        self._fast = {}                   # (id(blocks), device, dtype) -> (gen, blocks, [(owner dict, key, tensor, version, address)])
+        self._fast = {}                   # (id(blocks), device, dtype) -> (gen, blocks, SlotGuard of the blocks' tensors, [(block, _pack_gen)])
         self._plans = {}
         # True: the NaN guards of model.py:175,183-184 raise inside the forward that saw the NaN (one host sync per forward).
         # "deferred" (train mode only): they raise at the start of the next forward, or from flush_nan() - the eager fine-tune
@@ -625,9 +626,9 @@ class ModelState:
 
     def refresh_weights(self, blocks, device, stream, dtype="fp32", fold_bn=True):
         # fast path (eval plans, whose block list lives as long as the plan): nothing this library or PyTorch wrote since
-        # the last full check of this very list of blocks - one flat walk over (owner dict, key, tensor, version, address)
-        # instead of rebuilding 75 pairs of stamps. The walk re-reads the modules' CURRENT entries: a replaced Parameter
-        # object (pruning, parametrize, `conv.weight = nn.Parameter(...)`) fails `is` and takes the slow path.
+        # the last full check of this very list of blocks - one SlotGuard walk (object, version, address of every stamped
+        # tensor) instead of rebuilding 75 pairs of stamps. The guard re-reads the modules' CURRENT entries: a replaced
+        # Parameter object (pruning, parametrize, `conv.weight = nn.Parameter(...)`) fails `is` and takes the slow path.
         # Training (fold_bn=False) never uses it: after an optimizer step every weight is stale anyway, and
         # `mark_unfolded` moves the generation on every train-mode forward.
         if not fold_bn:
@@ -635,22 +636,14 @@ class ModelState:
             return
         fkey = (id(blocks), device.index, dtype)
         fast = self._fast.get(fkey)
-        if fast is not None and fast[0] == self._gen and fast[1] is blocks:
-            for owner, name, t, ver, ptr in fast[2]:
-                if owner[name] is not t or t._version != ver or t.data_ptr() != ptr:
-                    break
-            else:
-                if all(blk.__dict__.get("_pack_gen", 0) == gen for blk, gen in fast[3]):
-                    return
+        if (fast is not None and fast[0] == self._gen and fast[1] is blocks and fast[2].ok()
+                and all(blk.__dict__.get("_pack_gen", 0) == gen for blk, gen in fast[3])):
+            return
         self._refresh_weights_slow(blocks, device, stream, dtype, fold_bn)
-        flat = []
-        for blk in blocks:
-            for owner, name in PackedBlock.stamp_slots(blk):
-                t = owner[name]
-                flat.append((owner, name, t, t._version, t.data_ptr()))
         if len(self._fast) > 64:
             self._fast.clear()
-        self._fast[fkey] = (self._gen, blocks, flat, [(blk, blk.__dict__.get("_pack_gen", 0)) for blk in blocks])
+        guard = SlotGuard([slot for blk in blocks for slot in PackedBlock.stamp_slots(blk)], versions=True)
+        self._fast[fkey] = (self._gen, blocks, guard, [(blk, blk.__dict__.get("_pack_gen", 0)) for blk in blocks])
 
     def _refresh_weights_slow(self, blocks, device, stream, dtype="fp32", fold_bn=True):
         stale, refold = [], []

@@ -166,6 +166,8 @@ class GraphedTrainStep:
         self.model._engine.invalidate()
         if self.ema is not None and hasattr(self.ema.module, "_engine"):
             self.ema.module._engine.invalidate()        # the averaged tensors were rewritten the same way
+        if hasattr(self.opt, "forget_uploads"):
+            self.opt.forget_uploads()                   # and the device row tables of `yt.SGD` hold the captured step's rows
         return self.loss
 
     def release(self):

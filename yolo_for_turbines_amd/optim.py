@@ -198,6 +198,12 @@ class SGD(torch.optim.SGD):
             t.device_first = old is not None and old.device_first
         return t
 
+    def forget_uploads(self):
+        """Something else than an eager `step()` wrote the device row tables (a HIP-graph replay copies its captured rows
+        into them): the next eager step uploads its own rows again."""
+        for tab in self._tables.values():
+            tab.uploaded = None
+
     def _unwritten(self):
         """Parameters whose momentum buffer exists but has never been written (every loss-scaled step so far was skipped).
         Reads device memory, so it waits for the device: for checkpointing, not for the step."""

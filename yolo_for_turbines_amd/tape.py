@@ -9,8 +9,9 @@ Pointers that change from step to step (input batch, fresh prediction tensors, u
 before recording; every recorded argument that falls into a slot's byte range becomes a relocation.
 
 Everything else a table refers to is owned by the plan or by the model and does not move: activation / statistics /
-workspace buffers, packed weights, gradient buckets (`dist.GradBuckets`), parameters and BatchNorm buffers (a table checks
-their addresses before it replays and is re-recorded when one has moved).
+workspace buffers, packed weights, gradient buckets (`dist.GradBuckets`), parameters and BatchNorm buffers. A table keeps none of the model's tensors alive
+and checks nothing itself: the plan watches the model's parameter and buffer slots and drops its tables when one changed
+(`TrainPlan.drop_tables`).
 """
 from __future__ import annotations
 
@@ -29,7 +30,6 @@ class CallTape:
         self.slot_range = {}                  # name -> (index, base, nbytes) at record time
         self.keep = []                        # ctypes objects / tensors the table points at
         self.cuts = []                        # [(call index, payload)]: the host does something after call index - 1
-        self.guards = []                      # (tensor, data_ptr) that must not have moved
         self._c = None
 
     # ---- recording
@@ -37,9 +37,6 @@ class CallTape:
         if name not in self.slot_range:
             self.slot_names.append(name)
         self.slot_range[name] = (self.slot_names.index(name), int(base), int(nbytes))
-
-    def guard(self, tensors):
-        self.guards = [(t, t.data_ptr()) for t in tensors]
 
     def cut(self, payload):
         self.cuts.append((len(self.calls), payload))
@@ -88,12 +85,6 @@ class CallTape:
         return self
 
     # ---- replay
-    def fresh(self):
-        for t, ptr in self.guards:
-            if t.data_ptr() != ptr:
-                return False
-        return True
-
     def run(self, slots, stream, lo=0, hi=None):
         """Replay calls[lo:hi] with the given slot values ({name: address})."""
         arr, n, rel, nrel, sl = self._c

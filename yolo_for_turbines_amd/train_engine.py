@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import _DT, PackedBlock, Program, TView, _act_code, build_network_program, resolve_dtype
+from .guards import SlotGuard
 from .tape import CallTape, RecordingLib
 
 _const_cache = {}
@@ -45,7 +46,6 @@ def _desc(B, x: TView, cin, cout, k, s, y_ld, y_off, r: TView = None, act=L.ACT_
     return d
 
 
-_WGRAD_OVERLAP = os.environ.get("YOLO_WGRAD_OVERLAP", "1") != "0"      # A/B switch: weight gradients on a side stream
 # Launch tables (tape.py): the whole-network forward / backward record their ~900 launches once per plan and replay them
 # through ONE C call (yolo_train_fwd_batch / yolo_train_bwd_batch). YOLO_TRAIN_TAPE=0 keeps the per-launch path (A/B).
 _TAPE = os.environ.get("YOLO_TRAIN_TAPE", "1") != "0"
@@ -122,9 +122,37 @@ class TrainPlan:
         self.gen = 0                      # bumped by every train-mode forward: a backward must see the buffers of ITS forward
         self.pinned = False               # set by GraphedTrainStep: pointers into this plan are baked into a HIP graph
         self.dropped = False              # set when the model dropped its plans (model.to(), ...)
+        self.guard = None                 # guards.SlotGuard of everything of the model the tables and `plist` hold (watch)
+        self.plist = None                 # list(model.parameters()): valid exactly as long as the guard is
+        self.orders = {}                  # need pattern -> (parameters in backward-production order, their ids)
+        self.bmap = None                  # _bstats_map(plan), made by its first call
+        self.brows = {}                   # (op index, conv flags) -> (rows, ld) of yolo_conv_bstats_rows
 
     def view_ptr(self, v: TView):
         return self.ybuf[v.buf].data_ptr()
+
+    def watch(self, model):
+        """Guard what the recorded tables and their `post` lists hold by address or by object: every parameter and buffer slot
+        of the model (`num_batches_tracked` included), and the BatchNorm settings baked into the recorded calls."""
+        mods = list(model.modules())
+        slots = [(m._parameters, k) for m in mods for k in m._parameters] + [(m._buffers, k) for m in mods for k in m._buffers]
+        bns = [vars(blk._modules["batch_norm"]) for blk in self.blocks if blk.batch_norm_act]
+        self.guard = SlotGuard(slots, values=[(d, k) for d in bns for k in ("momentum", "eps", "track_running_stats")])
+        self.plist = list(model.parameters())
+
+    def check_guard(self):
+        """Start of every forward and backward: a replaced Parameter / buffer object, moved storage or a changed BatchNorm
+        setting drops the tables. False: nothing is watched any more (the next forward calls `watch`)."""
+        if self.guard is not None and self.guard.ok():
+            return True
+        self.drop_tables()
+        return False
+
+    def drop_tables(self):
+        """Forget everything recorded from the model's tensors; the next step records again."""
+        self.fwd_tape, self.guard, self.plist = None, None, None
+        self.bwd_tapes.clear()
+        self.orders.clear()
 
 
 def _forward(state, model, plan: TrainPlan, x, use_tape=False):
@@ -142,7 +170,7 @@ def _forward(state, model, plan: TrainPlan, x, use_tape=False):
             preds[op["pred"]] = torch.empty((B, 3, op["Ho"], op["Wo"], op["block"].conv.out_channels // 3), dtype=torch.float32,
                                             device=dev)
     tape = plan.fwd_tape if use_tape else None
-    if tape is not None and tape.fresh():
+    if tape is not None:                                 # (recorded from the model as it still is: TrainPlan.check_guard)
         slots = {"x": xin.data_ptr()}
         for k, t in enumerate(preds):
             slots[f"pred{k}"] = t.data_ptr()
@@ -158,7 +186,6 @@ def _forward(state, model, plan: TrainPlan, x, use_tape=False):
         post = _forward_launches(lib, state, plan, x, xin, preds, stream)
         if use_tape:
             tape.post = post
-            tape.guard(list(model.parameters()) + list(model.buffers()))
             plan.fwd_tape = tape.finish()
     tracked, stats_written, bn_blocks = (tape.post if tape is not None else post)
     if tracked:
@@ -311,9 +338,8 @@ def _bstats_map(plan: TrainPlan):
     """op index i -> op index P for the input-gradient launches that can also take block P's BatchNorm-backward sums:
     P is the only producer of i's input tensor (same channel view, plain NHWC store, BatchNorm block) and i is the FIRST
     consumer of that tensor in forward order - the backward visits it last, so its dgrad writes the complete gradient."""
-    got = plan.__dict__.get("_bmap")
-    if got is not None:
-        return got
+    if plan.bmap is not None:
+        return plan.bmap
     prog = plan.prog
     producers, first_use = {}, {}
     for j, op in enumerate(prog.ops):
@@ -337,14 +363,14 @@ def _bstats_map(plan: TrainPlan):
             if (P < i and po["block"].batch_norm_act and po["out_mode"] == L.OUT_NHWC and yv.off == xv.off and yv.C == xv.C
                     and yv.ld == xv.ld and xv.C == op["block"].conv.in_channels and _act_code(po["block"]) in (L.ACT_LEAKY, L.ACT_MISH)):
                 bmap[i] = P
-    plan._bmap = bmap
+    plan.bmap = bmap
     return bmap
 
 
 def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_input_grad=False, buckets=None, tape=None):
     """need: dict param-id -> bool; seeds: {symbolic buf: gradient tensor} for stand-alone blocks.
     tape (a CallTape being recorded): every launch goes through the recording proxy, every temporary stays alive in the
-    tape, bucket completions become cut points, and everything runs on one stream.
+    tape and bucket completions become cut points. Everything runs on the current stream, recorded or not.
     Returns (dict param-id -> grad tensor, gradient buffer of the input or None)."""
     lib = L.lib() if tape is None else RecordingLib(L.lib(), tape)
     retain = None if tape is None else tape.keep
@@ -376,39 +402,11 @@ def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_inpu
     for b, t in (seeds or {}).items():
         G.state[b] = ("own", t)
     dz_scratch = {}
-    # Weight gradients on a SIDE stream (single GPU): wgrad + its split-K reduce only feed the optimizer, while the chain
-    # dz -> dgrad -> BatchNorm backward of the previous block is what the next block waits for. The BatchNorm passes and the
-    # reduce are HBM-bound, the convolutions matrix-bound, so the two streams complement each other on the CUs. dz scratch
-    # buffers then rotate in pairs: a buffer is rewritten only after the wgrad that read it has finished (event), and the
-    # main stream joins the side stream before this function returns (allocator reuse stays stream-ordered). With gradient
-    # buckets (data parallel) everything stays on one stream: the all-reduce hooks are ordered against it.
-    # Measured (bf16, B=32, 416^2): eager 22.8 -> 21.0 ms (fp32 80.0 -> 76.2): the second stream mostly fills the launch gaps of
-    # the first. Replayed as ONE HIP graph there are no gaps and the concurrent kernels only disturb each other (19.0 -> 19.7
-    # ms), so a capture keeps everything on one stream.
-    overlap = buckets is None and tape is None and _WGRAD_OVERLAP and not torch.cuda.is_current_stream_capturing()
-    main_s = torch.cuda.current_stream()
-    side_s = None
-    if overlap:
-        side_s = getattr(plan, "side_stream", None)
-        if side_s is None:
-            side_s = plan.side_stream = torch.cuda.Stream(device=dev)
-    busy = {}                                                          # id(scratch tensor) -> event of its last side-stream reader
-    rot = {}
 
-    def scratch(numel):
-        if not overlap:
-            t = dz_scratch.get(numel)
-            if t is None:
-                t = dz_scratch[numel] = keep(torch.empty(numel, dtype=plan.tdtype, device=dev))
-            return t
-        k = rot.get(numel, 0)
-        rot[numel] = k ^ 1
-        t = dz_scratch.get((numel, k))
+    def scratch(numel):                                                # everything runs on one stream: one buffer per size
+        t = dz_scratch.get(numel)
         if t is None:
-            t = dz_scratch[(numel, k)] = torch.empty(numel, dtype=plan.tdtype, device=dev)
-        ev = busy.pop(id(t), None)
-        if ev is not None:
-            main_s.wait_event(ev)
+            t = dz_scratch[numel] = keep(torch.empty(numel, dtype=plan.tdtype, device=dev))
         return t
 
     # Frozen backbone (`freeze=True`, model.py:306-309,330-334): nothing below the first block that owns a trainable
@@ -510,19 +508,8 @@ def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_inpu
         # ---------------------------------------------------------------- wgrad
         if need.get(id(cv.weight), False):
             dw = new_grad(cv.weight)
-            wstream = stream
-            if overlap:
-                e_dz = torch.cuda.Event()
-                e_dz.record(main_s)
-                side_s.wait_event(e_dz)
-                dw.record_stream(side_s)
-                wstream = side_s.cuda_stream
             L.check(lib.yolo_conv_wgrad(dz.data_ptr(), dz_ld, 0, plan.view_ptr(xv), xv.ld, xv.off, dw.data_ptr(), B, xv.H, xv.W, cin,
-                                        cout, k, s, code, plan.wg_ws.data_ptr(), plan.wg_ws.numel(), wstream), "yolo_conv_wgrad")
-            if overlap:
-                e_w = torch.cuda.Event()
-                e_w.record(side_s)
-                busy[id(dz)] = e_w
+                                        cout, k, s, code, plan.wg_ws.data_ptr(), plan.wg_ws.numel(), stream), "yolo_conv_wgrad")
             grads[id(cv.weight)] = dw
             done(cv.weight)
         # ---------------------------------------------------------------- dgrad into the input's gradient
@@ -546,11 +533,11 @@ def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_inpu
                     d.flags |= L.FLAG_RESIDUAL
                 P = bmap.get(i)
                 rows = 0
-                if P is not None and P >= first_needed and not overlap:
-                    rl = plan.__dict__.setdefault("_brows", {}).get((i, d.flags))
+                if P is not None and P >= first_needed:
+                    rl = plan.brows.get((i, d.flags))
                     if rl is None:
                         ldv = C.c_int(0)
-                        rl = plan._brows[(i, d.flags)] = (L.lib().yolo_conv_bstats_rows(d, C.byref(ldv)), ldv.value)
+                        rl = plan.brows[(i, d.flags)] =(L.lib().yolo_conv_bstats_rows(d, C.byref(ldv)), ldv.value)
                     rows, rld_ = rl
                 if rows:
                     pst = plan.stats[P]
@@ -570,12 +557,8 @@ def _backward(state, model, plan: TrainPlan, dpreds, need, seeds=None, want_inpu
                                                cin, cout, code, stream), "yolo_conv_dgrad_s2")
         # the gradient of this block's output is consumed: recycle its buffer (unless shared with a concat slice
         # whose other producer has not been processed yet)
-        if yv is not None and op["out_mode"] != L.OUT_UPSAMPLE2X and not _shared_later(prog, i, yv.buf):
+        if yv is not None and not _shared_later(prog, i, yv.buf):
             G.release(yv.buf)
-        elif yv is not None and op["out_mode"] == L.OUT_UPSAMPLE2X and not _shared_later(prog, i, yv.buf):
-            G.release(yv.buf)
-    if overlap:
-        main_s.wait_stream(side_s)                                     # join: every gradient is ready in main-stream order
     gin = G.state.get(prog.input.buf)
     return grads, (gin[1] if (want_input_grad and gin is not None and gin[0] == "own") else None)
 
@@ -613,6 +596,7 @@ class YoloTrainFn(torch.autograd.Function):
             raise RuntimeError("yolo_for_turbines_amd: a newer train-mode forward of the same (batch, size, dtype) has overwritten "
                                "the activations this backward needs (one set of buffers per shape): call backward() before the "
                                "next forward, or run the second forward under torch.no_grad() / model.eval()")
+        plan.check_guard()
         flags = tuple(ctx.needs_input_grad[2:])
         need = {id(p): f for p, f in zip(plist, flags)}
         with torch.cuda.device(plan.device):
@@ -621,11 +605,11 @@ class YoloTrainFn(torch.autograd.Function):
             # without a collective - they give every gradient a fixed address, which is what lets the table be replayed.
             buckets = None
             if state.ddp is not None or _TAPE:
-                cached = plan.__dict__.setdefault("_orders", {}).get(flags)
-                if cached is None or cached[2] is not plist:
+                cached = plan.orders.get(flags)
+                if cached is None:
                     order = _bucket_order(plan, need)
-                    cached = plan._orders[flags] = (order, tuple(id(p) for p in order), plist)
-                order, sig = cached[0], cached[1]
+                    cached = plan.orders[flags] = (order, tuple(id(p) for p in order))
+                order, sig = cached
                 buckets = plan.buckets
                 if buckets is None or buckets.signature != sig:      # first backward, or the trainable set changed (unfreeze)
                     from .dist import GradBuckets
@@ -649,7 +633,7 @@ def _backward_taped(state, model, plan, dpreds, need, flags, plist, buckets):
     key = (flags, tuple(None if d is None else tuple(d.stride()) for d in dps))
     stream = L.current_stream()
     got = plan.bwd_tapes.get(key)
-    if got is not None and got[0].fresh():
+    if got is not None:
         tape = got[0]
         slots = {f"dp{k}": d.data_ptr() for k, d in enumerate(dps) if d is not None}
         lo = 0
@@ -671,31 +655,10 @@ def _backward_taped(state, model, plan, dpreds, need, flags, plist, buckets):
             tape.slot(f"dp{k}", lo_addr, span)
     grads, _ = _backward(state, model, plan, dps, need, buckets=buckets, tape=tape)
     out = [grads.get(id(p)) if need[id(p)] else None for p in plist]
-    tape.guard(list(model.parameters()) + list(model.buffers()))
     if len(plan.bwd_tapes) >= 2:                                     # each table keeps its temporaries alive: bound them
         plan.bwd_tapes.pop(next(iter(plan.bwd_tapes)))
     plan.bwd_tapes[key] = (tape.finish(),)
     return out
-
-
-def _same_params(plan, plist):
-    """Cheap identity check of a cached ``list(model.parameters())``: the plan's blocks are in module order, so their own
-    parameter dictionaries (conv.weight, [conv.bias], [bn.weight, bn.bias]) enumerate the same objects in the same order."""
-    i = 0
-    n = len(plist)
-    for blk in plan.blocks:
-        mods = blk._modules
-        cp = mods["conv"]._parameters
-        if blk.batch_norm_act:
-            bp = mods["batch_norm"]._parameters
-            own = (cp["weight"], bp["weight"], bp["bias"])
-        else:
-            own = (cp["weight"], cp["bias"])
-        for prm in own:
-            if i >= n or plist[i] is not prm:
-                return False
-            i += 1
-    return i == n
 
 
 def forward_train(state, model, x):
@@ -714,14 +677,14 @@ def forward_train(state, model, x):
             if dt != "fp32" and not plan.stem:
                 raise NotImplementedError("the 16-bit path needs the 3->32 stem block as the first layer")
         state._remember(key, plan)
-        # (walking the module tree for model.parameters() costs 1.3 ms per step: the list is cached per plan and checked
-        #  against the parameter count and the identity of its ends - replacing a Parameter object drops the plans anyway
-        #  through the address guards of the launch tables)
-        plist = plan.__dict__.get("_plist")
-        if plist is None or not _same_params(plan, plist):
-            plist = plan._plist = [p for p in model.parameters()]
-        holder = (state, model, plan, plist)
-        preds = YoloTrainFn.apply(x, holder, *plist)
+        # (walking the module tree for model.parameters() costs 1.3 ms per step: the list is cached per plan, next to the
+        #  launch tables, and lives exactly as long as they do - the plan's guard re-reads every parameter and buffer slot of
+        #  the model, so a replaced Parameter or buffer object, moved storage or a changed BatchNorm setting drops list and
+        #  tables together and this step records again)
+        if not plan.check_guard():
+            plan.watch(model)
+        holder = (state, model, plan, plan.plist)
+        preds = YoloTrainFn.apply(x, holder, *plan.plist)
         if state.nan_check == "deferred":
             # The guard's flag read is a host sync that waits for this forward's own kernels, and the loss / backward can only be
             # enqueued after it: ~1 ms of idle queue per eager step. Deferred: the flag goes to pinned host memory behind the
