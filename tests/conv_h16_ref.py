@@ -11,7 +11,8 @@ activations are NHWC, weights OIHW. ``tests/test_conv_h16_ref_host.py`` ties the
 oracle.net.cnn_block, and proves for every integer case below what the GPU test relies on: that the fp32 value ahead of the
 store does not depend on the order of accumulation, and that most of those values need no rounding at the store.
 
-Integer cases: activations in +-{1..8}, weights in {-1, 0, +1}, integer shift and residual, scale in {1, 2, 0.5}. All
+Integer cases: activations and residual in +-{1..xmax} (xmax = 8 unless the case says otherwise: tests/conv_dma_h16_ref.py
+thins the activations of its large-K cases), weights in {-1, 0, +1}, integer shift, scale in {1, 2, 0.5}. All
 partial sums are integers (or halves) far below 2^24, so any fp32 evaluation gives the same bits and the expected output is
 ``torch.Tensor.to(dtype)`` of it. LeakyReLU stays exact in that sense: the kernels compute fmaxf(v, v * 0.1f), one fp32
 rounding of a product, and add the residual in fp32, a second one; ``kernel_steps=True`` states those two roundings.
@@ -94,17 +95,20 @@ def place(buf, v, off):
 # ------------------------------------------------------------------------------------------------------------ the cases
 # kind "fwd": x (B, H, W, cin) -> cout channels. kind "dgrad": dz (B, H, W, cout) -> dx (B, 2H, 2W, cin); x_* is the view of
 # dz, y_* of dx. res: 0 none, 1 a buffer of its own (r_ld, r_off), 2 the output buffer itself (dgrad: accumulate in place).
-# default: tile 0 runs conv_patch_h16.
-Case = collections.namedtuple("Case", "kind name B H W cin cout k stride out act x_ld x_off y_ld y_off res r_ld r_off default")
+# default: tile 0 runs the kernel the table is about (here conv_patch_h16) and must store the bits of the forced tile.
+# xmax: integer activations and residual lie in +-{1..xmax}. tile: the tile id a table forces (0: the test's own choice).
+# The last two fields came later: a case that leaves them at (8, 0) is seeded from the fields before them, as it always was.
+Case = collections.namedtuple("Case", "kind name B H W cin cout k stride out act x_ld x_off y_ld y_off res r_ld r_off default xmax tile")
+SEED_FIELDS = 19
 
 
 def _c(name, B, H, W, cin, cout, k=1, stride=1, out=OUT_NHWC, act=ACT_NONE, x_ld=None, x_off=0, y_ld=None, y_off=0, res=0,
-       r_ld=None, r_off=0, default=False, kind="fwd"):
+       r_ld=None, r_off=0, default=False, kind="fwd", xmax=8, tile=0):
     n, kin = (cin, cout) if kind == "dgrad" else (cout, cin)
     y_ld = y_ld or n
     if res == 2:
         r_ld, r_off = y_ld, y_off
-    return Case(kind, name, B, H, W, cin, cout, k, stride, out, act, x_ld or kin, x_off, y_ld, y_off, res, r_ld or n, r_off, default)
+    return Case(kind, name, B, H, W, cin, cout, k, stride, out, act, x_ld or kin, x_off, y_ld, y_off, res, r_ld or n, r_off, default, xmax, tile)
 
 
 UP, HEAD = OUT_UPSAMPLE2X, OUT_HEAD
@@ -203,12 +207,13 @@ def k_terms(c):
 
 
 def _gen(c, dtype, what):
-    return torch.Generator().manual_seed(zlib.crc32(repr((tuple(c), dtype, what)).encode()))
+    key = tuple(c) if (c.xmax, c.tile) != (8, 0) else tuple(c)[:SEED_FIELDS]
+    return torch.Generator().manual_seed(zlib.crc32(repr((key, dtype, what)).encode()))
 
 
-def _ints(shape, g):
-    v = torch.randint(-8, 8, shape, generator=g)
-    return torch.where(v >= 0, v + 1, v).float()            # +-{1..8}
+def _ints(shape, g, xmax=8):
+    v = torch.randint(-xmax, xmax, shape, generator=g)
+    return torch.where(v >= 0, v + 1, v).float()            # +-{1..xmax}
 
 
 def operands(c, dtype, gauss=False):
@@ -225,11 +230,11 @@ def operands(c, dtype, gauss=False):
         scale, shift = torch.rand(n, generator=g) + 0.5, torch.randn(n, generator=g) * 0.1
         r = torch.randn((c.B, rh, rw, c.r_ld), generator=g).to(tdt)
     else:
-        x = _ints((c.B, c.H, c.W, c.x_ld), g).to(tdt)
+        x = _ints((c.B, c.H, c.W, c.x_ld), g, c.xmax).to(tdt)
         w = torch.randint(-1, 2, wshape, generator=g).float()
         scale = torch.tensor([1.0, 2.0, 0.5])[torch.randint(0, 3, (n,), generator=g)]
         shift = torch.randint(-16, 17, (n,), generator=g).float()
-        r = _ints((c.B, rh, rw, c.r_ld), g).to(tdt)
+        r = _ints((c.B, rh, rw, c.r_ld), g, c.xmax).to(tdt)
     if c.out == OUT_HEAD:
         scale = torch.ones(n)                                # a bare convolution: scale = 1, shift = bias
     return dict(x=x, w=w, scale=scale, shift=shift, r=r if c.res else None)

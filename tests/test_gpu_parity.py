@@ -1951,15 +1951,15 @@ WS_CASES = [  # (B, H, W, cin, cout, stride, residual, act, y_ld, y_off): conv3_
     (1, 40, 24, 64, 24, 1, False, 1, 24, 0),         # 64 -> 24
     (2, 32, 64, 32, 64, 2, False, 1, 64, 0),         # stride 2: 16 x 32 outputs
     (1, 52, 44, 32, 48, 2, False, 2, 64, 16),        # stride 2, ragged, channel padding, view
-    (1, 208, 208, 32, 64, 1, True, 1, 64, 0),        # more tiles (338) than one round of some workgroups: the persistent loop and both buffers
-]
+    (1, 208, 208, 32, 64, 1, True, 1, 64, 0),        # 13 x 26 = 338 tiles on 338 workgroups: one tile each (the persistent loop, from 513
+]                                                    # tiles on, and the second patch buffer: tests/test_gpu_conv_dma_h16.py)
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("case", WS_CASES)
 def test_small_channel_3x3_weights_in_registers(yt, case, dtype):
     """conv3_ws_h16 through the C-ABI (tile 14, and the default tile, which must pick it): image borders (zero page), ragged tiles,
-    persistent workgroups alternating two patch buffers, residual / accumulate, ld / off views, channel padding, stride 2.
+    persistent workgroups (at most 338 tiles here: one tile each), residual / accumulate, ld / off views, channel padding, stride 2.
     Reference: fp64 convolution of the same rounded operands; round 2's kernel (tile 5) within the same tolerance."""
     import torch.nn.functional as F
     from yolo_for_turbines_amd import _lib as L

@@ -120,6 +120,9 @@ int conv_h16_launch_stats(const yolo_conv_desc* d, const void* x, const void* wf
                          (d->y_ld & 7) == 0 && (d->y_off & 7) == 0 && (!residual || ((d->r_ld & 7) == 0 && (d->r_off & 7) == 0));
     if (d->tile == kTileH16Dma && !dma_ok && !dma1_ok)
         return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 8 needs 3x3 stride 1 with more than 64 output channels, or 1x1 with >= 128 input and output channels");
+    // (tile 10 is an A/B id of conv3_dma_h16 alone: on any other convolution it used to run conv_patch_h16 without a word)
+    if (d->tile == kTileH16DmaIdentQuads && !dma_ok)
+        return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 10 needs 3x3 stride 1 with more than 64 output channels and 16-byte rows");
     const bool use_dma = dma_ok && (d->tile >= kTileH16Dma || (d->tile == 0 && !switches().no_dma));
     if (d->tile == kTileH16Ws && !ws_eligible(d, residual)) return fail(YOLO_ERR_UNSUPPORTED, "conv (16-bit): tile 14 needs a 3x3 32 -> 64 (stride 1 / 2) or 64 -> 32 (stride 1) layer, NHWC");
     if (!want_stats && ws_eligible(d, residual)) return conv_ws_launch(d, x, wf, scale, shift, residual, y, nan_flag, s);
