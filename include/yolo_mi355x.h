@@ -591,6 +591,11 @@ int yolo_decode_hw(void* pred, const int64_t* strides5, const float* anchors_3x2
                    int is_pred, float* boxes, int n_total, int box_offset, void* stream);
 int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
                     int write_back, float* boxes, int n_total, void* stream);
+/* The same launch into a row block of a larger buffer: the three scales fill rows [box_offset, box_offset + sum 3 gh gw) of every
+ * image of boxes (B, n_total, 6), nothing else is touched (the views of test-time augmentation share one buffer). box_offset >= 0
+ * and the block inside n_total, else YOLO_ERR_ARG. */
+int yolo_decode3_hw_at(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
+                       int write_back, float* boxes, int n_total, int box_offset, void* stream);
 
 /* Replaces non_max_suppression (utils.py:150-191) with calc_iou (utils.py:38-84) inlined,
  * batched over images. boxes: (B, n, 6) fp32. keep_idx: (B, n) int32, keep_count: (B) int32:
@@ -605,6 +610,54 @@ int yolo_sort_u64(const uint64_t* keys, uint64_t* sorted, int n, void* workspace
 size_t yolo_nms_workspace_bytes(int b, int n);
 int yolo_nms(const float* boxes, int b, int n, double iou_threshold, double obj_threshold, int center,
              int32_t* keep_idx, int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- weighted box fusion (csrc/fuse.hip; nothing of the reference) ------------------------------------------------------- */
+/* Merges the candidates of every image into clusters whose box is the score-weighted mean of the members' corners (WBF, Solovyev
+ * et al.). This comment is the contract (DESIGN.md 7.20 has it step by step; tests/fuse_ref.py restates it in numpy). All fp32,
+ * every operation rounded once (written fl), no fused multiply-add, IEEE division.
+ * boxes: (b, n, 6) fp32 rows [x, y, w, h, obj, cls]. A row is a candidate iff (double) obj > obj_threshold (NaN fails); the
+ * candidates are walked in the order of the NMS (obj descending, -0 = +0, ties by ascending row): g = a candidate's rank. Corners are
+ * the NMS's: center != 0: x1 = x - w / 2, y1 = y - h / 2, else x1 = x, y1 = y; x2 = x1 + w, y2 = y1 + h, a = w h.
+ * A cluster holds its founder's class (the float), rank and score, its member count n, S = sum of the members' scores, A[4] = sums
+ * of fl(s corner) and its fused corners F[4]. IoU of a candidate against a cluster, the NMS's expression on F:
+ * inter = max(min(x2, F.x2) - max(x1, F.x1), 0) max(min(y2, F.y2) - max(y1, F.y1), 0), ak = (F.x2 - F.x1) (F.y2 - F.y1),
+ * iou = inter / (((a + ak) - inter) + 1e-6f). Eligible clusters: all if class_agnostic != 0, else those whose class == cls (float
+ * equality). The candidate joins the eligible cluster of largest iou among those with iou > (float) iou_threshold, ties to the one
+ * created first: n += 1, S = fl(S + s), A_t = fl(A_t + fl(s corner_t)), F_t = fl(A_t / S). Otherwise it founds a cluster: n = 1,
+ * S = s, A_t = fl(s corner_t), F_t = corner_t.
+ * Score of a cluster: conf_type 0 fl(S / (float) n), conf_type 1 the founder's score; for n_views > 0 multiplied by
+ * fl((float) min(n, n_views) / (float) n_views).
+ * fused (b, n, 6): rows 0 .. count[b]-1 are the clusters in the order score descending (-0 = +0), ties by founder rank ascending:
+ * [x, y, w, h, score, founder's class] with w = fl(F.x2 - F.x1), h = fl(F.y2 - F.y1) and x = F.x1, y = F.y1, or for center != 0
+ * x = fl(F.x1 + fl(w / 2)), y = fl(F.y1 + fl(h / 2)); members (b, n) int32: n of that row. Rows from count[b] on are zero in
+ * both, so the result is input for yolo_nms, yolo_eval_detections or another fusion with any obj_threshold >= 0. assign (b, n)
+ * int32 or NULL: the output row that input row i joined, -1 for a row that is no candidate.
+ * Outside the bit contract, but terminating and in bounds: non-finite coordinates, and an obj_threshold < 0.
+ * The outputs are fully written by the call; everything is stream-ordered, nothing is read back. n <= 163,456 and b <= 2,047
+ * (the class-sorted ordering of yolo_nms), else YOLO_ERR_UNSUPPORTED. A segment (the candidates of one class of one image; of one
+ * image if class_agnostic) is walked by one wave with its first yolo_fuse_onchip_clusters clusters in LDS and the others in the
+ * workspace, its candidates prefetched yolo_fuse_chunk_candidates at a time. Workspace: 16-byte aligned, its size by
+ * yolo_fuse_workspace_bytes (HOST ONLY, no GPU needed; 0 outside the limits); every byte that is read was written by the call. */
+int yolo_fuse_onchip_clusters(void);
+int yolo_fuse_chunk_candidates(void);
+size_t yolo_fuse_workspace_bytes(int b, int n);
+int yolo_fuse_boxes(const float* boxes, int b, int n, double iou_threshold, double obj_threshold, int center, int class_agnostic,
+                    int n_views, int conf_type, float* fused, int32_t* members, int32_t* count, int32_t* assign, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
+/* ---- test-time augmentation (csrc/tta.hip; nothing of the reference) ---------------------------------------------------- */
+/* A view of a batch: x_nchw (n, c, h, w) fp32 -> out_nchw (n, c, oh, ow), resized and / or mirrored; not in place.
+ * (oh, ow) == (h, w): a mirrored copy, bit-exact. Otherwise bilinear with half-pixel centres and no antialias. Per axis, in double:
+ * f = (Y + 0.5) (h / oh) - 0.5, s = floor(f), f -= s; s < 0 -> (s, f) = (0, 0); s >= h - 1 -> (h - 1, 0); rows s and
+ * min(s + 1, h - 1), wy = (float) f; columns likewise. fp32, one rounding per operation: top = fl(fl(fl(1 - wx) p00) + fl(wx p01)),
+ * bot likewise from the second row, value = fl(fl(fl(1 - wy) top) + fl(wy bot)), stored at
+ * (flip_ud ? oh - 1 - Y : Y, flip_lr ? ow - 1 - X : X). */
+int yolo_tta_view(const float* x_nchw, int n, int c, int h, int w, float* out_nchw, int oh, int ow, int flip_lr, int flip_ud,
+                  void* stream);
+/* Boxes of a mirrored view back to the frame: rows [row_offset, row_offset + rows) of every image of a (b, n_total, 6) buffer of
+ * centre-format rows get cx <- fl(1 - cx) if flip_lr and cy <- fl(1 - cy) if flip_ud; nothing else is touched. (Decoded boxes
+ * are normalised per axis: a resized view needs no unmapping.) */
+int yolo_boxes_unflip(float* boxes, int b, int n_total, int row_offset, int rows, int flip_lr, int flip_ud, void* stream);
 
 /* ---- tiled detection of frames larger than the network input (nothing of the reference: its dataset was tiled offline) -- */
 /* HOST ONLY, no launch. Overlapping tiles of an h x w image: returns their number and, when origins_yx (HOST, may be NULL)

@@ -218,11 +218,20 @@ _SIGS = {
                                  C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "yolo_decode3_hw": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int,
                                   C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "yolo_decode3_hw_at": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "yolo_nms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_sort_u64_workspace_bytes": (C.c_size_t, [C.c_int]),
     "yolo_sort_u64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_fuse_onchip_clusters": (C.c_int, []),
+    "yolo_fuse_chunk_candidates": (C.c_int, []),
+    "yolo_fuse_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "yolo_fuse_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_tta_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_boxes_unflip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_tile_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "yolo_tile_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_tile_collect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -206,13 +206,14 @@ int yolo_decode3_ex(void* const* preds3, const int64_t* strides15, const float* 
     return yolo_decode3_hw(preds3, strides15, anchors3, hw6, b, nc, write_back, boxes, n_total, stream);
 }
 
-int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
-                    int write_back, float* boxes, int n_total, void* stream) {
+// the three scales into rows [first, first + sum 3 gh gw) of every image; `whole`: that must be the whole buffer
+static int decode3_launch(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
+                          int write_back, float* boxes, int n_total, long long first, bool whole, void* stream) {
     if (!preds3 || !strides15 || !anchors3 || !grids_hw6 || !boxes || b <= 0 || nc < 1) return fail(YOLO_ERR_ARG, "decode3: bad arguments");
     Decode3Args a;
     a.B = b; a.nc = nc; a.n_total = n_total; a.boxes = boxes; a.is_pred = write_back ? 1 : 2;
     long long blocks = 0;
-    long long off = 0;
+    long long off = first;
     for (int k = 0; k < 3; ++k) {
         const int gh = grids_hw6[2 * k], gw = grids_hw6[2 * k + 1];
         if (!preds3[k] || !anchors3[k] || gh <= 0 || gw <= 0) return fail(YOLO_ERR_ARG, "decode3: bad scale %d", k);
@@ -224,12 +225,24 @@ int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* 
         off += 3LL * gh * gw;
         blocks += ((long long)b * 3 * gh * gw + 63) / 64;
     }
-    if (off != n_total) return fail(YOLO_ERR_ARG, "decode3: n_total %d != sum of 3 gh gw = %lld", n_total, off);
+    if (whole && off != n_total) return fail(YOLO_ERR_ARG, "decode3: n_total %d != sum of 3 gh gw = %lld", n_total, off);
+    if (off > n_total) return fail(YOLO_ERR_ARG, "decode3: rows [%lld, %lld) outside n_total %d", first, off, n_total);
     if (blocks > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "decode3: too many cells");
     const size_t lds = (size_t)64 * (5 + nc) * sizeof(float);
     if (lds > 64 * 1024) return fail(YOLO_ERR_UNSUPPORTED, "decode: %d classes exceed the staging tile", nc);
     hipLaunchKernelGGL(decode3_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);
     return check_launch("decode3");
+}
+
+int yolo_decode3_hw(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
+                    int write_back, float* boxes, int n_total, void* stream) {
+    return decode3_launch(preds3, strides15, anchors3, grids_hw6, b, nc, write_back, boxes, n_total, 0, true, stream);
+}
+
+int yolo_decode3_hw_at(void* const* preds3, const int64_t* strides15, const float* const* anchors3, const int* grids_hw6, int b, int nc,
+                       int write_back, float* boxes, int n_total, int box_offset, void* stream) {
+    if (box_offset < 0) return fail(YOLO_ERR_ARG, "decode3: box_offset %d", box_offset);
+    return decode3_launch(preds3, strides15, anchors3, grids_hw6, b, nc, write_back, boxes, n_total, box_offset, false, stream);
 }
 
 }  // extern "C"
