@@ -564,6 +564,28 @@ int yolo_sgd_step_clip(const void* items_dev, int n_items, const int32_t* chunks
                        const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
                        const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream);
 int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const void* clip_state_dev, void* stream);
+/* Adam / AdamW (torch.optim.Adam / AdamW as PyTorch runs them by default on the GPU: foreach, not capturable, not fused), the
+ * same bits; the rounding of every pass is listed in csrc/optim_adam.hip. Two launches per parameter group over the tables of
+ * the SGD step. items (device): n_items x yolo_sgd_item {p, g, exp_avg, n}, FOLLOWED by n_items x float* (exp_avg_sq of each
+ * item), so the clip entry points above read the same table; an item with g == NULL is skipped and its step count stays.
+ * yolo_adam_prepare: one thread per item, in front of the step. *found_inf_dev (may be NULL) != 0: nothing moves. Otherwise, for
+ *   every item with a gradient, steps_dev[i] += 1 (int32, t below) and words_dev[8 i .. 8 i + 7] (float, 16-byte aligned) become
+ *   {float(1 - lr*wd), float(1 - beta1), float(beta2), float(1 - beta2), float(eps), float(sqrt(1 - beta2^t)),
+ *   float((lr / (1 - beta1^t)) * -1), float(wd)}, every expression in fp64 with the roundings of the Python expression and one
+ *   cast at the end. hyper5_dev: the group's {lr, beta1, beta2, eps, weight_decay} as doubles in DEVICE memory, read when the
+ *   kernel runs: a launch captured in a HIP graph follows an LR scheduler, and the step count is a device fact that a skipped
+ *   step does not move.
+ * yolo_adam_step: one block per chunk reads the item's words and does the whole update in registers (p, g, exp_avg, exp_avg_sq
+ *   read once; p, exp_avg, exp_avg_sq written once; the gradient is never written). Every option is a pointer that may be NULL:
+ *   grad_scale_dev (g * (float)(1.0 / (double)*grad_scale_dev) first, a rounding of its own), found_inf_dev (set: nothing is
+ *   touched), clip_state_dev (g * coef after the unscale, a rounding of its own, applied also when coef == 1; the state is what
+ *   yolo_clip_finalize left), shadows_dev + ema_state_dev (the weight average of every item with a gradient in the same launch,
+ *   as in the *_ema entry points; both or neither). decoupled != 0: AdamW's p *= 1 - lr*wd; otherwise g += wd * p when wd != 0. */
+int yolo_adam_prepare(const void* items_dev, int n_items, const double* hyper5_dev, int32_t* steps_dev, float* words_dev,
+                      const float* found_inf_dev, void* stream);
+int yolo_adam_step(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* words_dev,
+                   const float* grad_scale_dev, const float* found_inf_dev, const void* clip_state_dev, const void* shadows_dev,
+                   const void* ema_state_dev, int decoupled, int maximize, void* stream);
 
 /* ---- post-processing ------------------------------------------------------------------- */
 /* Replaces cells_to_boxes (utils.py:86-148) for one scale.

@@ -6,7 +6,8 @@ the device in the middle of the step, and the step cannot be captured in a HIP g
 PyTorch's scale arithmetic (`torch._amp_update_scale_`, one device-side kernel) and replaces the rest for a
 :class:`yolo_for_turbines_amd.SGD`: one launch reads the gradients and raises a device flag, the SGD launch reads the flag
 and the scale, unscales in registers and does nothing when the flag is set. Same bits as `torch.amp.GradScaler` +
-`torch.optim.SGD` after every step, skipped steps included.
+`torch.optim.SGD` after every step, skipped steps included. :class:`yolo_for_turbines_amd.Adam` and ``AdamW`` take the same
+path (their step count is a device word that a skipped step leaves alone).
 
 This module is the one place that leans on private members of `torch.amp.GradScaler` (`_per_optimizer_states`, `OptState`,
 `_check_scale_growth_tracker`; PyTorch 2.10); `tests/test_gpu_amp.py` pins the behaviour.
@@ -14,7 +15,7 @@ This module is the one place that leans on private members of `torch.amp.GradSca
 import torch
 from torch.amp.grad_scaler import OptState
 
-from .optim import SGD
+from .optim import NativeOptimizer
 
 
 class GradScaler(torch.amp.GradScaler):
@@ -22,14 +23,14 @@ class GradScaler(torch.amp.GradScaler):
     ``unscale_()`` and ``update()`` are inherited)::
 
         scaler.scale(loss).backward()
-        scaler.step(optimizer)          # yt.SGD: check launch + scaled step, no host wait; anything else: PyTorch's path
+        scaler.step(optimizer)          # yt.SGD / Adam / AdamW: check launch + scaled step, no host wait; anything else: PyTorch's path
         scaler.update()
 
     After a native ``step`` the ``.grad`` tensors still hold the SCALED gradients (PyTorch's ``step`` leaves them unscaled):
     the unscale happens in registers and is not written back. Call ``unscale_(optimizer)`` first to get unscaled gradients
     in memory; ``step`` then uses them as they are. Clipping needs neither: ``yt.SGD(max_grad_norm=...)`` takes the norm in
     the same read as the non-finite check and clips in registers. A skipped step still skips on the device, so
-    ``step`` always returns ``None`` for a ``yt.SGD`` and never reports whether it was applied.
+    ``step`` always returns ``None`` for a native optimizer and never reports whether it was applied.
     """
 
     def __init__(self, device="cuda", init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
@@ -39,7 +40,7 @@ class GradScaler(torch.amp.GradScaler):
         self._native_flags = {}          # id(optimizer) -> its found_inf word: one address for every step, so a capture can hold it
 
     def step(self, optimizer, *args, **kwargs):
-        if not self._enabled or not isinstance(optimizer, SGD):
+        if not self._enabled or not isinstance(optimizer, NativeOptimizer):
             return super().step(optimizer, *args, **kwargs)
         if "closure" in kwargs or args:
             raise RuntimeError("Closure use is not currently supported if GradScaler is enabled.")

@@ -29,36 +29,12 @@
 //   e   = fma(1 - d, p, e * d)                                             e.mul_(d).add_(p, alpha=1 - d)
 // t is advanced by a one-thread launch AFTER every entry has been updated (a later block must still see the old t), and -
 // like everything else - left alone when *found_inf is set: the average counts applied steps.
-#include "common.h"
+#include "optim.h"
 
 namespace yolo {
 
-struct SgdItem { float* p; const float* g; float* buf; long long n; };   // n < 0: the momentum buffer is new (first step): buf = g'
-static_assert(sizeof(SgdItem) == 32, "matches yolo_sgd_item in the header");
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SGD_CHUNK = 4096;          // elements per block: 256 threads x 4 x float4
-
-struct EmaState { int updates; float decay; int warmup; int reserved; };
-static_assert(sizeof(EmaState) == 16, "matches yolo_ema_state in the header");
 struct EmaItem { const void* src; void* dst; long long n; };             // n < 0: copy -n 32-bit words (integer entries)
 static_assert(sizeof(EmaItem) == 24, "matches yolo_ema_item in the header");
-
-// {d, 1 - d} of this update, from the state as it is when the block runs
-__device__ __forceinline__ void ema_coeffs(const EmaState* __restrict__ st, float& d, float& omd) {
-    const u32x4 s = *reinterpret_cast<const u32x4*>(st);
-    const int t = (int)s[0];
-    d = __uint_as_float(s[1]);
-    if (s[2] != 0) {
-        const float q = (float)(1 + t) / (float)(10 + t);
-        if (q < d) d = q;
-    }
-    omd = 1.0f - d;
-}
-
-// e * d is an argument of the fused multiply-add, not a candidate for contraction: it is rounded on its own, like mul_
-__device__ __forceinline__ float ema_one(float e, float p, float d, float omd) { return __builtin_fmaf(omd, p, e * d); }
 
 // EMA: ema (the shadow of p) moves towards the NEW p with the coefficients {ema_d, ema_omd}
 // CLIP: g * coef directly after the unscale, a rounding of its own like it (the grad.mul_(clip_coef) pass of clip_grad_norm_),
@@ -311,9 +287,6 @@ __global__ void ema_advance_kernel(EmaState* __restrict__ state, const float* __
 //             loss-scaled step reads its gradients once for both. INF: the largest |g| in place of the sum, NaN-propagating.
 //   finalize: one block over every group's partials in a fixed order, sqrt, one rounding to fp32, then
 //             coef = min(fl(fl(1 / fl(total + 1e-6f)) * max_norm), 1): torch turns `max_norm / tensor` into reciprocal() * max_norm.
-struct ClipState { float max_norm; float total_norm; float coef; int norm_type; };
-static_assert(sizeof(ClipState) == 16, "matches yolo_clip_state in the header");
-
 template <bool INF>
 __device__ __forceinline__ double clip_combine(double a, double b) {
     if (INF) return (b != b || b > a) ? b : a;           // a NaN on either side stays

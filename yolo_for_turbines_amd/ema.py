@@ -57,7 +57,7 @@ class _RowTable:
 class ModelEMA:
     """``ema = ModelEMA(model, decay=0.9998, warmup=True)``::
 
-        ema.attach(optimizer)      # yt.SGD: optimizer.step() now also moves the average, in the same launch
+        ema.attach(optimizer)      # yt.SGD / Adam / AdamW: optimizer.step() now also moves the average, in the same launch
         ema.update()               # any other optimizer: one standalone launch after optimizer.step()
         ema.module                 # a model in eval mode whose parameters and buffers ARE the averaged tensors
         ema.updates                # updates applied so far (reads the device word: waits for the device)
@@ -147,11 +147,12 @@ class ModelEMA:
 
     # ------------------------------------------------------------------------------------------------------ the user's side
     def attach(self, optimizer):
-        """Let ``optimizer.step()`` (a :class:`yolo_for_turbines_amd.SGD`) move the average: parameters with a gradient in the
+        """Let ``optimizer.step()`` (a :class:`yolo_for_turbines_amd.SGD`, ``Adam`` or ``AdamW``) move the average: parameters with a gradient in the
         step's own launch, everything else in one more."""
-        from .optim import SGD
-        if not isinstance(optimizer, SGD):
-            raise TypeError(f"{_WHO}.attach needs a yolo_for_turbines_amd.SGD; call update() after the step of any other optimizer")
+        from .optim import NativeOptimizer
+        if not isinstance(optimizer, NativeOptimizer):
+            raise TypeError(f"{_WHO}.attach needs a yolo_for_turbines_amd.SGD, Adam or AdamW; call update() after the step of any other "
+                            "optimizer")
         if self._attached is not None and self._attached is not optimizer:
             raise RuntimeError(f"{_WHO}: already attached to another optimizer")
         if getattr(optimizer, "_ema", None) not in (None, self):
@@ -167,7 +168,7 @@ class ModelEMA:
 
     @torch.no_grad()
     def update(self):
-        """One standalone launch over every entry (for optimizers other than ``yt.SGD``)."""
+        """One standalone launch over every entry (for optimizers other than the native ones)."""
         if self._attached is not None:
             raise RuntimeError(f"{_WHO}.update(): attached to an optimizer whose step() already moves the average; calling "
                                "update() as well would average twice")

@@ -25,14 +25,15 @@ class GraphedTrainStep:
     (``torch.bfloat16`` / ``torch.float16`` / None) selects what `train.py:53` selects. Returns the summed loss as a
     0-dim tensor that is overwritten by the next call.
 
-    ``grad_scaler`` (a :class:`yolo_for_turbines_amd.GradScaler`, with a :class:`yolo_for_turbines_amd.SGD`): the step is
+    ``grad_scaler`` (a :class:`yolo_for_turbines_amd.GradScaler`, with a :class:`yolo_for_turbines_amd.SGD`, ``Adam`` or
+    ``AdamW``): the step is
     `train.py:67-69`, ``scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update()``, all of it captured - the
     scale, the growth tracker and the skip decision are device memory read at replay time, so a replay whose gradients
     overflow skips its update and halves the scale like an eager step. The warm-up steps go through the scaler too. The
     returned loss is the unscaled one; ``grad_scaler.get_scale()`` reads the live value (and waits for the device).
 
     ``ema`` (a :class:`yolo_for_turbines_amd.ModelEMA` of ``model``): the weight average moves inside the captured step. With a
-    :class:`yolo_for_turbines_amd.SGD` it is attached to the optimizer (if it is not already) and rides in the step's own
+    :class:`yolo_for_turbines_amd.SGD`, ``Adam`` or ``AdamW`` it is attached to the optimizer (if it is not already) and rides in the step's own
     launch; with any other optimizer the step ends with ``ema.update()``. The warm-up steps go through it like everything
     else, its decay follows the device counter through the replays, and every replay invalidates the packed weights of
     ``ema.module`` along with the live model's.
@@ -44,19 +45,19 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep needs CUDA/HIP tensors (no CPU fallback)")
         if grad_scaler is not None:
             from .amp import GradScaler
-            from .optim import SGD
-            if not isinstance(grad_scaler, GradScaler) or not isinstance(optimizer, SGD):
+            from .optim import NativeOptimizer
+            if not isinstance(grad_scaler, GradScaler) or not isinstance(optimizer, NativeOptimizer):
                 raise TypeError("GraphedTrainStep: grad_scaler must be a yolo_for_turbines_amd.GradScaler stepping a "
-                                "yolo_for_turbines_amd.SGD (torch.amp.GradScaler.step reads its inf flag on the host, which "
-                                "cannot be captured)")
+                                "yolo_for_turbines_amd.SGD, Adam or AdamW (torch.amp.GradScaler.step reads its inf flag on the "
+                                "host, which cannot be captured)")
             if not grad_scaler.is_enabled():
                 raise ValueError("GraphedTrainStep: grad_scaler is disabled; pass grad_scaler=None instead")
         self.scaler = grad_scaler
         self.ema = ema
         self._ema_update = False                        # the step body ends with ema.update() (the optimizer cannot carry it)
         if ema is not None:
-            from .optim import SGD
-            if isinstance(optimizer, SGD):
+            from .optim import NativeOptimizer
+            if isinstance(optimizer, NativeOptimizer):
                 ema.attach(optimizer)                   # raises if it is attached elsewhere
             elif ema._attached is not None:
                 raise RuntimeError("GraphedTrainStep: ema is attached to another optimizer than the one this step runs")
@@ -94,7 +95,7 @@ class GraphedTrainStep:
             self._plan = plans[-1]
             self._plan.pinned = True
             self.graph = torch.cuda.CUDAGraph()
-            # Hyper-parameters across replays: `yt.SGD` keeps them in device memory and reads them when the kernel runs
+            # Hyper-parameters across replays: `yt.SGD` / `yt.Adam` / `yt.AdamW` keep them in device memory and read them when the kernel runs
             # (`sync_hyper` before each replay), so LR schedulers keep working. Any other optimizer bakes its Python floats
             # into the captured kernels: remember them and refuse a replay at different values rather than train silently
             # at the capture-time learning rate.
@@ -155,7 +156,7 @@ class GraphedTrainStep:
         elif self._hyper_snapshot() != self._baked:
             raise RuntimeError("GraphedTrainStep: the optimizer's hyper-parameters changed since the capture "
                                f"({self._baked} -> {self._hyper_snapshot()}) and this optimizer bakes them into the captured "
-                               "kernels; use yolo_for_turbines_amd.SGD (reads them from device memory at every replay) or "
+                               "kernels; use yolo_for_turbines_amd.SGD, Adam or AdamW (they read them from device memory at every replay) or "
                                "capture a new GraphedTrainStep")
         self.x.copy_(x, non_blocking=True)
         for dst, src in zip(self.targets, targets):

@@ -1,4 +1,5 @@
-"""SGD step of the fine-tune loop as one HIP launch (`csrc/optim.hip`).
+"""The optimizer steps of the fine-tune loop as HIP launches: SGD (`csrc/optim.hip`, described first) and Adam / AdamW
+(`csrc/optim_adam.hip`, :class:`Adam`), which share everything but the update itself through :class:`NativeOptimizer`.
 
 Drop-in for `torch.optim.SGD` as the reference constructs it (`code/train.py:171-172`:
 `SGD(model.parameters(), lr, momentum, weight_decay)`, stepped at `:68` through the GradScaler): same constructor,
@@ -26,21 +27,26 @@ import torch
 from . import _lib as L
 
 
+_SGD = "yolo_for_turbines_amd.optim.SGD"
+
+
 class _GroupTable:
     """What one parameter group needs for its launch: the chunk table (built once: tensor sizes never change) and the
     pointer table, which travels host -> device asynchronously every step."""
 
-    def __init__(self, params):
+    def __init__(self, params, who=_SGD, item_shape=None, hyper=(4, torch.float32)):
         dev = params[0].device
         ce = L.lib().yolo_sgd_chunk_elems()
         chunks = []
         for i, p in enumerate(params):
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.device == dev):
-                raise TypeError("yolo_for_turbines_amd.optim.SGD: parameters must be contiguous fp32 tensors on one GPU")
+                raise TypeError(f"{who}: parameters must be contiguous fp32 tensors on one GPU")
             chunks += [(i, s) for s in range(0, p.numel(), ce)]
+        self.who = who
         self.params = list(params)
         self.chunks = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev)
-        self.items = torch.empty((len(params), 4), dtype=torch.int64, device=dev)
+        self.item_shape = item_shape or (len(params), 4)    # int64 words of the row table (SGD: one yolo_sgd_item per parameter)
+        self.items = torch.empty(self.item_shape, dtype=torch.int64, device=dev)
         # eager steps: a ring of pinned buffers, each guarded by the event of its last copy, so the host (which runs ahead of
         # the GPU) never rewrites a table the GPU has not read yet
         self.ring = [[self._pinned(), None] for _ in range(3)]
@@ -50,13 +56,13 @@ class _GroupTable:
         # ever write; pinned memory cannot be allocated inside a capture, so eager steps keep two spares ready
         self.spares = []
         self.captured = []
-        # {lr, momentum, dampening, weight_decay} live in DEVICE memory and the kernel reads them when it runs: a step
-        # captured in a HIP graph then follows the LR scheduler (train.py:71-74 steps LinearLR after every batch) instead of
-        # replaying the capture-time values. Written stream-ordered, outside any capture, whenever the group's values change
-        # (SGD.sync_hyper); pinned staging ring guarded by events like the row tables.
-        self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
+        # {lr, momentum, dampening, weight_decay} (Adam: {lr, beta1, beta2, eps, weight_decay} as doubles) live in DEVICE memory
+        # and the kernel reads them when it runs: a step captured in a HIP graph then follows the LR scheduler (train.py:71-74
+        # steps LinearLR after every batch) instead of replaying the capture-time values. Written stream-ordered, outside any
+        # capture, whenever the group's values change (sync_hyper); pinned staging ring guarded by events like the row tables.
+        self.hyper = torch.zeros(hyper[0], dtype=hyper[1], device=dev)
         self.hyper_host = None                              # the values last pushed
-        self.hyper_ring = [[torch.zeros(4, dtype=torch.float32).pin_memory(), None] for _ in range(4)]
+        self.hyper_ring = [[torch.zeros(hyper[0], dtype=hyper[1]).pin_memory(), None] for _ in range(4)]
         self.hyper_slot = 0
         # loss-scaled steps: written[i] != 0 once parameter i's momentum buffer holds a value (set on the device after an
         # applied step; SGD._table fills it in for buffers the host knows about). device_first: some buffer of this group was
@@ -71,24 +77,25 @@ class _GroupTable:
         self.shadows_of = None
 
     def _pinned(self):
-        return torch.zeros((len(self.params), 4), dtype=torch.int64).pin_memory()
+        return torch.zeros(self.item_shape, dtype=torch.int64).pin_memory()
 
     def matches(self, params):
         return len(self.params) == len(params) and all(a is b for a, b in zip(self.params, params))
 
     def push_hyper(self, values):
-        """Enqueue {lr, momentum, dampening, weight_decay} -> device on the current stream if they changed."""
+        """Enqueue the group's hyper-parameter block -> device on the current stream if it changed."""
         if values == self.hyper_host:
             return
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: the hyper-parameters changed inside a stream capture; call "
+            raise RuntimeError(f"{self.who}: the hyper-parameters changed inside a stream capture; call "
                                "optimizer.sync_hyper() (GraphedTrainStep does) before the replay instead")
         slot = self.hyper_ring[self.hyper_slot]
         self.hyper_slot = (self.hyper_slot + 1) % len(self.hyper_ring)
         if slot[1] is not None:
             slot[1].synchronize()
         h = slot[0]
-        h[0], h[1], h[2], h[3] = values
+        for k, value in enumerate(values):
+            h[k] = value
         self.hyper.copy_(h, non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
@@ -98,7 +105,7 @@ class _GroupTable:
         """(pinned buffer to fill, ring slot or None)."""
         if capturing:
             if not self.spares:
-                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing")
+                raise RuntimeError(f"{self.who}: take one eager step before capturing")
             host = self.spares.pop()
             self.captured.append(host)
             return host, None
@@ -128,7 +135,8 @@ class _ClipState:
     """`yolo_clip_state` in device memory, the pinned ring ``max_norm`` travels through, and the fp64 workspace of the
     partial sums. The struct never moves: ``grad_norm`` / ``clip_coef`` are views of it and a captured graph points at it."""
 
-    def __init__(self, dev):
+    def __init__(self, dev, who=_SGD):
+        self.who = who
         self.words = torch.zeros(4, dtype=torch.float32, device=dev)        # {max_norm, total_norm, coef, norm_type}
         self.words[2:3].fill_(1.0)
         self.grad_norm, self.clip_coef = self.words[1], self.words[2]
@@ -143,7 +151,7 @@ class _ClipState:
         if max_norm == self.max_host:
             return
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: max_grad_norm changed inside a stream capture; call "
+            raise RuntimeError(f"{self.who}: max_grad_norm changed inside a stream capture; call "
                                "optimizer.sync_hyper() (GraphedTrainStep does) before the replay instead")
         slot = self.ring[self.slot]
         self.slot = (self.slot + 1) % len(self.ring)
@@ -159,14 +167,136 @@ class _ClipState:
         """One double per chunk of every group."""
         if self.partials is None or self.partials.numel() < n:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step with max_grad_norm set before capturing")
+                raise RuntimeError(f"{self.who}: take one eager step with max_grad_norm set before capturing")
             if self.partials is not None:
                 self.retired.append(self.partials)
             self.partials = torch.zeros(max(n, 1), dtype=torch.float64, device=self.words.device)
         return self.partials
 
 
-class SGD(torch.optim.SGD):
+class NativeOptimizer:
+    """What the native optimizers (:class:`SGD`, :class:`Adam`, :class:`AdamW`) share, and what ``GradScaler.step``,
+    ``ModelEMA.attach`` and ``GraphedTrainStep`` test for: the group tables with their pinned rings, the hyper-parameter push, the
+    clip state and its launches, the upload of a row table only when it differs, and the pointer table of the weight average.
+    A mixin in front of the ``torch.optim`` class; the subclass provides ``_hyper_of(group)`` and ``step()``."""
+
+    _WHO = _SGD                                             # the name its messages carry
+
+    def _native_init(self, max_grad_norm, grad_norm_type):
+        self._tables = {}                                   # group index -> _GroupTable
+        self._ema = None                                    # ema.ModelEMA.attach: step() moves that average in its own launch
+        # clipping by global norm: plain attributes, looked at by every step() / sync_hyper() (None: today's launches)
+        _clip_args(max_grad_norm, grad_norm_type, self._WHO)
+        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
+        self._clip = None                                   # _ClipState, with the first clipped step (or the first look at grad_norm)
+
+    def forget_uploads(self):
+        """Something else than an eager `step()` wrote the device row tables (a HIP-graph replay copies its captured rows
+        into them): the next eager step uploads its own rows again."""
+        for tab in self._tables.values():
+            tab.uploaded = None
+
+    def sync_hyper(self):
+        """Push every group's current hyper-parameters (SGD: {lr, momentum, dampening, weight_decay}; Adam: {lr, betas, eps,
+        weight_decay}) to the device (stream-ordered, a no-op when nothing changed). `step()` does this itself in eager mode;
+        call it before replaying a HIP graph that captured `step()` whenever an LR scheduler (train.py:71-74,187-189) or the
+        user changed `param_groups` in between."""
+        for gi, group in enumerate(self.param_groups):
+            tab = self._tables.get(gi)
+            if tab is not None:
+                tab.push_hyper(self._hyper_of(group))
+        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, self._WHO)
+        if clip is not None and self._clip is not None:
+            self._clip.push(clip[0])
+
+    def _clip_state(self):
+        if self._clip is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._WHO}: take one eager step with max_grad_norm set before capturing")
+            first = next((p for g in self.param_groups for p in g["params"]), None)
+            if first is None or not first.is_cuda:
+                raise TypeError(f"{self._WHO}: parameters must be contiguous fp32 tensors on one GPU")
+            self._clip = _ClipState(first.device, self._WHO)
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """``total_norm`` of the last clipped step: a 0-dim fp32 device tensor at a fixed address (a view of the clip state),
+        written by the step's own launches; reading it enqueues nothing and waits for nothing."""
+        return self._clip_state().grad_norm
+
+    @property
+    def clip_coef(self):
+        """The coefficient the last clipped step multiplied its gradients by (1 when the norm was within ``max_grad_norm``)."""
+        return self._clip_state().clip_coef
+
+    def _begin(self, tab, hyper, capturing):
+        """In front of the row filling of one group: the hyper-parameter push and the pointer table of the weight average."""
+        if capturing and tab.hyper_host is None:
+            raise RuntimeError(f"{self._WHO}: take one eager step before capturing")
+        if not capturing or hyper != tab.hyper_host:      # inside a capture an unchanged value needs no node at all
+            tab.push_hyper(hyper)
+        if self._ema is not None and tab.shadows_of is not self._ema:
+            if capturing:
+                raise RuntimeError(f"{self._WHO}: take one eager step before capturing (the first step with a "
+                                   "weight average attached uploads its pointer table)")
+            tab.shadows = torch.tensor([L.ptr(self._ema.shadow_of(p)) for p in tab.params], dtype=torch.int64).to(tab.items.device)
+            tab.shadows_of = self._ema
+
+    @staticmethod
+    def _upload(tab, host, slot, rows, capturing):
+        """With gradient buckets / a captured graph every address is the same step after step: upload the table only when it
+        differs from the one the device already holds (an H2D copy costs the GPU ~85 us of idle queue in front of it)."""
+        same = (not capturing) and tab.uploaded is not None and bool((rows == tab.uploaded).all())
+        if not same:
+            tab.items.copy_(host, non_blocking=True)
+            tab.uploaded = None if capturing else rows.copy()
+            if slot is not None:
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+
+    def _flag(self, t, dev, what):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.numel() == 1):
+            raise TypeError(f"{self._WHO}: {what} must be a one-element fp32 tensor on the parameters' GPU")
+        return t
+
+    def _norm(self, ready, clip, grad_scale, check_into):
+        """The launches of a clipped step in front of the update: partial sums per group (with the non-finite check in the same
+        read when ``check_into`` is given), then one finalize over all of them. Returns (clip state, grad_scale)."""
+        lib, st = L.lib(), L.current_stream()
+        max_norm, kind = clip
+        cs = self._clip_state()
+        dev = cs.words.device
+        cs.push(max_norm)
+        total = sum(r[1].chunks.shape[0] for r in ready)
+        ws = cs.workspace(total)
+        scale, check = self._flag(grad_scale, dev, "grad_scale"), self._flag(check_into, dev, "found_inf")
+        if check is not None and not ready:
+            check.zero_()
+        off = 0
+        for k, r in enumerate(ready):                        # every group's norm (and check) before any group is stepped
+            tab = r[1]
+            if tab.hyper.device != dev:
+                raise TypeError(f"{self._WHO}: max_grad_norm needs every parameter group on one GPU")
+            n = tab.chunks.shape[0]
+            L.check(lib.yolo_clip_norm_partials(tab.items.data_ptr(), tab.chunks.data_ptr(), n, L.ptr(scale), kind, ws.data_ptr() + 8 * off,
+                                                L.ptr(check), int(k == 0), st), "yolo_clip_norm_partials")
+            off += n
+        L.check(lib.yolo_clip_finalize(ws.data_ptr(), total, kind, cs.words.data_ptr(), st), "yolo_clip_finalize")
+        return cs, scale
+
+    def _check(self, ready, found_inf):
+        lib = L.lib()
+        if not ready:
+            found_inf.zero_()
+        for k, r in enumerate(ready):
+            tab = r[1]
+            L.check(lib.yolo_sgd_check_finite(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0],
+                                              self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
+                                              L.current_stream()), "yolo_sgd_check_finite")
+
+
+class SGD(NativeOptimizer, torch.optim.SGD):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
                  foreach=None, differentiable=False, fused=None, max_grad_norm=None, grad_norm_type=2.0):
         # foreach / fused select among PyTorch's own implementations: accepted for signature compatibility, irrelevant here
@@ -174,13 +304,8 @@ class SGD(torch.optim.SGD):
             raise ValueError("yolo_for_turbines_amd.optim.SGD: differentiable=True is not supported")
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                          maximize=maximize)
-        self._tables = {}                                   # group index -> _GroupTable
+        self._native_init(max_grad_norm, grad_norm_type)
         self._word = {}                                     # parameter -> its 1-element view of a table's `written`
-        self._ema = None                                    # ema.ModelEMA.attach: step() moves that average in its own launch
-        # clipping by global norm: plain attributes, looked at by every step() / sync_hyper() (None: today's launches)
-        _clip_args(max_grad_norm, grad_norm_type, "yolo_for_turbines_amd.optim.SGD")
-        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
-        self._clip = None                                   # _ClipState, with the first clipped step (or the first look at grad_norm)
 
     def _table(self, gi, params):
         t = self._tables.get(gi)
@@ -197,12 +322,6 @@ class SGD(torch.optim.SGD):
                 self._word[p] = t.written[i:i + 1]
             t.device_first = old is not None and old.device_first
         return t
-
-    def forget_uploads(self):
-        """Something else than an eager `step()` wrote the device row tables (a HIP-graph replay copies its captured rows
-        into them): the next eager step uploads its own rows again."""
-        for tab in self._tables.values():
-            tab.uploaded = None
 
     def _unwritten(self):
         """Parameters whose momentum buffer exists but has never been written (every loss-scaled step so far was skipped).
@@ -250,57 +369,14 @@ class SGD(torch.optim.SGD):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         return (float(group["lr"]), mom, damp, float(group["weight_decay"]))
 
-    def sync_hyper(self):
-        """Push every group's current {lr, momentum, dampening, weight_decay} to the device (stream-ordered, a no-op when
-        nothing changed). `step()` does this itself in eager mode; call it before replaying a HIP graph that captured
-        `step()` whenever an LR scheduler (train.py:71-74,187-189) or the user changed `param_groups` in between."""
-        for gi, group in enumerate(self.param_groups):
-            tab = self._tables.get(gi)
-            if tab is not None:
-                tab.push_hyper(self._hyper_of(group))
-        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, "yolo_for_turbines_amd.optim.SGD")
-        if clip is not None and self._clip is not None:
-            self._clip.push(clip[0])
-
-    def _clip_state(self):
-        if self._clip is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step with max_grad_norm set before capturing")
-            first = next((p for g in self.param_groups for p in g["params"]), None)
-            if first is None or not first.is_cuda:
-                raise TypeError("yolo_for_turbines_amd.optim.SGD: parameters must be contiguous fp32 tensors on one GPU")
-            self._clip = _ClipState(first.device)
-        return self._clip
-
-    @property
-    def grad_norm(self):
-        """``total_norm`` of the last clipped step: a 0-dim fp32 device tensor at a fixed address (a view of the clip state),
-        written by the step's own launches; reading it enqueues nothing and waits for nothing."""
-        return self._clip_state().grad_norm
-
-    @property
-    def clip_coef(self):
-        """The coefficient the last clipped step multiplied its gradients by (1 when the norm was within ``max_grad_norm``)."""
-        return self._clip_state().clip_coef
-
     def _prepare(self, gi, group, scaled):
         """Fill and (if it changed) upload the row table of one group for the gradients as they are now. Returns
         (table, indices of momentum buffers the host marked new, parameters this step updates)."""
         tab = self._table(gi, group["params"])
         mom = float(group["momentum"])
         capturing = torch.cuda.is_current_stream_capturing()
-        hyper = self._hyper_of(group)
-        if capturing and tab.hyper_host is None:
-            raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing")
-        if not capturing or hyper != tab.hyper_host:      # inside a capture an unchanged value needs no node at all
-            tab.push_hyper(hyper)
+        self._begin(tab, self._hyper_of(group), capturing)
         scaled = scaled or tab.device_first
-        if self._ema is not None and tab.shadows_of is not self._ema:
-            if capturing:
-                raise RuntimeError("yolo_for_turbines_amd.optim.SGD: take one eager step before capturing (the first step with a "
-                                   "weight average attached uploads its pointer table)")
-            tab.shadows = torch.tensor([L.ptr(self._ema.shadow_of(p)) for p in tab.params], dtype=torch.int64).to(tab.items.device)
-            tab.shadows_of = self._ema
         host, slot = tab.host_buffer(capturing)
         rows = host.numpy()                              # [p, g, momentum buffer, n] per parameter (yolo_sgd_item)
         updated, fresh = [], []
@@ -336,22 +412,8 @@ class SGD(torch.optim.SGD):
         # the kernel writes through raw pointers: tell PyTorch's version counters (the engine re-packs a weight when its
         # version moves - without this the forward would keep using the weights of step 0)
         torch.autograd.graph.increment_version(updated)
-        # With gradient buckets / a captured graph every address is the same step after step: upload the table only when it
-        # differs from the one the device already holds (an H2D copy costs the GPU ~85 us of idle queue in front of it)
-        same = (not capturing) and tab.uploaded is not None and bool((rows == tab.uploaded).all())
-        if not same:
-            tab.items.copy_(host, non_blocking=True)
-            tab.uploaded = None if capturing else rows.copy()
-            if slot is not None:
-                slot[1] = torch.cuda.Event()
-                slot[1].record()
+        self._upload(tab, host, slot, rows, capturing)
         return tab, fresh, updated
-
-    @staticmethod
-    def _flag(t, dev, what):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.numel() == 1):
-            raise TypeError(f"yolo_for_turbines_amd.optim.SGD: {what} must be a one-element fp32 tensor on the parameters' GPU")
-        return t
 
     @torch.no_grad()
     def step(self, closure=None, *, check_into=None):
@@ -409,24 +471,8 @@ class SGD(torch.optim.SGD):
         """step() with ``max_grad_norm`` set: partial sums per group (with the non-finite check in the same read when
         ``check_into`` is given), one finalize over all of them, then the clip variant of every group's step."""
         lib, st = L.lib(), L.current_stream()
-        max_norm, kind = clip
-        cs = self._clip_state()
+        cs, scale = self._norm(ready, clip, grad_scale, check_into)
         dev = cs.words.device
-        cs.push(max_norm)
-        total = sum(tab.chunks.shape[0] for _, tab, _, _ in ready)
-        ws = cs.workspace(total)
-        scale, check = self._flag(grad_scale, dev, "grad_scale"), self._flag(check_into, dev, "found_inf")
-        if check is not None and not ready:
-            check.zero_()
-        off = 0
-        for k, (_, tab, _, _) in enumerate(ready):           # every group's norm (and check) before any group is stepped
-            if tab.hyper.device != dev:
-                raise TypeError("yolo_for_turbines_amd.optim.SGD: max_grad_norm needs every parameter group on one GPU")
-            n = tab.chunks.shape[0]
-            L.check(lib.yolo_clip_norm_partials(tab.items.data_ptr(), tab.chunks.data_ptr(), n, L.ptr(scale), kind, ws.data_ptr() + 8 * off,
-                                                L.ptr(check), int(k == 0), st), "yolo_clip_norm_partials")
-            off += n
-        L.check(lib.yolo_clip_finalize(ws.data_ptr(), total, kind, cs.words.data_ptr(), st), "yolo_clip_finalize")
         ema = self._ema
         if ema is not None:
             rest = ema._rest({id(p) for r in ready for p in r[3]})
@@ -449,17 +495,187 @@ class SGD(torch.optim.SGD):
         if ema is not None:
             ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
 
-    def _check(self, ready, found_inf):
-        lib = L.lib()
-        if not ready:
-            found_inf.zero_()
-        for k, (_, tab, _, _) in enumerate(ready):
-            L.check(lib.yolo_sgd_check_finite(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0],
-                                              self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
-                                              L.current_stream()), "yolo_sgd_check_finite")
+
+_ADAM_WORDS = 8                                             # fp32 words per parameter that yolo_adam_prepare leaves for the step
 
 
-_FREE_TABLES = {}                                           # (device, ((address, elements), ...)) -> (rows, chunks, partials)
+class _AdamSteps(NativeOptimizer):
+    """`torch.optim.Adam` / `AdamW` as two launches per parameter group (`csrc/optim_adam.hip`): one thread per parameter
+    advances its step count and forms the scalars of this step on the device, then one block per chunk does the whole update in
+    registers. Same bits as PyTorch's default implementation on the GPU (foreach), same ``state`` layout (``step``, ``exp_avg``,
+    ``exp_avg_sq`` per parameter). The step count is a device fact - a step the loss scaler skips does not count, a captured replay
+    counts without the host - so ``state[p]["step"]`` is a 0-dim int32 view of the group's step words; ``state_dict()`` turns it
+    into PyTorch's CPU fp32 scalar and leaves out a parameter whose every step so far was skipped."""
+
+    def _adam_init(self, amsgrad, differentiable, max_grad_norm, grad_norm_type):
+        if amsgrad:
+            raise ValueError(f"{self._WHO}: amsgrad=True is not supported")
+        if differentiable:
+            raise ValueError(f"{self._WHO}: differentiable=True is not supported")
+        self._native_init(max_grad_norm, grad_norm_type)
+
+    def _hyper_of(self, group):
+        lr, betas = group["lr"], group["betas"]
+        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
+            raise TypeError(f"{self._WHO}: lr and betas must be Python numbers, not tensors (the device reads them from its own "
+                            "block; assign a float to param_groups, as LR schedulers do)")
+        if group.get("amsgrad"):
+            raise ValueError(f"{self._WHO}: amsgrad=True is not supported")
+        return (float(lr), float(betas[0]), float(betas[1]), float(group["eps"]), float(group["weight_decay"]))
+
+    def _adopt_steps(self, tab):
+        """The step words of a table from whatever ``state`` holds now (a view of an older table, or the CPU scalar of a loaded
+        ``state_dict``), and ``state`` pointed at the words. May wait for the device: never part of a steady-state step."""
+        counts = [int(self.state[p]["step"]) if "step" in self.state.get(p, {}) else 0 for p in tab.params]
+        tab.steps.copy_(torch.tensor(counts, dtype=torch.int32))
+        for i, p in enumerate(tab.params):
+            if "step" in self.state.get(p, {}):
+                self.state[p]["step"] = tab.steps[i]
+
+    def _table(self, gi, params):
+        t = self._tables.get(gi)
+        if t is None or not t.matches(params):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._WHO}: take one eager step before capturing")
+            n = len(params)
+            # rows: n x yolo_sgd_item {p, g, exp_avg, numel}, then n x exp_avg_sq; hyper: {lr, beta1, beta2, eps, weight_decay}
+            t = _GroupTable(params, self._WHO, item_shape=(5 * n,), hyper=(5, torch.float64))
+            dev = t.items.device
+            t.steps = torch.zeros(n, dtype=torch.int32, device=dev)
+            t.words = torch.zeros((n, _ADAM_WORDS), dtype=torch.float32, device=dev)
+            self._adopt_steps(t)
+            self._tables[gi] = t
+        return t
+
+    def state_dict(self):
+        """`torch.optim.Adam.state_dict()` with ``step`` as PyTorch keeps it (a CPU fp32 scalar), so the result loads into a
+        plain ``torch.optim.Adam`` / ``AdamW``. A parameter whose state was allocated but whose count is still 0 (every step so
+        far was skipped by the loss scaler) is left out: PyTorch's "never stepped". Reads the step words, so it waits for the
+        device: for checkpointing, not for the step."""
+        sd = super().state_dict()
+        counts = {}
+        for tab in self._tables.values():
+            counts.update(zip(map(id, tab.params), tab.steps.tolist()))
+        index, n = {}, 0
+        for group in self.param_groups:
+            for p in group["params"]:
+                if id(p) not in index:
+                    index[id(p)] = n
+                    n += 1
+        for pid, t in counts.items():
+            entry = sd["state"].get(index[pid])
+            if entry is None or "step" not in entry:
+                continue
+            if t == 0:
+                del sd["state"][index[pid]]
+            else:                                            # a new dict: the packed entry IS self.state[p]
+                sd["state"][index[pid]] = dict(entry, step=torch.tensor(float(t), dtype=torch.float32))
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        # the tables stay (their device memory may be part of a captured graph); their step words follow the loaded counts
+        for tab in self._tables.values():
+            self._adopt_steps(tab)
+
+    def _prepare(self, gi, group):
+        """Fill and (if it changed) upload the row table of one group for the gradients as they are now; allocate the moments
+        of a parameter that meets its first gradient. Returns (table, (), parameters this step updates)."""
+        hyper = self._hyper_of(group)                    # refused before anything is allocated
+        tab = self._table(gi, group["params"])
+        capturing = torch.cuda.is_current_stream_capturing()
+        self._begin(tab, hyper, capturing)
+        host, slot = tab.host_buffer(capturing)
+        flat, n = host.numpy(), len(tab.params)
+        rows, second = flat[:4 * n].reshape(n, 4), flat[4 * n:]
+        updated = []
+        for i, p in enumerate(tab.params):
+            g = p.grad
+            if g is None:
+                rows[i, 1] = 0                           # skipped by both kernels, like PyTorch: its count does not move
+                continue
+            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
+                raise TypeError(f"{self._WHO}: gradients must be dense contiguous fp32 on the parameter's GPU")
+            st = self.state[p]
+            if "exp_avg" not in st:
+                if capturing:
+                    raise RuntimeError(f"{self._WHO}: take one eager step before capturing (the first step allocates the moments)")
+                st["step"] = tab.steps[i]
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not all(t.dtype == torch.float32 and t.is_contiguous() and t.device == p.device and t.shape == p.shape for t in (m, v)):
+                raise TypeError(f"{self._WHO}: exp_avg and exp_avg_sq must be contiguous fp32 tensors of the parameter's shape on its GPU")
+            rows[i, 0], rows[i, 1], rows[i, 2], rows[i, 3] = p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel()
+            second[i] = v.data_ptr()
+            updated.append(p)
+        # the kernel writes through raw pointers: tell PyTorch's version counters (the engine re-packs a weight when its
+        # version moves)
+        torch.autograd.graph.increment_version(updated)
+        self._upload(tab, host, slot, flat, capturing)
+        return tab, (), updated
+
+    @torch.no_grad()
+    def step(self, closure=None, *, check_into=None):
+        """Two launches per parameter group. ``self.grad_scale`` / ``self.found_inf`` (set by ``GradScaler.step``), ``check_into``,
+        an attached weight average and ``self.max_grad_norm`` mean what they mean for :meth:`SGD.step`; a skipped step moves no
+        parameter, moment, step count or average."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, self._WHO)                           # refused before anything moves
+        lib, st = L.lib(), L.current_stream()
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
+        ready = [(g,) + self._prepare(gi, g) for gi, g in groups]
+        cs = None
+        if clip is not None:
+            cs, _ = self._norm(ready, clip, grad_scale, check_into)
+        elif check_into is not None:                         # every group is checked before any group is stepped
+            self._check(ready, check_into)
+        ema = self._ema
+        if ema is not None:                                  # what these launches leave over, decided (and uploaded) before them
+            rest = ema._rest({id(p) for r in ready for p in r[3]})
+        for group, tab, _, _ in ready:
+            dev = tab.hyper.device
+            scale, flag = L.ptr(self._flag(grad_scale, dev, "grad_scale")), L.ptr(self._flag(found_inf, dev, "found_inf"))
+            avg = (0, 0) if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
+            n = len(tab.params)
+            L.check(lib.yolo_adam_prepare(tab.items.data_ptr(), n, tab.hyper.data_ptr(), tab.steps.data_ptr(), tab.words.data_ptr(), flag, st),
+                    "yolo_adam_prepare")
+            L.check(lib.yolo_adam_step(tab.items.data_ptr(), n, tab.chunks.data_ptr(), tab.chunks.shape[0], tab.words.data_ptr(), scale, flag,
+                                       0 if cs is None else cs.words.data_ptr(), *avg, int(bool(group.get("decoupled_weight_decay", False))),
+                                       int(bool(group["maximize"])), st), "yolo_adam_step")
+        if ema is not None:                                  # the entries left over, then the counter; both skipped with the step
+            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
+        return loss
+
+
+class Adam(_AdamSteps, torch.optim.Adam):
+    """Drop-in for ``torch.optim.Adam``: same constructor plus ``max_grad_norm`` / ``grad_norm_type`` as on :class:`SGD`.
+    ``foreach`` / ``fused`` / ``capturable`` select among PyTorch's own implementations: accepted, irrelevant here (every step is
+    capturable). ``amsgrad=True`` and ``differentiable=True`` raise ``ValueError``."""
+    _WHO = "yolo_for_turbines_amd.optim.Adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, max_grad_norm=None, grad_norm_type=2.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize,
+                         decoupled_weight_decay=decoupled_weight_decay)
+        self._adam_init(amsgrad, differentiable, max_grad_norm, grad_norm_type)
+
+
+class AdamW(_AdamSteps, torch.optim.AdamW):
+    """Drop-in for ``torch.optim.AdamW`` (Adam with decoupled weight decay, ``p *= 1 - lr * weight_decay``); see :class:`Adam`."""
+    _WHO = "yolo_for_turbines_amd.optim.AdamW"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None, max_grad_norm=None, grad_norm_type=2.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize)
+        self._adam_init(amsgrad, differentiable, max_grad_norm, grad_norm_type)
+
+
+_FREE_TABLES = {}                                          # (device, ((address, elements), ...)) -> (rows, chunks, partials)
 
 
 @torch.no_grad()
