@@ -106,6 +106,8 @@ typedef struct yolo_conv_op {
 } yolo_conv_op;
 
 const char* yolo_last_error(void);
+/* 101: the six SGD step entry points of 100 (by value, _hp, _amp, _hp_ema, _amp_ema, _clip) are one, yolo_sgd_step, with the
+ * argument list the _clip one had and clip_state_dev optional like every other option. */
 int yolo_version(void);
 /* The A/B environment switches (INTEGRATION.md has the table) are read once, when the library is loaded. This writes what was
  * read as "NAME=value\n" per switch, in the table's order (a boolean is 0 / 1 in the sense of its name: YOLO_NO_DMA=1 means the
@@ -490,48 +492,41 @@ int yolo_loss_bwd_opts(const float* pred, const int64_t* strides5, const float* 
 /* One launch over every parameter tensor; the same bits as torch.optim.SGD's default implementation (each of its passes
  * rounds a + alpha * b once). items (device): n_items x yolo_sgd_item; an item with g == NULL is skipped; n < 0 marks a
  * momentum buffer that does not exist yet (first step: buf = g + wd * p). chunks (device): n_chunks x {item index, first
- * element}, one per yolo_sgd_chunk_elems() elements of every item. */
+ * element}, one per yolo_sgd_chunk_elems() elements of every item.
+ * yolo_sgd_step: one block per chunk does the whole update in registers (p, g, buf read once; p, buf written once; the gradient
+ *   is never written). hyper4_dev: {lr, momentum, dampening, weight_decay} as a 16-byte aligned float[4] in DEVICE memory, read
+ *   when the kernel runs: a launch captured in a HIP graph then follows the LR scheduler of train.py:71-74,187-189 (stepped after
+ *   every batch) instead of replaying the capture-time values. nesterov needs momentum > 0 and dampening == 0 (the caller's
+ *   responsibility: the values are not on the host). Every option is a pointer that may be NULL:
+ *   grad_scale_dev (fp16 loss scaling without a host wait, torch.amp.GradScaler, train.py:39,67-69: g * (float)(1.0 /
+ *   (double)*grad_scale_dev) first, a rounding of its own; NULL, or a scale of 1: no unscale), found_inf_dev (set: nothing is
+ *   touched), written_dev ("first step" as a device fact: written_dev[i] == 0 means item i's momentum buffer was never written,
+ *   buf = g + wd * p, and n of an item may then have either sign; a second small launch sets the word to 1 for every item with a
+ *   gradient after a step that was applied; needs found_inf_dev; NULL: the sign of n says "first step"), clip_state_dev (g * coef
+ *   after the unscale, a rounding of its own, applied also when coef == 1; the state is what yolo_clip_finalize left),
+ *   shadows_dev + ema_state_dev (the weight average below of every item with a gradient moved in the same launch, towards the
+ *   NEW parameter value; shadows_dev: n_items x float*, the average of each item's parameter, NULL entry: plain update; both or
+ *   neither; `updates` is not advanced: the caller finishes the update with yolo_ema_update).
+ * yolo_sgd_check_finite: one launch over the same tables; *found_inf_dev (float) becomes 1.0f when any gradient holds an inf
+ *   or a NaN (exponent bits all ones). clear != 0: a one-thread launch sets the word to 0.0f first (stream-ordered,
+ *   capturable); clear == 0 adds to what an earlier call (another parameter group) found. Nothing else is written. */
 typedef struct yolo_sgd_item { float* p; const float* g; float* buf; long long n; } yolo_sgd_item;
 int yolo_sgd_chunk_elems(void);
-int yolo_sgd_step(const void* items_dev, const int32_t* chunks_dev, int n_chunks, float lr, float momentum, float dampening,
-                  float weight_decay, int nesterov, int maximize, void* stream);
-/* The same update with {lr, momentum, dampening, weight_decay} read from DEVICE memory (16-byte aligned float[4]) when the
- * kernel runs: a launch captured in a HIP graph then follows the LR scheduler of train.py:71-74,187-189 (stepped after
- * every batch) instead of replaying the capture-time values. nesterov needs momentum > 0 and dampening == 0 (caller's
- * responsibility here: the values are not on the host). */
-int yolo_sgd_step_hp(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, int nesterov, int maximize,
-                     void* stream);
-/* fp16 loss scaling without a host wait (torch.amp.GradScaler, train.py:39,67-69).
- * yolo_sgd_check_finite: one launch over the same tables; *found_inf_dev (float) becomes 1.0f when any gradient holds an inf
- * or a NaN (exponent bits all ones). clear != 0: a one-thread launch sets the word to 0.0f first (stream-ordered,
- * capturable); clear == 0 adds to what an earlier call (another parameter group) found. Nothing else is written.
- * yolo_sgd_step_amp: the update of yolo_sgd_step_hp with g * (float)(1.0 / (double)*grad_scale_dev) in front of it as a
- * rounding of its own (grad_scale_dev == NULL, or a scale of 1: no unscale); the gradient is not written back.
- * *found_inf_dev != 0: nothing is touched. "First step" is a device fact here: written_dev[i] == 0 means item i's momentum
- * buffer was never written (buf = g + wd * p); a second small launch sets it to 1 for every item with a gradient after a
- * step that was applied. n of an item may be given with either sign. */
+int yolo_sgd_step(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                  const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
+                  const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream);
 int yolo_sgd_check_finite(const void* items_dev, const int32_t* chunks_dev, int n_chunks, float* found_inf_dev, int clear, void* stream);
-int yolo_sgd_step_amp(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                      const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, int nesterov, int maximize,
-                      void* stream);
 /* Weight average (an exponential moving average of every parameter and BatchNorm statistic), fp32, bit for bit
  * e.mul_(d).add_(p, alpha = 1 - d) of PyTorch on the GPU:
  *   d = warmup ? min(decay, float(1 + updates) / float(10 + updates)) : decay;   e = fma(1 - d, p, e * d)
  * The yolo_ema_state lives in device memory, 16-byte aligned, and is read when a kernel runs, never passed by value: a launch captured in a HIP
  * graph follows the warm-up of the decay through its replays.
- * yolo_sgd_step_hp_ema / yolo_sgd_step_amp_ema: the steps above with the average of every item that has a gradient moved in
- * the same launch, towards the NEW parameter value. shadows_dev: n_items x float*, the average of each item's parameter
- * (NULL entry: plain update). Neither advances `updates`: the caller finishes the update with yolo_ema_update.
+ * yolo_sgd_step with shadows_dev + ema_state_dev moves the average of what it updates in its own launch and leaves `updates` alone.
  * yolo_ema_update: one launch over n_chunks chunks of a table of yolo_ema_item rows (chunks as for the step); n > 0: n floats
  * are averaged, n < 0: -n 32-bit words are copied (integer entries). advance != 0: a one-thread launch then adds 1 to
  * `updates`. found_inf_dev (may be NULL) != 0: nothing is written and nothing is counted, like the skipped step. */
 typedef struct yolo_ema_state { int32_t updates; float decay; int32_t warmup; int32_t reserved; } yolo_ema_state;
 typedef struct yolo_ema_item { const void* src; void* dst; long long n; } yolo_ema_item;
-int yolo_sgd_step_hp_ema(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, const void* shadows_dev,
-                         const void* ema_state_dev, int nesterov, int maximize, void* stream);
-int yolo_sgd_step_amp_ema(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                          const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, const void* shadows_dev,
-                          const void* ema_state_dev, int nesterov, int maximize, void* stream);
 int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chunks, void* ema_state_dev, const float* found_inf_dev,
                     int advance, void* stream);
 /* Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type, error_if_nonfinite=False)
@@ -550,19 +545,13 @@ int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chun
  *   yolo_sgd_check_finite into it (clear as there). No atomics: the same bits every run.
  * yolo_clip_finalize: one block reduces n_partials doubles (every group's, laid out one after the other) in a fixed order and
  *   writes total_norm, coef and norm_type. n_partials == 0: total_norm = 0.
- * yolo_sgd_step_clip: the update of yolo_sgd_step_hp with g * coef (a rounding of its own, applied also when coef == 1) directly
- *   after the unscale. Every option of the other entry points is a pointer that may be NULL: grad_scale_dev, found_inf_dev
- *   (set: nothing is touched), written_dev (as in yolo_sgd_step_amp, needs found_inf_dev; NULL: the sign of n says "first
- *   step"), shadows_dev + ema_state_dev (as in the *_ema entry points; both or neither).
+ * yolo_sgd_step / yolo_adam_step with clip_state_dev: the update with g * coef in registers, as described there.
  * yolo_clip_scale_grads: g *= coef in place for every item with a gradient (p and buf of the items are not looked at). */
 enum { YOLO_NORM_L2 = 0, YOLO_NORM_INF = 1 };
 typedef struct yolo_clip_state { float max_norm; float total_norm; float coef; int32_t norm_type; } yolo_clip_state;
 int yolo_clip_norm_partials(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* grad_scale_dev, int norm_type,
                             double* partials_dev, float* found_inf_dev, int clear, void* stream);
 int yolo_clip_finalize(const double* partials_dev, int n_partials, int norm_type, void* clip_state_dev, void* stream);
-int yolo_sgd_step_clip(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                       const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
-                       const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream);
 int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const void* clip_state_dev, void* stream);
 /* Adam / AdamW (torch.optim.Adam / AdamW as PyTorch runs them by default on the GPU: foreach, not capturable, not fused), the
  * same bits; the rounding of every pass is listed in csrc/optim_adam.hip. Two launches per parameter group over the tables of
@@ -580,7 +569,7 @@ int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int 
  *   grad_scale_dev (g * (float)(1.0 / (double)*grad_scale_dev) first, a rounding of its own), found_inf_dev (set: nothing is
  *   touched), clip_state_dev (g * coef after the unscale, a rounding of its own, applied also when coef == 1; the state is what
  *   yolo_clip_finalize left), shadows_dev + ema_state_dev (the weight average of every item with a gradient in the same launch,
- *   as in the *_ema entry points; both or neither). decoupled != 0: AdamW's p *= 1 - lr*wd; otherwise g += wd * p when wd != 0. */
+ *   as in yolo_sgd_step; both or neither). decoupled != 0: AdamW's p *= 1 - lr*wd; otherwise g += wd * p when wd != 0. */
 int yolo_adam_prepare(const void* items_dev, int n_items, const double* hyper5_dev, int32_t* steps_dev, float* words_dev,
                       const float* found_inf_dev, void* stream);
 int yolo_adam_step(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* words_dev,

@@ -13,13 +13,14 @@ def test_amp_symbols_are_declared_exported_and_bound():
     g.build()
     from yolo_for_turbines_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "yolo_mi355x.h")).read()
-    for name in ("yolo_sgd_check_finite", "yolo_sgd_step_amp"):
+    for name in ("yolo_sgd_check_finite", "yolo_sgd_step"):
         assert re.search(r"\bint %s\s*\(" % name, hdr), name
         assert name in _lib.EXPORTS and hasattr(_lib.lib(), name)
     # argument errors come back as codes, never as a launch
     assert _lib.lib().yolo_sgd_check_finite(None, None, 1, None, 1, None) < 0
     assert b"sgd_check_finite" in _lib.lib().yolo_last_error()
-    assert _lib.lib().yolo_sgd_step_amp(None, 1, None, 1, None, None, None, None, 0, 0, None) < 0
+    assert _lib.lib().yolo_sgd_step(None, 1, None, 1, None, None, None, None, None, None, None, 0, 0, None) < 0    # NULL tables
+    assert b"sgd_step" in _lib.lib().yolo_last_error()
 
 
 def test_grad_scaler_falls_back_to_pytorch_for_other_optimizers():

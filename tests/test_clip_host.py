@@ -13,7 +13,7 @@ import torch
 from tests import clip_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("yolo_clip_norm_partials", "yolo_clip_finalize", "yolo_sgd_step_clip", "yolo_clip_scale_grads")
+NEW = ("yolo_clip_norm_partials", "yolo_clip_finalize", "yolo_sgd_step", "yolo_clip_scale_grads")
 
 
 @pytest.fixture(scope="module")
@@ -57,14 +57,25 @@ def test_entry_points_refuse_bad_arguments_before_any_launch(built):
     assert lib.yolo_clip_norm_partials(ok, ok, -1, 0, 0, ok, 0, 0, 0) < 0
     assert lib.yolo_clip_norm_partials(ok, ok, 1, 0, 2, ok, 0, 0, 0) < 0
     assert lib.yolo_clip_norm_partials(0, ok, 1, 0, 0, ok, 0, 0, 0) < 0 and b"clip_norm_partials" in lib.yolo_last_error()
-    assert lib.yolo_sgd_step_clip(ok, 1, ok, 1, ok, 0, 0, 0, 0, 0, 0, 0, 0, 0) < 0                       # NULL state
-    assert lib.yolo_sgd_step_clip(ok, 1, ok, 1, ok, ok + 8, 0, 0, 0, 0, 0, 0, 0, 0) < 0
-    assert lib.yolo_sgd_step_clip(ok, -1, ok, 1, ok, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0
-    assert lib.yolo_sgd_step_clip(ok, 1, ok, 1, ok, ok, 0, 0, ok, 0, 0, 0, 0, 0) < 0                     # written without found_inf
-    assert lib.yolo_sgd_step_clip(ok, 1, ok, 1, ok, ok, 0, 0, 0, ok, 0, 0, 0, 0) < 0                     # shadows without the EMA state
+    # yolo_sgd_step(items, n_items, chunks, n_chunks, hyper4, clip state, grad_scale, found_inf, written, shadows, ema state, ...)
+    assert lib.yolo_sgd_step(0, 1, 0, 1, ok, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0 and b"sgd_step" in lib.yolo_last_error()   # NULL tables
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, 0, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0                            # NULL hyper-parameters
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok + 4, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0                       # misaligned hyper-parameters
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok + 4, 0, 0, 0, 0, 0, 0, 0, 0, 0) < 0                        # the same without a clip state
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, ok + 8, 0, 0, 0, 0, 0, 0, 0, 0) < 0                       # misaligned clip state
+    assert lib.yolo_sgd_step(ok, -1, ok, 1, ok, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0                          # negative counts
+    assert lib.yolo_sgd_step(ok, 1, ok, -1, ok, ok, 0, 0, 0, 0, 0, 0, 0, 0) < 0
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, ok, 0, 0, ok, 0, 0, 0, 0, 0) < 0                          # written without found_inf
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, 0, 0, 0, ok, 0, 0, 0, 0, 0) < 0
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, ok, 0, 0, 0, ok, 0, 0, 0, 0) < 0                          # shadows without the EMA state
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, 0, 0, 0, 0, 0, ok, 0, 0, 0) < 0                           # the EMA state without shadows
+    assert lib.yolo_sgd_step(ok, 1, ok, 1, ok, 0, 0, 0, 0, ok, ok + 8, 0, 0, 0) < 0                      # misaligned EMA state
     assert lib.yolo_clip_scale_grads(ok, ok, 1, 0, 0) < 0 and b"clip_scale_grads" in lib.yolo_last_error()
     assert lib.yolo_clip_scale_grads(ok, ok, -1, ok, 0) < 0
-    assert lib.yolo_clip_scale_grads(0, 0, 0, ok, 0) == 0 and lib.yolo_sgd_step_clip(0, 0, 0, 0, 0, ok, 0, 0, 0, 0, 0, 0, 0, 0) == 0   # nothing to do
+    assert lib.yolo_clip_scale_grads(0, 0, 0, ok, 0) == 0 and lib.yolo_sgd_step(0, 0, 0, 0, 0, ok, 0, 0, 0, 0, 0, 0, 0, 0) == 0   # nothing to do
+    # a NULL clip state is an option like the others, not an error (no chunks: the argument check is all that runs)
+    assert lib.yolo_sgd_step(ok, 1, ok, 0, ok, 0, 0, 0, 0, 0, 0, 0, 0, 0) == 0
+    assert lib.yolo_sgd_step(ok, 1, ok, 0, ok, ok + 8, 0, 0, 0, 0, 0, 0, 0, 0) < 0                       # but a misaligned one still is
 
 
 def test_sgd_and_free_function_argument_checks():

@@ -1,5 +1,5 @@
 """GPU tests (``-m gpu``) of gradient clipping by global norm (`yolo_for_turbines_amd/optim.py`, the `clip_*` kernels and
-`sgd_step_clip_kernel` of `csrc/optim.hip`): the norm against fp64 through the C ABI, the coefficient against CPU PyTorch bit
+`sgd_step_kernel<EMA, CLIP>` of `csrc/optim.hip`): the norm against fp64 through the C ABI, the coefficient against CPU PyTorch bit
 for bit, the fused step (plain, loss-scaled, with the weight average; skipped steps included) against a twin that does
 ``unscale_`` + ``clip_grads_with_norm_`` + ``torch.optim.SGD.step`` + `tests/ema_ref.py` on plain PyTorch, the free function, and
 the network eagerly and as one captured graph."""

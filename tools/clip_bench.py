@@ -112,13 +112,10 @@ def main():
             if clipped:
                 L.check(lib.yolo_clip_norm_partials(items, chunks, n, scale, 0, cs.partials.data_ptr(), flag, 1, st))
                 L.check(lib.yolo_clip_finalize(cs.partials.data_ptr(), n, 0, cs.words.data_ptr(), st))
-                L.check(lib.yolo_sgd_step_clip(items, len(tab.params), chunks, n, tab.hyper.data_ptr(), cs.words.data_ptr(), scale, *words,
-                                               0, 0, 0, 0, st))
             elif scaled:
                 L.check(lib.yolo_sgd_check_finite(items, chunks, n, flag, 1, st))
-                L.check(lib.yolo_sgd_step_amp(items, len(tab.params), chunks, n, tab.hyper.data_ptr(), scale, flag, tab.written.data_ptr(), 0, 0, st))
-            else:
-                L.check(lib.yolo_sgd_step_hp(items, chunks, n, tab.hyper.data_ptr(), 0, 0, st))
+            L.check(lib.yolo_sgd_step(items, len(tab.params), chunks, n, tab.hyper.data_ptr(), cs.words.data_ptr() if clipped else 0, scale, *words,
+                                      0, 0, 0, 0, st))
         return run, (m, opt, scaler), sum(p.numel() for p in m.parameters())
 
     legs = {k: launches(k) for k in ("a0", "a1", "b0", "b1")}

@@ -85,7 +85,8 @@ def main():
                 ema.update()
         tab = opt._tables[0]
         st = L.current_stream()
-        plain = (tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr())
+        # yolo_sgd_step up to its options: no clip state, no scale, no found_inf, no written words
+        plain = (tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(), 0, 0, 0, 0)
         rest = next(iter(ema._tables.values())) if ema is not None else None
         assert ema is None or len(ema._tables) == 1
 
@@ -94,10 +95,10 @@ def main():
 
         def run():
             if kind == "b":
-                L.check(lib.yolo_sgd_step_hp_ema(*plain, tab.shadows.data_ptr(), ema._state.data_ptr(), 0, 0, st))
+                L.check(lib.yolo_sgd_step(*plain, tab.shadows.data_ptr(), ema._state.data_ptr(), 0, 0, st))
                 update_rest()
                 return
-            L.check(lib.yolo_sgd_step_hp(*plain, 0, 0, st))
+            L.check(lib.yolo_sgd_step(*plain, 0, 0, 0, 0, st))
             if kind == "c":
                 update_rest()
             elif kind == "d":

@@ -15,12 +15,12 @@
 //   p  = fma(-lr, g", p)                   param.add_(grad, alpha=-lr)
 //
 // fp16 loss scaling (torch.amp.GradScaler, train.py:39,67-69) without a host wait: `sgd_check_finite_kernel` reads every
-// gradient once and raises a device word; `sgd_step_amp_kernel` reads that word and the scale, returns untouched when the
+// gradient once and raises a device word; `sgd_step_kernel` reads that word and the scale, returns untouched when the
 // word is set, and otherwise unscales in registers (g * inv_scale, rounded on its own like the separate unscale pass of
 // `_amp_foreach_non_finite_check_and_unscale_`) in front of the chain above. The gradient is not written back.
 //
 // Weight average (EMA of every parameter and BatchNorm statistic; `ema.py`). The step holds the new parameter value in a
-// register when it stores it, so the `*_ema` variants of the two step kernels move the average in the same launch: one more
+// register when it stores it, so its EMA instantiations move the average in the same launch: one more
 // read and one more write per element, 28 bytes where the plain step moves 20. What the optimizer does not own (running
 // statistics, parameters without a gradient, the integer counters) goes through `ema_update_kernel`, one launch over a table
 // of (src, dst, n) rows. The arithmetic, with t = the number of updates applied so far (a device word, read when the
@@ -89,31 +89,54 @@ __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* _
     }
 }
 
-// chunks[c] = (item index, first element): built once per optimizer (sizes never change), the items every step.
-// hyper != nullptr: {lr, momentum, dampening, weight_decay} are read from device memory at EXECUTION time, so a captured
-// launch follows a learning-rate schedule (train.py:71-74 steps a LinearLR warm-up after every batch) instead of replaying
-// the values of the capture; the by-value arguments are then ignored.
+// The step. chunks[c] = (item index, first element): built once per optimizer (sizes never change), the items every step.
+// hyper: {lr, momentum, dampening, weight_decay} in device memory, read at EXECUTION time, so a captured launch follows a
+// learning-rate schedule (train.py:71-74 steps a LinearLR warm-up after every batch) instead of replaying the values of the
+// capture. Every option is a pointer that may be NULL:
+//   found_inf   set: every block returns without touching p, the momentum buffer or the average.
+//   grad_scale  the loss scale: inv_scale is `scale.double().reciprocal().float()` of GradScaler.unscale_, applied in registers;
+//               NULL: inv_scale = 1.0f, and sgd_update then has no unscale rounding at all.
+//   written     who decides "first step" (buf = g', which ignores dampening): written[item] == 0 says the item's momentum buffer
+//               has never been written - a device fact under a loss scale, where a skipped first step leaves it unwritten;
+//               sgd_mark_written_kernel sets the word after a step that was applied, in a launch of its own (a later block of
+//               the same item must still read the old value). NULL: the sign of n says it.
+//   shadows + state (EMA says whether they are given): shadows[item] is the average of that item's parameter, moved in the same
+//               launch (NULL entry: this parameter has none, plain update). An item without a gradient is skipped here like
+//               everywhere; its average is the caller's business (ema_update_kernel).
+//   clip (CLIP says whether it is given): coef is the word the finalize launch left in the clip state. CLIP is a template
+//               parameter because g * coef is a rounding of its own that an unclipped step must not have.
+template <bool EMA, bool CLIP>
 __global__ __launch_bounds__(256) void sgd_step_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
-                                                       const float* __restrict__ hyper, float neg_lr, float momentum, float omd, float wd,
-                                                       int nesterov, int maximize) {
-    if (hyper != nullptr) {
-        const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
-        neg_lr = -h[0]; momentum = h[1]; omd = 1.0f - h[2]; wd = h[3];
-    }
+                                                       const float* __restrict__ hyper, const ClipState* __restrict__ clip,
+                                                       const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                                                       const int* __restrict__ written, float* const* __restrict__ shadows,
+                                                       const EmaState* __restrict__ state, int nesterov, int maximize) {
+    if (found_inf != nullptr && *found_inf != 0.f) return;
+    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
+    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
+    const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
+    const float coef = CLIP ? clip->coef : 1.0f;
     const int2 ck = chunks[blockIdx.x];
     const SgdItem it = items[ck.x];
     if (it.g == nullptr) return;                         // parameter without a gradient this step: skipped, like PyTorch
-    const bool first = it.n < 0;
-    const long long n = first ? -it.n : it.n;
-    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        if (aligned && cnt == 4) sgd_update<true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize);
-        else sgd_update<false>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize);
+    const bool first = written != nullptr ? written[ck.x] == 0 : it.n < 0;
+    const long long n = it.n < 0 ? -it.n : it.n;
+    float* ema = nullptr;
+    float d = 0.f, e_omd = 0.f;
+    if (EMA) {
+        ema = shadows[ck.x];
+        ema_coeffs(state, d, e_omd);
     }
+    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)ema)) & 15) == 0;
+    for_each_quad(ck, n, aligned, [&](long long i0, int cnt, bool vec) {
+        if (EMA && ema != nullptr) {
+            if (vec) sgd_update<true, true, CLIP>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
+            else sgd_update<false, true, CLIP>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
+        } else {
+            if (vec) sgd_update<true, false, CLIP>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
+            else sgd_update<false, false, CLIP>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
+        }
+    });
 }
 
 // One block per chunk, as in the step. A value is non-finite when its exponent bits are all ones: an integer test, which no
@@ -127,65 +150,10 @@ __global__ __launch_bounds__(256) void sgd_check_finite_kernel(const SgdItem* __
     const int2 ck = chunks[blockIdx.x];
     const SgdItem it = items[ck.x];
     if (it.g == nullptr) return;                         // uniform over the block
-    const long long n = it.n < 0 ? -it.n : it.n;
-    const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(it.g);
-    const bool aligned = (((size_t)g) & 15) == 0;
     constexpr unsigned EXP = 0x7f800000u;
     int bad = 0;
-    const long long base = (long long)ck.y + threadIdx.x * 4;
-    if (aligned && (long long)ck.y + SGD_CHUNK <= n) {   // full chunk: four independent 16-byte loads in flight
-        u32x4 v[SGD_CHUNK / 1024];
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r) v[r] = *reinterpret_cast<const u32x4*>(g + base + r * 1024);
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bad |= (v[r][e] & EXP) == EXP;
-    } else {
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-            const long long i0 = base + r * 1024;
-            if (i0 >= n) break;
-            const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-            if (aligned && cnt == 4) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(g + i0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bad |= (v[e] & EXP) == EXP;
-            } else {
-                for (int e = 0; e < cnt; ++e) bad |= (g[i0 + e] & EXP) == EXP;
-            }
-        }
-    }
+    scan_grad_chunk(reinterpret_cast<const unsigned*>(it.g), ck, it.n < 0 ? -it.n : it.n, [&](unsigned bits) { bad |= (bits & EXP) == EXP; });
     if (__syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.0f;
-}
-
-// The step under a loss scale. found_inf (device, never NULL): non-zero -> every block returns without touching p or the
-// momentum buffer. grad_scale (device, may be NULL: the gradients are unscaled already): inv_scale is
-// `scale.double().reciprocal().float()` of GradScaler.unscale_. written[item] == 0: this item's momentum buffer has never
-// been written (buf = g', PyTorch's first applied step, which ignores dampening); sgd_mark_written_kernel sets it after a
-// step that was applied, in a launch of its own (a later block of the same item must still read the old value).
-__global__ __launch_bounds__(256) void sgd_step_amp_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
-                                                           const float* __restrict__ hyper, const float* __restrict__ grad_scale,
-                                                           const float* __restrict__ found_inf, const int* __restrict__ written,
-                                                           int nesterov, int maximize) {
-    if (*found_inf != 0.f) return;
-    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
-    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
-    const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
-    const int2 ck = chunks[blockIdx.x];
-    const SgdItem it = items[ck.x];
-    if (it.g == nullptr) return;
-    const bool first = written[ck.x] == 0;
-    const long long n = it.n < 0 ? -it.n : it.n;
-    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        if (aligned && cnt == 4) sgd_update<true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
-        else sgd_update<false>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
-    }
 }
 
 // One thread per item, after the step: the buffer of every item that had a gradient has now been written, unless the
@@ -195,45 +163,6 @@ __global__ __launch_bounds__(256) void sgd_mark_written_kernel(const SgdItem* __
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_items || *found_inf != 0.f) return;
     if (items[i].g != nullptr) written[i] = 1;
-}
-
-// The two steps above with the weight average moved in the same launch. AMP: the loss-scaled form (found_inf, grad_scale and
-// written as in sgd_step_amp_kernel); otherwise the form of sgd_step_kernel with the hyper-parameters in device memory.
-// shadows[item]: the average of that item's parameter (NULL: this parameter has none, plain update). An item without a
-// gradient is skipped here like everywhere; its average is the caller's business (ema_update_kernel).
-template <bool AMP>
-__global__ __launch_bounds__(256) void sgd_step_ema_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
-                                                           const float* __restrict__ hyper, const float* __restrict__ grad_scale,
-                                                           const float* __restrict__ found_inf, const int* __restrict__ written,
-                                                           float* const* __restrict__ shadows, const EmaState* __restrict__ state,
-                                                           int nesterov, int maximize) {
-    if (AMP && *found_inf != 0.f) return;
-    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
-    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
-    const float inv_scale = (AMP && grad_scale != nullptr) ? (float)(1.0 / (double)*grad_scale) : 1.0f;
-    const int2 ck = chunks[blockIdx.x];
-    const SgdItem it = items[ck.x];
-    if (it.g == nullptr) return;
-    const bool first = AMP ? written[ck.x] == 0 : it.n < 0;
-    const long long n = it.n < 0 ? -it.n : it.n;
-    float* const ema = shadows[ck.x];
-    float d, e_omd;
-    ema_coeffs(state, d, e_omd);
-    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)ema)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        const bool vec = aligned && cnt == 4;
-        if (ema != nullptr) {
-            if (vec) sgd_update<true, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd);
-            else sgd_update<false, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd);
-        } else {
-            if (vec) sgd_update<true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
-            else sgd_update<false>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale);
-        }
-    }
 }
 
 // The average on its own: chunks[c] = (row, first element) as for the step. found_inf may be NULL (no loss scale).
@@ -251,16 +180,11 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const EmaItem* __restri
     }
     const float* __restrict__ p = reinterpret_cast<const float*>(it.src);
     float* __restrict__ e = reinterpret_cast<float*>(it.dst);
-    const long long n = it.n;
     float d, omd;
     ema_coeffs(state, d, omd);
     const bool aligned = ((((size_t)p) | ((size_t)e)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        if (aligned && cnt == 4) {
+    for_each_quad(ck, it.n, aligned, [&](long long i0, int cnt, bool vec) {
+        if (vec) {
             const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
             f32x4 ev = *reinterpret_cast<const f32x4*>(e + i0);
 #pragma unroll
@@ -269,7 +193,7 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const EmaItem* __restri
         } else {
             for (int k = 0; k < cnt; ++k) e[i0 + k] = ema_one(e[i0 + k], p[i0 + k], d, omd);
         }
-    }
+    });
 }
 
 // One thread, after every entry has been updated: an applied update counts.
@@ -318,13 +242,10 @@ __global__ __launch_bounds__(256) void clip_norm_partials_kernel(const SgdItem* 
         return;
     }
     const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
-    const long long n = it.n < 0 ? -it.n : it.n;
-    const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(it.g);
-    const bool aligned = (((size_t)g) & 15) == 0;
     constexpr unsigned EXP = 0x7f800000u;
     int bad = 0;
     double acc = 0.0;
-    auto take = [&](unsigned bits) {
+    scan_grad_chunk(reinterpret_cast<const unsigned*>(it.g), ck, it.n < 0 ? -it.n : it.n, [&](unsigned bits) {
         if (CHECK) bad |= (bits & EXP) == EXP;           // on the value as it lies in memory, like the check launch
         float v = __uint_as_float(bits);
         if (inv_scale != 1.0f) {
@@ -333,31 +254,7 @@ __global__ __launch_bounds__(256) void clip_norm_partials_kernel(const SgdItem* 
         }
         if (INF) acc = clip_combine<true>(acc, (double)__builtin_fabsf(v));
         else { const double d = (double)v; acc = __builtin_fma(d, d, acc); }
-    };
-    const long long base = (long long)ck.y + threadIdx.x * 4;
-    if (aligned && (long long)ck.y + SGD_CHUNK <= n) {   // full chunk: four independent 16-byte loads in flight
-        u32x4 v[SGD_CHUNK / 1024];
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r) v[r] = *reinterpret_cast<const u32x4*>(g + base + r * 1024);
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) take(v[r][e]);
-    } else {
-#pragma unroll
-        for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-            const long long i0 = base + r * 1024;
-            if (i0 >= n) break;
-            const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-            if (aligned && cnt == 4) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(g + i0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) take(v[e]);
-            } else {
-                for (int e = 0; e < cnt; ++e) take(g[i0 + e]);
-            }
-        }
-    }
+    });
     const double sum = clip_block_reduce<INF, 4>(acc);
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
     if (CHECK) {
@@ -394,48 +291,6 @@ __global__ __launch_bounds__(FIN_THREADS) void clip_finalize_kernel(const double
     state->norm_type = INF ? 1 : 0;
 }
 
-// The step with every option behind a pointer that may be NULL: found_inf (set: nothing is touched), grad_scale (unscale in
-// registers), written (who decides "first step": these device words, or the sign of n), shadows + ema (the weight average in
-// the same launch; EMA says whether they are given). coef is the word the finalize launch left in the clip state.
-template <bool EMA>
-__global__ __launch_bounds__(256) void sgd_step_clip_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
-                                                            const float* __restrict__ hyper, const ClipState* __restrict__ clip,
-                                                            const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
-                                                            const int* __restrict__ written, float* const* __restrict__ shadows,
-                                                            const EmaState* __restrict__ state, int nesterov, int maximize) {
-    if (found_inf != nullptr && *found_inf != 0.f) return;
-    const f32x4 h = *reinterpret_cast<const f32x4*>(hyper);
-    const float neg_lr = -h[0], momentum = h[1], omd = 1.0f - h[2], wd = h[3];
-    const float inv_scale = grad_scale != nullptr ? (float)(1.0 / (double)*grad_scale) : 1.0f;
-    const float coef = clip->coef;
-    const int2 ck = chunks[blockIdx.x];
-    const SgdItem it = items[ck.x];
-    if (it.g == nullptr) return;
-    const bool first = written != nullptr ? written[ck.x] == 0 : it.n < 0;
-    const long long n = it.n < 0 ? -it.n : it.n;
-    float* ema = nullptr;
-    float d = 0.f, e_omd = 0.f;
-    if (EMA) {
-        ema = shadows[ck.x];
-        ema_coeffs(state, d, e_omd);
-    }
-    const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)ema)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        const bool vec = aligned && cnt == 4;
-        if (EMA && ema != nullptr) {
-            if (vec) sgd_update<true, true, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
-            else sgd_update<false, true, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, ema, d, e_omd, coef);
-        } else {
-            if (vec) sgd_update<true, false, true>(it.p, it.g, it.buf, i0, 4, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
-            else sgd_update<false, false, true>(it.p, it.g, it.buf, i0, cnt, first, neg_lr, momentum, omd, wd, nesterov, maximize, inv_scale, nullptr, 0.f, 0.f, coef);
-        }
-    }
-}
-
 // g *= coef in place over a chunk table (clip_grad_norm_ for other optimizers): the item's p and buf are not looked at
 __global__ __launch_bounds__(256) void clip_scale_grads_kernel(const SgdItem* __restrict__ items, const int2* __restrict__ chunks,
                                                                const ClipState* __restrict__ clip) {
@@ -445,13 +300,8 @@ __global__ __launch_bounds__(256) void clip_scale_grads_kernel(const SgdItem* __
     if (it.g == nullptr) return;
     const long long n = it.n < 0 ? -it.n : it.n;
     float* __restrict__ g = const_cast<float*>(it.g);
-    const bool aligned = (((size_t)g) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        if (aligned && cnt == 4) {
+    for_each_quad(ck, n, (((size_t)g) & 15) == 0, [&](long long i0, int cnt, bool vec) {
+        if (vec) {
             f32x4 v = *reinterpret_cast<const f32x4*>(g + i0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = v[e] * coef;
@@ -459,7 +309,7 @@ __global__ __launch_bounds__(256) void clip_scale_grads_kernel(const SgdItem* __
         } else {
             for (int e = 0; e < cnt; ++e) g[i0 + e] = g[i0 + e] * coef;
         }
-    }
+    });
 }
 
 }  // namespace yolo
@@ -470,23 +320,28 @@ extern "C" {
 
 int yolo_sgd_chunk_elems(void) { return SGD_CHUNK; }
 
-int yolo_sgd_step(const void* items_dev, const int32_t* chunks_dev, int n_chunks, float lr, float momentum, float dampening,
-                  float weight_decay, int nesterov, int maximize, void* stream) {
-    if (n_chunks == 0) return YOLO_OK;
-    if (!items_dev || !chunks_dev || n_chunks < 0) return fail(YOLO_ERR_ARG, "sgd_step: bad arguments");
-    if (nesterov && (momentum <= 0.f || dampening != 0.f)) return fail(YOLO_ERR_ARG, "sgd_step: nesterov needs momentum > 0 and dampening = 0");
-    hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
-                       (const int2*)chunks_dev, (const float*)nullptr, -lr, momentum, 1.0f - dampening, weight_decay, nesterov, maximize);
+int yolo_sgd_step(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
+                  const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
+                  const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream) {
+    if (((size_t)clip_state_dev & 15) || n_chunks < 0 || n_items < 0) return fail(YOLO_ERR_ARG, "sgd_step: bad arguments");
+    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
+    // the "written" words are advanced by a launch that reads *found_inf; the average needs its table and its state together
+    if (!items_dev || !chunks_dev || !hyper4_dev || ((size_t)hyper4_dev & 15) || (written_dev && !found_inf_dev) ||
+        (!shadows_dev != !ema_state_dev) || ((size_t)ema_state_dev & 15))
+        return fail(YOLO_ERR_ARG, "sgd_step: bad arguments");
+    const dim3 grid((unsigned)n_chunks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SGD_LAUNCH(EMA, CLIP)                                                                                                          \
+    hipLaunchKernelGGL((sgd_step_kernel<EMA, CLIP>), grid, block, 0, st, (const SgdItem*)items_dev, (const int2*)chunks_dev, hyper4_dev, \
+                       (const ClipState*)clip_state_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,                        \
+                       (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize)
+    if (shadows_dev) { if (clip_state_dev) SGD_LAUNCH(true, true); else SGD_LAUNCH(true, false); }
+    else { if (clip_state_dev) SGD_LAUNCH(false, true); else SGD_LAUNCH(false, false); }
+#undef SGD_LAUNCH
+    if (written_dev)
+        hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, (const SgdItem*)items_dev, n_items,
+                           found_inf_dev, (int*)written_dev);
     return check_launch("sgd_step");
-}
-
-int yolo_sgd_step_hp(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, int nesterov, int maximize,
-                     void* stream) {
-    if (n_chunks == 0) return YOLO_OK;
-    if (!items_dev || !chunks_dev || !hyper4_dev || n_chunks < 0 || ((size_t)hyper4_dev & 15)) return fail(YOLO_ERR_ARG, "sgd_step_hp: bad arguments");
-    hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
-                       (const int2*)chunks_dev, hyper4_dev, 0.f, 0.f, 1.f, 0.f, nesterov, maximize);
-    return check_launch("sgd_step_hp");
 }
 
 int yolo_sgd_check_finite(const void* items_dev, const int32_t* chunks_dev, int n_chunks, float* found_inf_dev, int clear, void* stream) {
@@ -496,45 +351,6 @@ int yolo_sgd_check_finite(const void* items_dev, const int32_t* chunks_dev, int 
     hipLaunchKernelGGL(sgd_check_finite_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
                        (const int2*)chunks_dev, found_inf_dev);
     return check_launch("sgd_check_finite");
-}
-
-int yolo_sgd_step_amp(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                      const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, int nesterov, int maximize, void* stream) {
-    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
-    if (!items_dev || !chunks_dev || !hyper4_dev || !found_inf_dev || !written_dev || n_chunks < 0 || n_items < 0 || ((size_t)hyper4_dev & 15))
-        return fail(YOLO_ERR_ARG, "sgd_step_amp: bad arguments");
-    hipLaunchKernelGGL(sgd_step_amp_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
-                       (const int2*)chunks_dev, hyper4_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev, nesterov, maximize);
-    hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const SgdItem*)items_dev, n_items, found_inf_dev, (int*)written_dev);
-    return check_launch("sgd_step_amp");
-}
-
-int yolo_sgd_step_hp_ema(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev, const void* shadows_dev,
-                         const void* ema_state_dev, int nesterov, int maximize, void* stream) {
-    if (n_chunks == 0) return YOLO_OK;
-    if (!items_dev || !chunks_dev || !hyper4_dev || !shadows_dev || !ema_state_dev || n_chunks < 0 || ((size_t)hyper4_dev & 15) ||
-        ((size_t)ema_state_dev & 15))
-        return fail(YOLO_ERR_ARG, "sgd_step_hp_ema: bad arguments");
-    hipLaunchKernelGGL(sgd_step_ema_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
-                       (const int2*)chunks_dev, hyper4_dev, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr,
-                       (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
-    return check_launch("sgd_step_hp_ema");
-}
-
-int yolo_sgd_step_amp_ema(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                          const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev, const void* shadows_dev,
-                          const void* ema_state_dev, int nesterov, int maximize, void* stream) {
-    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
-    if (!items_dev || !chunks_dev || !hyper4_dev || !found_inf_dev || !written_dev || !shadows_dev || !ema_state_dev || n_chunks < 0 ||
-        n_items < 0 || ((size_t)hyper4_dev & 15) || ((size_t)ema_state_dev & 15))
-        return fail(YOLO_ERR_ARG, "sgd_step_amp_ema: bad arguments");
-    hipLaunchKernelGGL(sgd_step_ema_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const SgdItem*)items_dev,
-                       (const int2*)chunks_dev, hyper4_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
-                       (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
-    hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const SgdItem*)items_dev, n_items, found_inf_dev, (int*)written_dev);
-    return check_launch("sgd_step_amp_ema");
 }
 
 int yolo_ema_update(const void* items_dev, const int32_t* chunks_dev, int n_chunks, void* ema_state_dev, const float* found_inf_dev,
@@ -581,30 +397,6 @@ int yolo_clip_finalize(const double* partials_dev, int n_partials, int norm_type
     else
         hipLaunchKernelGGL(clip_finalize_kernel<false>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, partials_dev, n_partials, (ClipState*)clip_state_dev);
     return check_launch("clip_finalize");
-}
-
-int yolo_sgd_step_clip(const void* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* hyper4_dev,
-                       const void* clip_state_dev, const float* grad_scale_dev, const float* found_inf_dev, int32_t* written_dev,
-                       const void* shadows_dev, const void* ema_state_dev, int nesterov, int maximize, void* stream) {
-    if (!clip_state_dev || ((size_t)clip_state_dev & 15) || n_chunks < 0 || n_items < 0) return fail(YOLO_ERR_ARG, "sgd_step_clip: bad arguments");
-    if (n_chunks == 0 || n_items == 0) return YOLO_OK;
-    // the "written" words are advanced by a launch that reads *found_inf; the average needs its table and its state together
-    if (!items_dev || !chunks_dev || !hyper4_dev || ((size_t)hyper4_dev & 15) || (written_dev && !found_inf_dev) ||
-        (!shadows_dev != !ema_state_dev) || ((size_t)ema_state_dev & 15))
-        return fail(YOLO_ERR_ARG, "sgd_step_clip: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (shadows_dev)
-        hipLaunchKernelGGL(sgd_step_clip_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, st, (const SgdItem*)items_dev, (const int2*)chunks_dev,
-                           hyper4_dev, (const ClipState*)clip_state_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
-                           (float* const*)shadows_dev, (const EmaState*)ema_state_dev, nesterov, maximize);
-    else
-        hipLaunchKernelGGL(sgd_step_clip_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, st, (const SgdItem*)items_dev, (const int2*)chunks_dev,
-                           hyper4_dev, (const ClipState*)clip_state_dev, grad_scale_dev, found_inf_dev, (const int*)written_dev,
-                           (float* const*)nullptr, (const EmaState*)nullptr, nesterov, maximize);
-    if (written_dev)
-        hipLaunchKernelGGL(sgd_mark_written_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, (const SgdItem*)items_dev, n_items,
-                           found_inf_dev, (int*)written_dev);
-    return check_launch("sgd_step_clip");
 }
 
 int yolo_clip_scale_grads(const void* items_dev, const int32_t* chunks_dev, int n_chunks, const void* clip_state_dev, void* stream) {

@@ -159,12 +159,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const SgdItem* __restric
         ema_coeffs(state, d, e_omd);
     }
     const bool aligned = ((((size_t)it.p) | ((size_t)it.g) | ((size_t)it.buf) | ((size_t)v) | ((size_t)ema)) & 15) == 0;
-#pragma unroll
-    for (int r = 0; r < SGD_CHUNK / 1024; ++r) {
-        const long long i0 = (long long)ck.y + r * 1024 + threadIdx.x * 4;
-        if (i0 >= n) break;
-        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-        const bool vec = aligned && cnt == 4;
+    for_each_quad(ck, n, aligned, [&](long long i0, int cnt, bool vec) {
         if (EMA && ema != nullptr) {
             if (vec) adam_update<true, true, CLIP>(it.p, it.g, it.buf, v, i0, 4, k, decoupled, maximize, inv_scale, coef, ema, d, e_omd);
             else adam_update<false, true, CLIP>(it.p, it.g, it.buf, v, i0, cnt, k, decoupled, maximize, inv_scale, coef, ema, d, e_omd);
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const SgdItem* __restric
             if (vec) adam_update<true, false, CLIP>(it.p, it.g, it.buf, v, i0, 4, k, decoupled, maximize, inv_scale, coef, nullptr, 0.f, 0.f);
             else adam_update<false, false, CLIP>(it.p, it.g, it.buf, v, i0, cnt, k, decoupled, maximize, inv_scale, coef, nullptr, 0.f, 0.f);
         }
-    }
+    });
 }
 
 }  // namespace yolo

@@ -12,8 +12,9 @@ optimizers use, `optimizer.grad_scale` and `optimizer.found_inf`) the step unsca
 when `found_inf` is set: no host wait, capturable. Whether a momentum buffer has been written yet is then a device fact
 (a skipped first step leaves it unwritten), kept as one int32 word per parameter next to the tables.
 
-With a weight average attached (`ema.ModelEMA.attach`) the same launch also moves the average of every parameter it updates
-(the `_ema` entry points); without one the step is the launches it always was.
+With a weight average attached (`ema.ModelEMA.attach`) the same launch also moves the average of every parameter it updates;
+without one the step is the launches it always was. Every one of these modes is an optional pointer of one entry point,
+`yolo_sgd_step`.
 
 With ``max_grad_norm`` set the step clips by global norm, `torch.nn.utils.clip_grad_norm_` between the unscale and the step,
 without writing a gradient: one launch per group leaves fp64 partial sums (and, under a loss scale, does the non-finite check
@@ -67,7 +68,7 @@ class _GroupTable:
         # loss-scaled steps: written[i] != 0 once parameter i's momentum buffer holds a value (set on the device after an
         # applied step; SGD._table fills it in for buffers the host knows about). device_first: some buffer of this group was
         # allocated by a loss-scaled step, so only the device knows whether it was written - every later step of the group
-        # then goes through the kernel that reads the words.
+        # then hands the words to the kernel.
         self.written = torch.zeros(len(params), dtype=torch.int32, device=dev)
         self.device_first = False
         self.no_inf = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -131,6 +132,17 @@ def _clip_args(max_norm, norm_type, who):
     return m, kind
 
 
+def _grads_of(params, who):
+    """``p.grad`` of every parameter of a group table, which are on one GPU (None: that parameter is skipped this step); TypeError
+    for a gradient the kernels cannot read. One call per group: the walk over the parameters is what a step costs the host."""
+    dev, f32 = params[0].device, torch.float32
+    grads = [p.grad for p in params]
+    for g in grads:
+        if g is not None and (g.is_sparse or g.dtype != f32 or not g.is_contiguous() or g.device != dev):
+            raise TypeError(f"{who}: gradients must be dense contiguous fp32 on the parameter's GPU")
+    return grads
+
+
 class _ClipState:
     """`yolo_clip_state` in device memory, the pinned ring ``max_norm`` travels through, and the fp64 workspace of the
     partial sums. The struct never moves: ``grad_norm`` / ``clip_coef`` are views of it and a captured graph points at it."""
@@ -178,7 +190,9 @@ class NativeOptimizer:
     """What the native optimizers (:class:`SGD`, :class:`Adam`, :class:`AdamW`) share, and what ``GradScaler.step``,
     ``ModelEMA.attach`` and ``GraphedTrainStep`` test for: the group tables with their pinned rings, the hyper-parameter push, the
     clip state and its launches, the upload of a row table only when it differs, and the pointer table of the weight average.
-    A mixin in front of the ``torch.optim`` class; the subclass provides ``_hyper_of(group)`` and ``step()``."""
+    A mixin in front of the ``torch.optim`` class. It owns ``step()``; the subclass provides ``_hyper_of(group)``,
+    ``_prepare(gi, group, scaled)`` -> (table, rows the host marked new, parameters this step updates) and
+    ``_launch(group, tab, fresh, scale, flag, clip, avg, st)``, the update of one group."""
 
     _WHO = _SGD                                             # the name its messages carry
 
@@ -295,6 +309,44 @@ class NativeOptimizer:
                                               self._flag(found_inf, tab.hyper.device, "found_inf").data_ptr(), int(k == 0),
                                               L.current_stream()), "yolo_sgd_check_finite")
 
+    @torch.no_grad()
+    def step(self, closure=None, *, check_into=None):
+        """One launch per parameter group (Adam / AdamW: two). With the tensor attributes ``self.grad_scale`` / ``self.found_inf`` set (what
+        ``GradScaler.step`` hands PyTorch's fused optimizers) the gradients are unscaled in registers (``p.grad`` keeps the
+        scaled values) and nothing is touched when ``found_inf`` is non-zero; without them nothing changes. ``check_into``
+        (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it. With a weight
+        average attached (``ModelEMA.attach``) the same launches also move the average of every parameter they update; one
+        more launch does the entries left over (BatchNorm statistics, parameters without a gradient) and counts the update.
+        With ``self.max_grad_norm`` set, the gradients are clipped by their global norm over all groups (``grad_norm_type`` 2 or
+        inf) between the unscale and everything else, in registers: ``check_into`` then comes from the same read as the norm.
+        A skipped step moves no parameter, momentum buffer or moment, step count or average."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, self._WHO)                           # refused before anything moves
+        st = L.current_stream()
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        scaled = grad_scale is not None or found_inf is not None
+        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
+        ready = [(g,) + self._prepare(gi, g, scaled) for gi, g in groups]
+        cs = None
+        if clip is not None:
+            cs, _ = self._norm(ready, clip, grad_scale, check_into)
+        elif check_into is not None:                         # every group is checked before any group is stepped
+            self._check(ready, check_into)
+        ema = self._ema
+        if ema is not None:                                  # what these launches leave over, decided (and uploaded) before them
+            rest = ema._rest({id(p) for r in ready for p in r[3]})
+        for group, tab, fresh, _ in ready:
+            dev = tab.hyper.device
+            scale, flag = self._flag(grad_scale, dev, "grad_scale"), self._flag(found_inf, dev, "found_inf")
+            avg = (0, 0) if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
+            self._launch(group, tab, fresh, scale, flag, 0 if cs is None else cs.words.data_ptr(), avg, st)
+        if ema is not None:                                  # the entries left over, then the counter; both skipped with the step
+            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
+        return loss
+
 
 class SGD(NativeOptimizer, torch.optim.SGD):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
@@ -380,13 +432,10 @@ class SGD(NativeOptimizer, torch.optim.SGD):
         host, slot = tab.host_buffer(capturing)
         rows = host.numpy()                              # [p, g, momentum buffer, n] per parameter (yolo_sgd_item)
         updated, fresh = [], []
-        for i, p in enumerate(tab.params):
-            g = p.grad
+        for i, (p, g) in enumerate(zip(tab.params, _grads_of(tab.params, _SGD))):
             if g is None:
                 rows[i, 1] = 0                           # skipped by the kernel, like PyTorch
                 continue
-            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
-                raise TypeError("yolo_for_turbines_amd.optim.SGD: gradients must be dense contiguous fp32 on the parameter's GPU")
             n = p.numel()
             rows[i, 0] = p.data_ptr()
             rows[i, 1] = g.data_ptr()
@@ -415,85 +464,22 @@ class SGD(NativeOptimizer, torch.optim.SGD):
         self._upload(tab, host, slot, rows, capturing)
         return tab, fresh, updated
 
-    @torch.no_grad()
-    def step(self, closure=None, *, check_into=None):
-        """One launch per parameter group. With the tensor attributes ``self.grad_scale`` / ``self.found_inf`` set (what
-        ``GradScaler.step`` hands PyTorch's fused optimizers) the gradients are unscaled in registers (``p.grad`` keeps the
-        scaled values) and nothing is touched when ``found_inf`` is non-zero; without them nothing changes. ``check_into``
-        (one fp32 element on the GPU): first run the non-finite check over every group's gradients into it. With a weight
-        average attached (``ModelEMA.attach``) the same launches also move the average of every parameter they update; one
-        more launch does the entries left over (BatchNorm statistics, parameters without a gradient) and counts the update.
-        With ``self.max_grad_norm`` set, the gradients are clipped by their global norm over all groups (``grad_norm_type`` 2 or
-        inf) between the unscale and everything else, in registers: ``check_into`` then comes from the same read as the norm."""
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, "yolo_for_turbines_amd.optim.SGD")   # refused before anything moves
-        lib = L.lib()
-        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
-        scaled = grad_scale is not None or found_inf is not None
-        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
-        ready = [(g,) + self._prepare(gi, g, scaled) for gi, g in groups]
-        if clip is not None:
-            self._step_clipped(ready, clip, grad_scale, found_inf, scaled, check_into)
-            return loss
-        if check_into is not None:                           # every group is checked before any group is stepped
-            self._check(ready, check_into)
-        ema = self._ema
-        if ema is not None:                                  # what these launches leave over, decided (and uploaded) before them
-            rest = ema._rest({id(p) for r in ready for p in r[3]})
-        # with a weight average attached: the `_ema` twins of the two entry points, which take {shadow table, EMA state} too
-        step_amp, step_hp = (lib.yolo_sgd_step_amp, lib.yolo_sgd_step_hp) if ema is None else (lib.yolo_sgd_step_amp_ema, lib.yolo_sgd_step_hp_ema)
-        for group, tab, fresh, _ in ready:
-            dev = tab.hyper.device
-            nest, maxi = int(bool(group["nesterov"])), int(bool(group["maximize"]))
-            avg = () if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
-            what = "yolo_sgd_step" + ("_amp" if scaled or tab.device_first else "_hp") + ("" if ema is None else "_ema")
-            if scaled or tab.device_first:
-                flag = self._flag(found_inf, dev, "found_inf")
-                L.check(step_amp(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(),
-                                 L.ptr(self._flag(grad_scale, dev, "grad_scale")), (flag if flag is not None else tab.no_inf).data_ptr(),
-                                 tab.written.data_ptr(), *avg, nest, maxi, L.current_stream()), what)
-                continue
-            L.check(step_hp(tab.items.data_ptr(), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(), *avg, nest, maxi,
-                            L.current_stream()), what)
-            if len(fresh) == len(tab.params):                # the host marked these buffers new and this step wrote them
-                tab.written.fill_(1)
-            else:
-                for i in fresh:
-                    tab.written[i:i + 1].fill_(1)
-        if ema is not None:                                  # the entries left over, then the counter; both skipped with the step
-            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
-        return loss
-
-    def _step_clipped(self, ready, clip, grad_scale, found_inf, scaled, check_into):
-        """step() with ``max_grad_norm`` set: partial sums per group (with the non-finite check in the same read when
-        ``check_into`` is given), one finalize over all of them, then the clip variant of every group's step."""
-        lib, st = L.lib(), L.current_stream()
-        cs, scale = self._norm(ready, clip, grad_scale, check_into)
-        dev = cs.words.device
-        ema = self._ema
-        if ema is not None:
-            rest = ema._rest({id(p) for r in ready for p in r[3]})
-        flag = self._flag(found_inf, dev, "found_inf")
-        for group, tab, fresh, _ in ready:
-            nest, maxi = int(bool(group["nesterov"])), int(bool(group["maximize"]))
-            avg = (0, 0) if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
-            on_device = scaled or tab.device_first           # "first step" is then the device's to say, as in yolo_sgd_step_amp
-            words = ((flag if flag is not None else tab.no_inf).data_ptr(), tab.written.data_ptr()) if on_device else (0, 0)
-            L.check(lib.yolo_sgd_step_clip(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0],
-                                           tab.hyper.data_ptr(), cs.words.data_ptr(), L.ptr(scale), *words, *avg, nest, maxi, st),
-                    "yolo_sgd_step_clip")
-            if on_device:
-                continue
-            if len(fresh) == len(tab.params):
-                tab.written.fill_(1)
-            else:
-                for i in fresh:
-                    tab.written[i:i + 1].fill_(1)
-        if ema is not None:
-            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
+    def _launch(self, group, tab, fresh, scale, flag, clip, avg, st):
+        """One `yolo_sgd_step`. Under a loss scale, or once a loss-scaled step allocated a buffer of this group, "first step" is the
+        device's to say (the `written` words, with `tab.no_inf` standing in for an absent ``found_inf``); otherwise the host marked
+        the new buffers in the rows, and marks them written here."""
+        on_device = scale is not None or flag is not None or tab.device_first
+        words = ((flag if flag is not None else tab.no_inf).data_ptr(), tab.written.data_ptr()) if on_device else (0, 0)
+        L.check(L.lib().yolo_sgd_step(tab.items.data_ptr(), len(tab.params), tab.chunks.data_ptr(), tab.chunks.shape[0], tab.hyper.data_ptr(),
+                                      clip, L.ptr(scale), *words, *avg, int(bool(group["nesterov"])), int(bool(group["maximize"])), st),
+                "yolo_sgd_step")
+        if on_device:
+            return
+        if len(fresh) == len(tab.params):                    # the host marked these buffers new and this step wrote them
+            tab.written.fill_(1)
+        else:
+            for i in fresh:
+                tab.written[i:i + 1].fill_(1)
 
 
 _ADAM_WORDS = 8                                             # fp32 words per parameter that yolo_adam_prepare leaves for the step
@@ -578,9 +564,10 @@ class _AdamSteps(NativeOptimizer):
         for tab in self._tables.values():
             self._adopt_steps(tab)
 
-    def _prepare(self, gi, group):
+    def _prepare(self, gi, group, scaled):
         """Fill and (if it changed) upload the row table of one group for the gradients as they are now; allocate the moments
-        of a parameter that meets its first gradient. Returns (table, (), parameters this step updates)."""
+        of a parameter that meets its first gradient. Returns (table, (), parameters this step updates). ``scaled`` changes
+        nothing here: the step count is the device's either way."""
         hyper = self._hyper_of(group)                    # refused before anything is allocated
         tab = self._table(gi, group["params"])
         capturing = torch.cuda.is_current_stream_capturing()
@@ -589,13 +576,10 @@ class _AdamSteps(NativeOptimizer):
         flat, n = host.numpy(), len(tab.params)
         rows, second = flat[:4 * n].reshape(n, 4), flat[4 * n:]
         updated = []
-        for i, p in enumerate(tab.params):
-            g = p.grad
+        for i, (p, g) in enumerate(zip(tab.params, _grads_of(tab.params, self._WHO))):
             if g is None:
                 rows[i, 1] = 0                           # skipped by both kernels, like PyTorch: its count does not move
                 continue
-            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
-                raise TypeError(f"{self._WHO}: gradients must be dense contiguous fp32 on the parameter's GPU")
             st = self.state[p]
             if "exp_avg" not in st:
                 if capturing:
@@ -615,41 +599,14 @@ class _AdamSteps(NativeOptimizer):
         self._upload(tab, host, slot, flat, capturing)
         return tab, (), updated
 
-    @torch.no_grad()
-    def step(self, closure=None, *, check_into=None):
-        """Two launches per parameter group. ``self.grad_scale`` / ``self.found_inf`` (set by ``GradScaler.step``), ``check_into``,
-        an attached weight average and ``self.max_grad_norm`` mean what they mean for :meth:`SGD.step`; a skipped step moves no
-        parameter, moment, step count or average."""
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        clip = _clip_args(self.max_grad_norm, self.grad_norm_type, self._WHO)                           # refused before anything moves
-        lib, st = L.lib(), L.current_stream()
-        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
-        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
-        ready = [(g,) + self._prepare(gi, g) for gi, g in groups]
-        cs = None
-        if clip is not None:
-            cs, _ = self._norm(ready, clip, grad_scale, check_into)
-        elif check_into is not None:                         # every group is checked before any group is stepped
-            self._check(ready, check_into)
-        ema = self._ema
-        if ema is not None:                                  # what these launches leave over, decided (and uploaded) before them
-            rest = ema._rest({id(p) for r in ready for p in r[3]})
-        for group, tab, _, _ in ready:
-            dev = tab.hyper.device
-            scale, flag = L.ptr(self._flag(grad_scale, dev, "grad_scale")), L.ptr(self._flag(found_inf, dev, "found_inf"))
-            avg = (0, 0) if ema is None else (tab.shadows.data_ptr(), ema._state.data_ptr())
-            n = len(tab.params)
-            L.check(lib.yolo_adam_prepare(tab.items.data_ptr(), n, tab.hyper.data_ptr(), tab.steps.data_ptr(), tab.words.data_ptr(), flag, st),
-                    "yolo_adam_prepare")
-            L.check(lib.yolo_adam_step(tab.items.data_ptr(), n, tab.chunks.data_ptr(), tab.chunks.shape[0], tab.words.data_ptr(), scale, flag,
-                                       0 if cs is None else cs.words.data_ptr(), *avg, int(bool(group.get("decoupled_weight_decay", False))),
-                                       int(bool(group["maximize"])), st), "yolo_adam_step")
-        if ema is not None:                                  # the entries left over, then the counter; both skipped with the step
-            ema._finish(rest, self._flag(found_inf, rest.rows.device, "found_inf"))
-        return loss
+    def _launch(self, group, tab, fresh, scale, flag, clip, avg, st):
+        """`yolo_adam_prepare` (the scalars and the count of this step), then `yolo_adam_step`."""
+        lib, n, scale, flag = L.lib(), len(tab.params), L.ptr(scale), L.ptr(flag)
+        L.check(lib.yolo_adam_prepare(tab.items.data_ptr(), n, tab.hyper.data_ptr(), tab.steps.data_ptr(), tab.words.data_ptr(), flag, st),
+                "yolo_adam_prepare")
+        L.check(lib.yolo_adam_step(tab.items.data_ptr(), n, tab.chunks.data_ptr(), tab.chunks.shape[0], tab.words.data_ptr(), scale, flag,
+                                   clip, *avg, int(bool(group.get("decoupled_weight_decay", False))), int(bool(group["maximize"])), st),
+                "yolo_adam_step")
 
 
 class Adam(_AdamSteps, torch.optim.Adam):
