@@ -107,7 +107,9 @@ typedef struct yolo_conv_op {
 
 const char* yolo_last_error(void);
 /* 101: the six SGD step entry points of 100 (by value, _hp, _amp, _hp_ema, _amp_ema, _clip) are one, yolo_sgd_step, with the
- * argument list the _clip one had and clip_state_dev optional like every other option. */
+ * argument list the _clip one had and clip_state_dev optional like every other option.
+ * 102: yolo_wgrad_plan; yolo_conv_wgrad refuses a channel slice that does not fit its buffer and, for 16-bit dtypes, operands or a
+ * workspace that are not 16-byte aligned. */
 int yolo_version(void);
 /* The A/B environment switches (INTEGRATION.md has the table) are read once, when the library is loaded. This writes what was
  * read as "NAME=value\n" per switch, in the table's order (a boolean is 0 / 1 in the sense of its name: YOLO_NO_DMA=1 means the
@@ -296,10 +298,31 @@ int yolo_bn_act_bwd(const void* dy, int dy_ld, int dy_off, const void* z, int z_
 int yolo_upsample2x_bwd(const void* dup, int d_ld, int d_off, void* dx, int x_ld, int x_off, int n, int h, int w, int c,
                         int dtype, void* stream);
 /* dW (OIHW fp32) = sum over pixels dz (x) x; n,h,w = INPUT dims of the conv; dz has the output dims.
- * 16-bit operands with cin % 32 == 0 run on the bf16/f16 matrix cores, everything else on the f32 ones. */
+ * dz: NHWC gradient of the raw conv output, channels [dz_off, dz_off + cout) of rows of dz_ld elements; x: NHWC conv input,
+ * channels [x_off, x_off + cin) of rows of x_ld elements. Rules, checked before anything is launched (YOLO_ERR_ARG):
+ *   - the four ld / off values are multiples of 4, and a slice lies inside its buffer: dz_off + cout <= dz_ld, x_off + cin <= x_ld;
+ *   - the padding of a slice up to the next multiple of 4 channels (16-bit kernels: of 8) is read and must be zero; it must lie
+ *     inside the row (x_ld >= cin rounded up to 4). Other neighbour channels are never read into a result;
+ *   - 16-bit dtypes: dz, x and the workspace are 16-byte aligned.
+ * A workspace smaller than yolo_wgrad_workspace_bytes is refused with YOLO_ERR_WORKSPACE. 16-bit operands whose four ld / off values
+ * are multiples of 8 run on the bf16 / f16 matrix cores (three kernels, yolo_wgrad_plan says which), everything else on the f32
+ * ones. Every kernel adds its K slices in a fixed order: two calls on the same operands give the same bits. */
 size_t yolo_wgrad_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype);
 int yolo_conv_wgrad(const void* dz, int dz_ld, int dz_off, const void* x, int x_ld, int x_off, float* dw_oihw, int n, int h,
                     int w, int cin, int cout, int ksize, int stride, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* What yolo_conv_wgrad will launch for these arguments and how the launch cuts the work (host only, nothing is launched; the same
+ * decision function and launch plans as the call itself; YOLO_ERR_ARG where the call would refuse the shape or the ld / off values):
+ *   out8[0] kernel, YOLO_WGRAD_KERNEL_*: F32 wgrad_f32_kernel (any dtype), PATCH wgrad_patch_h16, DMA wgrad3_dma_h16, STEM stem_wgrad_h16
+ *   out8[1] dW tiles (STEM: 1)
+ *   out8[2] K tiles: F32 steps of 32 pixels; PATCH / DMA tiles of 32 or 64 output pixels; STEM K steps of 16 pixels
+ *   out8[3] K slices (STEM: workgroups)
+ *   out8[4] K tiles per slice (STEM: K steps per wave)
+ *   out8[5] fan-in of the reduce kernel: the G of wgrad_reduce<G> / wgrad_reduce_acc<G>; STEM: the strided parts of stem_wgrad_reduce
+ *   out8[6] trailing slices (STEM: workgroups) that get no K tile and write zeros
+ *   out8[7] DMA: the fragment look-ahead of the instantiation (3, or 5 under YOLO_WGRAD_LA=5); else 0 */
+enum { YOLO_WGRAD_KERNEL_F32 = 0, YOLO_WGRAD_KERNEL_PATCH = 1, YOLO_WGRAD_KERNEL_DMA = 2, YOLO_WGRAD_KERNEL_STEM = 3 };
+int yolo_wgrad_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype, int dz_ld, int dz_off, int x_ld, int x_off,
+                    int32_t* out8);
 /* Test hook for the gfx950 transposing LDS read (ds_read_b64_tr_b16) the 16-bit wgrad kernel is built on:
  * in = [64][ld] 16-bit image; out[lane][8] = what lane receives as its 32x32x16 MFMA operand, i.e.
  * in[8*(lane/32) + e][lane%32]. */

@@ -1006,52 +1006,6 @@ def test_transposing_lds_read_semantics(yt):
         np.testing.assert_array_equal(got, ((8 * (lane // 32) + e) * ld + lane % 32).astype(np.int16))
 
 
-WGRAD16_CASES = [  # cin, cout, k, stride, H, W, N, dz_ld
-    (64, 128, 3, 1, 13, 13, 2, 128), (32, 64, 3, 1, 20, 20, 1, 64), (128, 64, 3, 2, 16, 16, 2, 64), (64, 64, 3, 2, 26, 26, 1, 64),
-    (256, 128, 1, 1, 13, 13, 3, 128), (128, 21, 1, 1, 10, 10, 2, 32), (96, 255, 1, 1, 7, 7, 1, 256), (192, 96, 3, 1, 19, 38, 1, 96),
-    (64, 32, 1, 1, 52, 52, 1, 32), (512, 64, 3, 1, 5, 5, 4, 64),
-    # round 3, wgrad3_dma_h16 (3x3 stride 1, cin >= 32): several K slices with the XCD-aware workgroup map and a ragged last
-    # slice; one dW tile with 16 slices; channel counts that are not multiples of the 64-wide tile or of 16
-    (128, 256, 3, 1, 52, 52, 4, 256), (64, 64, 3, 1, 104, 40, 2, 64), (40, 72, 3, 1, 9, 9, 3, 72), (96, 32, 3, 1, 17, 33, 5, 40),
-    # round 3, stem_wgrad_h16 (first block: <= 3 input channels in an 8-channel 16-bit buffer, <= 32 output channels, W % 16 == 0):
-    # every border, rows shorter than a batch of K steps, waves with ragged last batches, one input channel, 24 output channels
-    (3, 32, 3, 1, 32, 32, 2, 32), (3, 32, 3, 1, 7, 48, 3, 32), (1, 32, 3, 1, 16, 16, 1, 32), (3, 24, 3, 1, 20, 64, 2, 40),
-    (3, 32, 3, 1, 1, 16, 1, 32), (3, 32, 3, 1, 416, 416, 1, 32)]
-
-
-@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-@pytest.mark.parametrize("case", WGRAD16_CASES)
-def test_wgrad_16bit_kernel_vs_fp64(yt, case, dtype):
-    """yolo_conv_wgrad on 16-bit operands (transposing-read MFMA kernel) against an fp64 CPU convolution
-    weight gradient of the SAME rounded operands: only the fp32 accumulation order differs."""
-    from yolo_for_turbines_amd import _lib as L
-    cin, cout, k, s, H, W, N, dz_ld = case
-    tdt, code = (torch.bfloat16, L.BF16) if dtype == "bf16" else (torch.float16, L.F16)
-    rng = np.random.Generator(np.random.PCG64(hash(case) % 1000))
-    pad = k // 2
-    Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
-    x = torch.from_numpy(rng.standard_normal((N, H, W, cin), dtype=np.float32)).to(tdt)
-    x_ld = 8 if cin <= 3 else cin                                   # the first block reads the 8-channel 16-bit input buffer
-    dz = torch.zeros((N, Ho, Wo, dz_ld), dtype=tdt)
-    dz[..., :cout] = torch.from_numpy(rng.standard_normal((N, Ho, Wo, cout), dtype=np.float32)).to(tdt)
-    xw = x.double().permute(0, 3, 1, 2)
-    w = torch.zeros((cout, cin, k, k), dtype=torch.float64, requires_grad=True)
-    y = torch.nn.functional.conv2d(xw, w, stride=s, padding=pad)
-    y.backward(dz[..., :cout].double().permute(0, 3, 1, 2))
-    want = w.grad
-    lib = L.lib()
-    ws = torch.empty(lib.yolo_wgrad_workspace_bytes(N, H, W, cin, cout, k, s, code), dtype=torch.uint8, device="cuda")
-    dw = torch.full((cout, cin, k, k), float("nan"), dtype=torch.float32, device="cuda")
-    xp = torch.zeros((N, H, W, x_ld), dtype=tdt)
-    xp[..., :cin] = x
-    xd, dzd = xp.cuda(), dz.cuda()
-    L.check(lib.yolo_conv_wgrad(dzd.data_ptr(), dz_ld, 0, xd.data_ptr(), x_ld, 0, dw.data_ptr(), N, H, W, cin, cout, k, s, code,
-                                ws.data_ptr(), ws.numel(), L.current_stream()), "wgrad")
-    got = dw.cpu().double()
-    err = float((got - want).abs().max() / want.abs().max())
-    assert err < 2e-5, f"{case} {dtype}: rel err {err}"
-
-
 # ------------------------------------------------------------- fused loss kernels (loss.py:29-81)
 @pytest.mark.parametrize("nc,S,B", [(2, 96, 4), (80, 64, 2), (2, 416, 2)])
 def test_fused_loss_values_and_gradients_vs_oracle(yt, nc, S, B):

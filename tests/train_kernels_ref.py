@@ -1,5 +1,6 @@
 """fp64 restatements of the operations the training kernels replace (bn_train.hip): train-mode BatchNorm2d statistics,
-the normalise + activation + skip-add pass, its backward, the bias gradient and the gradient of nearest 2x upsampling.
+the normalise + activation + skip-add pass, its backward, the bias gradient and the gradient of nearest 2x upsampling; and of
+the convolution's weight gradient (wgrad_*.hip).
 
 Plain torch, no project code; CPU or device tensors. Every input is taken as stored (already rounded to its dtype) and
 promoted to fp64. Channels are the LAST dimension everywhere (NHWC, or (m, c) with the pixels flattened); per-channel
@@ -105,6 +106,28 @@ def upsample2x_bwd_abs_ref(dup):
     """Sum of the magnitudes of the four terms (the scale of the rounding bound)."""
     a = _d(dup).abs()
     return a[:, 0::2, 0::2] + a[:, 0::2, 1::2] + a[:, 1::2, 0::2] + a[:, 1::2, 1::2]
+
+
+def wgrad_ref(x, dz, k, stride):
+    """Weight gradient of conv2d(padding = k // 2): x (n, h, w, cin), dz (n, ho, wo, cout), both NHWC -> dW (cout, cin, k, k):
+    dW[co, ci, kh, kw] = sum over n, ho, wo of dz[n, ho, wo, co] * x[n, ho * stride + kh - pad, wo * stride + kw - pad, ci],
+    as k * k shifted sums over the pixels both operands have. fp64 whatever the inputs are, on their device."""
+    n, h, w, cin = x.shape
+    ho, wo, cout = dz.shape[1], dz.shape[2], dz.shape[3]
+    pad = k // 2
+    x, dz = _d(x), _d(dz)
+    dw = torch.zeros((cout, cin, k, k), dtype=torch.float64, device=x.device)
+    for kh in range(k):
+        for kw in range(k):
+            # output rows / columns whose tap (kh, kw) lies inside the image
+            a0, a1 = max(0, -((kh - pad) // stride)), min(ho, (h - 1 - kh + pad) // stride + 1)
+            b0, b1 = max(0, -((kw - pad) // stride)), min(wo, (w - 1 - kw + pad) // stride + 1)
+            if a1 <= a0 or b1 <= b0:
+                continue
+            xs = x[:, a0 * stride + kh - pad:(a1 - 1) * stride + kh - pad + 1:stride,
+                   b0 * stride + kw - pad:(b1 - 1) * stride + kw - pad + 1:stride]
+            dw[:, :, kh, kw] = torch.einsum("nhwc,nhwd->dc", xs, dz[:, a0:a1, b0:b1])
+    return dw
 
 
 def mish_fp32_formula_rel_error(lo=-30.0, hi=30.0, n=600001):

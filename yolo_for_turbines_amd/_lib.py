@@ -17,6 +17,7 @@ OUT_NHWC, OUT_UPSAMPLE2X, OUT_HEAD = 0, 1, 2
 FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY, FLAG_SPLIT_BF16, FLAG_SPLIT_WEIGHTS_READY = 1, 2, 4, 8, 16
 FLAG_SPLIT_K = 32
 FLAG_FILTERS_APPENDED = 64
+WGRAD_KERNEL_F32, WGRAD_KERNEL_PATCH, WGRAD_KERNEL_DMA, WGRAD_KERNEL_STEM = 0, 1, 2, 3      # YOLO_WGRAD_KERNEL_* of the header
 LOSS_BOX_KINDS = {"mse": 0, "giou": 1, "diou": 2, "ciou": 3}          # YOLO_LOSS_BOX_* / YOLO_LOSS_OBJ_* of the header
 LOSS_OBJ_KINDS = {"mse": 0, "bce": 1}
 
@@ -155,6 +156,7 @@ _SIGS = {
     "yolo_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
     "yolo_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_wgrad_plan": (C.c_int, [C.c_int] * 12 + [C.POINTER(C.c_int32)]),
     "yolo_debug_tr_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_packed_dgrad_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "yolo_pack_weights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

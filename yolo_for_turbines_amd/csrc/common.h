@@ -261,7 +261,14 @@ int dgrad_s2_h16_launch(const void* dz, int dz_ld, int dz_off, const void* wf, c
                         int dx_ld, int dx_off, int n, int ho, int wo, int cin, int cout, int dtype, hipStream_t s);
 int conv_h16_launch(const yolo_conv_desc* d, const void* x, const void* wf, const float* scale, const float* shift,
                     const void* residual, void* y, int32_t* nan_flag, hipStream_t s);
+// How a weight-gradient launch cuts its work (yolo_wgrad_plan): filled by the plan_* function the launch itself runs on.
+// dw_tiles: output tiles; k_tiles: steps of the reduction (16-bit: K tiles of pixels; stem: 16-pixel K steps); slices: K slices
+// (stem: workgroups); per_slice: K tiles per slice (stem: K steps per wave); fan_in: lanes (stem: strided parts) that share one
+// output of the reduce kernel; empty: trailing slices (stem: workgroups) without a K tile; variant: dma look-ahead, else 0.
+struct WgradGeom { int dw_tiles, k_tiles, slices, per_slice, fan_in, empty, variant; };
+int wgrad_reduce_fan_in(long long total4, int nslices);     // wgrad_f32.hip: G of wgrad_reduce<G>
 // wgrad_stem_h16.hip: weight gradient of the first block (3x3 stride 1, <= 3 input channels, <= 32 output channels)
+WgradGeom wgrad_stem_geom(int n, int h, int w);
 bool wgrad_stem_eligible(int n, int h, int w, int cin, int cout, int ksize, int stride, int dz_ld, int dz_off, int x_ld, int x_off);
 size_t wgrad_stem_workspace(int n, int h, int w);
 int wgrad_stem_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x_off, float* workspace, float* dw_oihw, int n, int h,
@@ -277,12 +284,14 @@ int stem_h16_launch(const float* x, const float* wt, const float* scale, const f
 // wgrad_h16.hip (bf16 / fp16 weight gradient, transposing LDS reads)
 bool wgrad_h16_eligible(int cin, int cout, int ks, int stride, int dz_ld, int dz_off, int x_ld, int x_off);
 size_t wgrad_h16_workspace(int n, int h, int w, int cin, int cout, int ks, int stride);
+WgradGeom wgrad_h16_geom(int n, int h, int w, int cin, int cout, int ks, int stride);
 int wgrad_h16_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x_ld, int x_off, float* partial, int n, int h, int w,
                      int cin, int cout, int ks, int stride, int dtype, int* cout_pad, hipStream_t s);
 int tr_probe_launch(const void* in, void* out, int ld, hipStream_t s);
 // wgrad_dma_h16.hip (3x3 stride-1 weight gradient: LDS-DMA operands, one partial per CU, accumulator-order partials + own reduce)
 bool wgrad_dma_eligible(int cin, int cout, int ks, int stride, int dz_ld, int dz_off, int x_ld, int x_off);
 size_t wgrad_dma_workspace(int n, int h, int w, int cin, int cout);
+WgradGeom wgrad_dma_geom(int n, int h, int w, int cin, int cout);
 int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x_ld, int x_off, float* partial, float* dw, int n, int h,
                      int w, int cin, int cout, int dtype, hipStream_t s);
 // offset (elements) of the fragment-order copy inside a packed weight buffer

@@ -405,6 +405,27 @@ bool wgrad_dma_eligible(int cin, int cout, int ks, int stride, int dz_ld, int dz
     return dz_ld >= round_up(cout, 8) && x_ld >= round_up(cin, 8);
 }
 
+// G of wgrad_reduce_acc<G>: enough threads to keep the chip busy on the small tensors of the high-resolution layers
+static int wd_fan_in(long long total4, int nslices) {
+    if (total4 < 32768 && nslices >= 32) return 16;
+    if (total4 < 131072 && nslices >= 8) return 4;
+    return 1;
+}
+static int wd_lookahead() { return switches().wgrad_la == 5 ? 5 : 3; }          // tuning knob (A/B runs): the LA instantiation
+
+WgradGeom wgrad_dma_geom(int n, int h, int w, int cin, int cout) {
+    const WgradDPlan q = plan_wgrad_d(n, h, w, cin, cout);
+    WgradGeom g;
+    g.dw_tiles = q.tiles_m * q.tiles_n;
+    g.k_tiles = q.total_tiles;
+    g.slices = q.nslices;
+    g.per_slice = q.tiles_per_slice;
+    g.fan_in = wd_fan_in((long long)g.dw_tiles * (WD_TILE_FLOATS / 4), q.nslices);
+    g.empty = q.nslices - ceil_div(q.total_tiles, q.tiles_per_slice);
+    g.variant = wd_lookahead();
+    return g;
+}
+
 size_t wgrad_dma_workspace(int n, int h, int w, int cin, int cout) {
     const WgradDPlan q = plan_wgrad_d(n, h, w, cin, cout);
     return (size_t)q.nslices * q.tiles_m * q.tiles_n * WD_TILE_FLOATS * sizeof(float);
@@ -414,7 +435,6 @@ int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x
                      int w, int cin, int cout, int dtype, hipStream_t s) {
     const WgradDPlan q = plan_wgrad_d(n, h, w, cin, cout);
     if ((long long)n * h * w > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "wgrad: too many pixels");
-    if (((size_t)dz | (size_t)x | (size_t)partial) & 15) return fail(YOLO_ERR_ARG, "wgrad: operands must be 16-byte aligned");
     WgradDArgs a;
     a.dz = (const unsigned short*)dz; a.x = (const unsigned short*)x; a.partial = partial;
     a.N = n; a.H = h; a.W = w;
@@ -424,8 +444,8 @@ int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x
     a.th_tiles = q.th_tiles; a.tw_tiles = q.tw_tiles; a.total_tiles = q.total_tiles;
     a.tiles_per_slice = q.tiles_per_slice; a.nslices = q.nslices;
     const int grid = a.ntile * a.nslices;
-    const int la = switches().wgrad_la;                     // tuning knobs (A/B runs)
-    a.prio = switches().wgrad_prio;
+    const int la = wd_lookahead();
+    a.prio = switches().wgrad_prio;                         // tuning knob (A/B runs)
     auto go3 = [&](auto kern) -> int {
         static LdsOnce once;                                // one per instantiation of this generic lambda
         if (int rc = reserve_lds(once, reinterpret_cast<const void*>(kern), WD_LDS, "wgrad3_dma_h16")) return rc;
@@ -437,15 +457,15 @@ int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x
     else rc3 = la == 5 ? go3(&wgrad3_dma_h16<_Float16, 5>) : go3(&wgrad3_dma_h16<_Float16, 3>);
     if (rc3) return rc3;
     if (int rc = check_launch("wgrad3_dma_h16")) return rc;
-    // reduce: enough threads to keep the chip busy on the small tensors of the high-resolution layers
     const long long total4 = (long long)a.ntile * (WD_TILE_FLOATS / 4);
     auto go = [&](auto kern, int G) {
         const long long nt = total4 * G;
         const int blocks = (int)((nt + 255) / 256 < 8192 ? (nt + 255) / 256 : 8192);
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, (const float*)partial, dw, a.nslices, a.ntile, a.tiles_n, cout, cin);
     };
-    if (total4 < 32768 && a.nslices >= 32) go(wgrad_reduce_acc<16>, 16);
-    else if (total4 < 131072 && a.nslices >= 8) go(wgrad_reduce_acc<4>, 4);
+    const int G = wd_fan_in(total4, a.nslices);
+    if (G == 16) go(wgrad_reduce_acc<16>, 16);
+    else if (G == 4) go(wgrad_reduce_acc<4>, 4);
     else go(wgrad_reduce_acc<1>, 1);
     return check_launch("wgrad_reduce_acc");
 }

@@ -198,21 +198,25 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ pa
     }
 }
 
+// lanes per output vector: vectors x lanes >= ~64k threads: the small tensors of the high-resolution layers have 128-512 slices
+// and < 10k vectors (also what yolo_wgrad_plan reports)
+int wgrad_reduce_fan_in(long long total4, int nslices) {
+    if (total4 < 16384 && nslices >= 32) return 16;
+    if (total4 < 65536 && nslices >= 8) return 4;
+    return 1;
+}
+
 static int launch_wgrad_reduce(const float* partial, float* dw, int nslices, int cout, int cin, int cin_pad, int taps, int cout_pad,
                                long long total4, hipStream_t s) {
-    // vectors x lanes >= ~64k threads: the small tensors of the high-resolution layers have 128-512 slices and < 10k vectors
-    if (total4 < 16384 && nslices >= 32) {
-        const long long nt = total4 * 16;
-        const int grid = (int)((nt + 255) / 256 < 8192 ? (nt + 255) / 256 : 8192);
+    const int G = wgrad_reduce_fan_in(total4, nslices);
+    const long long nt = total4 * G;
+    const int grid = (int)((nt + 255) / 256 < 8192 ? (nt + 255) / 256 : 8192);
+    if (G == 16)
         hipLaunchKernelGGL(wgrad_reduce<16>, dim3(grid), dim3(256), 0, s, partial, dw, nslices, cout, cin, cin_pad, taps, cout_pad, total4);
-    } else if (total4 < 65536 && nslices >= 8) {
-        const long long nt = total4 * 4;
-        const int grid = (int)((nt + 255) / 256 < 8192 ? (nt + 255) / 256 : 8192);
+    else if (G == 4)
         hipLaunchKernelGGL(wgrad_reduce<4>, dim3(grid), dim3(256), 0, s, partial, dw, nslices, cout, cin, cin_pad, taps, cout_pad, total4);
-    } else {
-        const int grid = (int)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
+    else
         hipLaunchKernelGGL(wgrad_reduce<1>, dim3(grid), dim3(256), 0, s, partial, dw, nslices, cout, cin, cin_pad, taps, cout_pad, total4);
-    }
     return check_launch("wgrad_reduce");
 }
 
@@ -243,6 +247,47 @@ static WgradPlan plan_wgrad(int n, int h, int w, int cin, int cout, int ks, int 
     return q;
 }
 
+static bool wgrad_shape_ok(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype) {
+    if (dtype != YOLO_F32 && dtype != YOLO_BF16 && dtype != YOLO_F16) return false;
+    return n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && (ksize == 1 || ksize == 3) && (stride == 1 || stride == 2);
+}
+
+// The one routing decision behind yolo_conv_wgrad and yolo_wgrad_plan: the argument rules that need no pointer, then the kernel
+// (YOLO_WGRAD_KERNEL_*) and how its launch cuts the work, from the plan_* / *_eligible functions the launches themselves use.
+struct WgradRoute { int kernel; WgradGeom g; };
+
+static int wgrad_route(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype, int dz_ld, int dz_off, int x_ld,
+                       int x_off, WgradRoute* r) {
+    if (!wgrad_shape_ok(n, h, w, cin, cout, ksize, stride, dtype)) return fail(YOLO_ERR_ARG, "wgrad: bad shape");
+    const int cp = cin_pad_of(cin);
+    if ((dz_ld & 3) || (dz_off & 3) || (x_ld & 3) || (x_off & 3) || x_ld < cp || dz_ld < ((cout + 3) & ~3) || dz_off < 0 || x_off < 0)
+        return fail(YOLO_ERR_ARG, "wgrad: ld/off must be multiples of 4 and cover the padded channels");
+    if (dz_off + cout > dz_ld || x_off + cin > x_ld)
+        return fail(YOLO_ERR_ARG, "wgrad: a channel slice must lie inside its buffer (dz %d + %d > %d or x %d + %d > %d)", dz_off, cout,
+                    dz_ld, x_off, cin, x_ld);
+    if (dtype != YOLO_F32 && wgrad_stem_eligible(n, h, w, cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off)) {
+        r->kernel = YOLO_WGRAD_KERNEL_STEM;
+        r->g = wgrad_stem_geom(n, h, w);
+    } else if (dtype != YOLO_F32 && wgrad_dma_eligible(cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off)) {
+        r->kernel = YOLO_WGRAD_KERNEL_DMA;
+        r->g = wgrad_dma_geom(n, h, w, cin, cout);
+    } else if (dtype != YOLO_F32 && wgrad_h16_eligible(cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off)) {
+        r->kernel = YOLO_WGRAD_KERNEL_PATCH;
+        r->g = wgrad_h16_geom(n, h, w, cin, cout, ksize, stride);
+    } else {
+        const WgradPlan q = plan_wgrad(n, h, w, cin, cout, ksize, stride);
+        r->kernel = YOLO_WGRAD_KERNEL_F32;
+        r->g.dw_tiles = q.tiles_m * q.tiles_n;
+        r->g.k_tiles = q.total_steps;
+        r->g.slices = q.nslices;
+        r->g.per_slice = q.steps_per_slice;
+        r->g.fan_in = wgrad_reduce_fan_in((long long)cout * ksize * ksize * (cp / 4), q.nslices);
+        r->g.empty = q.nslices - ceil_div(q.total_steps, q.steps_per_slice);        // 0: plan_wgrad leaves no empty slice
+        r->g.variant = 0;
+    }
+    return YOLO_OK;
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -250,8 +295,7 @@ using namespace yolo;
 extern "C" {
 
 size_t yolo_wgrad_workspace_bytes(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype) {
-    if (dtype != YOLO_F32 && dtype != YOLO_BF16 && dtype != YOLO_F16) return 0;
-    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return 0;
+    if (!wgrad_shape_ok(n, h, w, cin, cout, ksize, stride, dtype)) return 0;
     const WgradPlan q = plan_wgrad(n, h, w, cin, cout, ksize, stride);
     size_t need = (size_t)q.nslices * q.cout_pad * q.kp * sizeof(float);
     if (dtype != YOLO_F32) {
@@ -269,6 +313,16 @@ size_t yolo_wgrad_workspace_bytes(int n, int h, int w, int cin, int cout, int ks
     return need;
 }
 
+int yolo_wgrad_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int dtype, int dz_ld, int dz_off, int x_ld, int x_off,
+                    int32_t* out8) {
+    if (!out8) return fail(YOLO_ERR_ARG, "wgrad_plan: null pointer");
+    WgradRoute r;
+    if (int rc = wgrad_route(n, h, w, cin, cout, ksize, stride, dtype, dz_ld, dz_off, x_ld, x_off, &r)) return rc;
+    out8[0] = r.kernel; out8[1] = r.g.dw_tiles; out8[2] = r.g.k_tiles; out8[3] = r.g.slices;
+    out8[4] = r.g.per_slice; out8[5] = r.g.fan_in; out8[6] = r.g.empty; out8[7] = r.g.variant;
+    return YOLO_OK;
+}
+
 /* probe of the gfx950 transposing LDS read used by the 16-bit wgrad kernel (tests only):
  * in: [64][ld] 16-bit image, out: [64 lanes][8] what each lane receives for the 32x32x16 operand */
 int yolo_debug_tr_probe(const void* in, void* out, int ld, void* stream) {
@@ -276,24 +330,26 @@ int yolo_debug_tr_probe(const void* in, void* out, int ld, void* stream) {
     return tr_probe_launch(in, out, ld, (hipStream_t)stream);
 }
 
-/* dz: NHWC gradient of the raw conv output (n, ho, wo, cout) with channel stride dz_ld (>= cout rounded
- * up to 4; any padding channels must be zero); x: NHWC conv input; dw: OIHW fp32 out. */
+/* dz: NHWC gradient of the raw conv output (n, ho, wo, cout), channels [dz_off, dz_off + cout) of rows of dz_ld elements; x: NHWC
+ * conv input, channels [x_off, x_off + cin) of rows of x_ld; dw: OIHW fp32 out. The rules are those of the header. */
 int yolo_conv_wgrad(const void* dz, int dz_ld, int dz_off, const void* x, int x_ld, int x_off, float* dw_oihw, int n, int h,
                     int w, int cin, int cout, int ksize, int stride, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (!dz || !x || !dw_oihw || !workspace) return fail(YOLO_ERR_ARG, "wgrad: null pointer");
     const size_t need = yolo_wgrad_workspace_bytes(n, h, w, cin, cout, ksize, stride, dtype);
     if (!need) return fail(YOLO_ERR_ARG, "wgrad: bad shape");
     if (workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "wgrad: workspace %zu < %zu", workspace_bytes, need);
+    WgradRoute r;
+    if (int rc = wgrad_route(n, h, w, cin, cout, ksize, stride, dtype, dz_ld, dz_off, x_ld, x_off, &r)) return rc;
+    if (dtype != YOLO_F32 && (((size_t)dz | (size_t)x | (size_t)workspace) & 15))          // every 16-bit path issues 16-byte accesses
+        return fail(YOLO_ERR_ARG, "wgrad: 16-bit operands and the workspace must be 16-byte aligned");
     const int cp = cin_pad_of(cin);
-    if ((dz_ld & 3) || (dz_off & 3) || (x_ld & 3) || (x_off & 3) || x_ld < cp || dz_ld < ((cout + 3) & ~3))
-        return fail(YOLO_ERR_ARG, "wgrad: ld/off must be multiples of 4 and cover the padded channels");
     hipStream_t s = (hipStream_t)stream;
     const long long total = (long long)cout * ksize * ksize * (cp / 4);            // float4 groups of the partial layout
-    if (dtype != YOLO_F32 && wgrad_stem_eligible(n, h, w, cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off))
+    if (r.kernel == YOLO_WGRAD_KERNEL_STEM)
         return wgrad_stem_launch(dz, dz_ld, dz_off, x, x_off, (float*)workspace, dw_oihw, n, h, w, cin, cout, dtype, s);
-    if (dtype != YOLO_F32 && wgrad_dma_eligible(cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off))
+    if (r.kernel == YOLO_WGRAD_KERNEL_DMA)
         return wgrad_dma_launch(dz, dz_ld, dz_off, x, x_ld, x_off, (float*)workspace, dw_oihw, n, h, w, cin, cout, dtype, s);
-    if (dtype != YOLO_F32 && wgrad_h16_eligible(cin, cout, ksize, stride, dz_ld, dz_off, x_ld, x_off)) {
+    if (r.kernel == YOLO_WGRAD_KERNEL_PATCH) {
         int cout_pad = 0;
         const int ns = wgrad_h16_launch(dz, dz_ld, dz_off, x, x_ld, x_off, (float*)workspace, n, h, w, cin, cout, ksize, stride, dtype,
                                         &cout_pad, s);

@@ -293,6 +293,19 @@ size_t wgrad_h16_workspace(int n, int h, int w, int cin, int cout, int ks, int s
     return (size_t)q.nslices * q.cout_pad * q.kp * sizeof(float);
 }
 
+WgradGeom wgrad_h16_geom(int n, int h, int w, int cin, int cout, int ks, int stride) {
+    const WgradHPlan q = plan_wgrad_h(n, h, w, cin, cout, ks, stride);
+    WgradGeom g;
+    g.dw_tiles = q.tiles_m * q.tiles_n;
+    g.k_tiles = q.total_tiles;
+    g.slices = q.nslices;
+    g.per_slice = q.tiles_per_slice;
+    g.fan_in = wgrad_reduce_fan_in((long long)cout * ks * ks * (cin_pad_of(cin) / 4), q.nslices);
+    g.empty = q.nslices - ceil_div(q.total_tiles, q.tiles_per_slice);
+    g.variant = 0;
+    return g;
+}
+
 template <typename T, int KS, int STRIDE>
 static int launch_wh(const WgradHArgs& a, hipStream_t s) {
     constexpr int TT = KS == 3 ? 1 : 2;

@@ -202,17 +202,18 @@ __global__ __launch_bounds__(256) void stem_wgrad_h16(const StemWgArgs p) {
 }
 
 // dW[co][ci][kh][kw] = sum over workgroups, fixed order: grid = cout, 256 threads = 32 columns x 8 strided parts
+constexpr int SW_RPARTS = 8;
 __global__ __launch_bounds__(256) void stem_wgrad_reduce(const float* __restrict__ partial, int nblk, int cin, float* __restrict__ dw) {
-    __shared__ float red[8][32];
+    __shared__ float red[SW_RPARTS][32];
     const int co = blockIdx.x, n = threadIdx.x & 31, part = threadIdx.x >> 5;
     float s = 0.f;
-    for (int b = part; b < nblk; b += 8) s += partial[((size_t)b * 32 + co) * 32 + n];
+    for (int b = part; b < nblk; b += SW_RPARTS) s += partial[((size_t)b * 32 + co) * 32 + n];
     red[part][n] = s;
     __syncthreads();
     if (part == 0 && n < cin * 9) {
         float t = 0.f;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) t += red[q][n];
+        for (int q = 0; q < SW_RPARTS; ++q) t += red[q][n];
         dw[(size_t)co * cin * 9 + n] = t;
     }
 }
@@ -223,24 +224,48 @@ static int stem_wgrad_blocks(long long segs) {
     return (int)(nb < 1 ? 1 : nb);
 }
 
+struct StemWgPlan { long long segs; int nblk, segs_per_wave; };
+
+static StemWgPlan plan_wgrad_stem(int n, int h, int w) {
+    StemWgPlan q;
+    q.segs = (long long)n * h * (w / 16);
+    q.nblk = stem_wgrad_blocks(q.segs);
+    q.segs_per_wave = (int)((q.segs + 4LL * q.nblk - 1) / (4LL * q.nblk));
+    return q;
+}
+
+WgradGeom wgrad_stem_geom(int n, int h, int w) {
+    const StemWgPlan q = plan_wgrad_stem(n, h, w);
+    WgradGeom g;
+    g.dw_tiles = 1;
+    g.k_tiles = (int)q.segs;
+    g.slices = q.nblk;
+    g.per_slice = q.segs_per_wave;
+    g.fan_in = SW_RPARTS;
+    g.empty = q.nblk - (int)((q.segs + 4LL * q.segs_per_wave - 1) / (4LL * q.segs_per_wave));
+    g.variant = 0;
+    return g;
+}
+
 bool wgrad_stem_eligible(int n, int h, int w, int cin, int cout, int ksize, int stride, int dz_ld, int dz_off, int x_ld, int x_off) {
     if (switches().no_stem_wgrad || ksize != 3 || stride != 1 || cin < 1 || cin > 3 || cout < 1 || cout > 32) return false;
-    if (x_ld != SW_XLD || (x_off & 7) || dz_ld < 32 || (dz_ld & 7) || (dz_off & 7) || (w & 15) || h < 1) return false;
+    // the dz DMA moves 32 channels from dz_off whatever cout is: they must lie inside the pixel's row
+    if (x_ld != SW_XLD || (x_off & 7) || dz_ld - dz_off < 32 || (dz_ld & 7) || (dz_off & 7) || (w & 15) || h < 1) return false;
     return (long long)n * h * w <= 0x7fffffffLL;
 }
 
-size_t wgrad_stem_workspace(int n, int h, int w) { return (size_t)stem_wgrad_blocks((long long)n * h * (w / 16)) * 32 * 32 * sizeof(float); }
+size_t wgrad_stem_workspace(int n, int h, int w) { return (size_t)plan_wgrad_stem(n, h, w).nblk * 32 * 32 * sizeof(float); }
 
 int wgrad_stem_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x_off, float* workspace, float* dw_oihw, int n, int h,
                       int w, int cin, int cout, int dtype, hipStream_t s) {
     StemWgArgs a;
     a.dz = (const unsigned short*)dz; a.x = (const unsigned short*)x; a.partial = workspace;
     a.H = h; a.W = w; a.cin = cin; a.dz_ld = dz_ld; a.dz_off = dz_off; a.x_off = x_off;
+    const StemWgPlan q = plan_wgrad_stem(n, h, w);
     a.segs_per_row = w / 16;
-    const long long segs = (long long)n * h * a.segs_per_row;
-    a.total_segs = (int)segs;
-    const int nblk = stem_wgrad_blocks(segs);
-    a.segs_per_wave = (int)((segs + 4LL * nblk - 1) / (4LL * nblk));
+    a.total_segs = (int)q.segs;
+    const int nblk = q.nblk;
+    a.segs_per_wave = q.segs_per_wave;
     a.mg_spr = sw_magic(a.segs_per_row); a.mg_H = sw_magic(h);
     const size_t lds = 4 * SW_WAVE_LDS;
     static LdsOnce once_b, once_h;
