@@ -231,7 +231,7 @@ def test_eval_model_reads_prepared_weights_and_remakes_them(L):
         (plan,) = ready._engine._plans.values()
         i = next(i for i in range(len(plan.table)) if plan.table[i].d.flags & L.FLAG_SPLIT_WEIGHTS_READY)
         pk = ready._engine.packed(plan.blocks[i], x.device)
-        assert plan.table[i].w_packed == pk.w.data_ptr() == pk.s3.data_ptr() and pk.s3_stamp == pk.stamp
+        assert plan.table[i].w_packed == pk.w.data_ptr() == pk.prepared["s3"].buf.data_ptr() and pk.prepared["s3"].stamp == pk.stamp
         name = next(n for n, mod in ready.named_modules() if mod is plan.blocks[i])
         plan.blocks[i].conv.weight.mul_(1.25)
         changed = [o.clone() for o in ready(x)]
@@ -244,4 +244,4 @@ def test_eval_model_reads_prepared_weights_and_remakes_them(L):
         off = s3._small_model(yt, False)
         off(x)
         assert not any(f & (L.FLAG_SPLIT_BF16 | L.FLAG_SPLIT_WEIGHTS_READY) for f in flags_of(off))
-        assert all(pk.s3 is None for per_dev in off._engine._packed.values() for pk in per_dev.values())
+        assert all("s3" not in pk.prepared for per_dev in off._engine._packed.values() for pk in per_dev.values())

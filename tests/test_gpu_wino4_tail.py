@@ -198,13 +198,13 @@ def test_packed_block_marks_its_filters_stale(built):
     blk = yt.model.CNNBlock(128, 256, kernel_size=3, padding=1)
     st = engine.ModelState()
     pk = st.packed(blk, torch.device("cpu"))
-    assert pk.u4 is None
-    u4 = pk.want_u4(_desc(L, 1, 52, 52, 128, 256))
-    assert u4.numel() == 36 * 32 * 256 * 16 and pk.u4_stamp is None
-    assert pk.want_u4(_desc(L, 8, 104, 104, 128, 256)) is u4                        # one buffer serves every plan
-    pk.u4_stamp = pk.stamp = engine.PackedBlock.stamp_of(blk)[0]
+    assert "u4" not in pk.prepared
+    u4 = pk.want("u4", _desc(L, 1, 52, 52, 128, 256))
+    assert u4.numel() == 36 * 32 * 256 * 16 and pk.prepared["u4"].stamp is None
+    assert pk.want("u4", _desc(L, 8, 104, 104, 128, 256)) is u4                        # one buffer serves every plan
+    pk.prepared["u4"].stamp = pk.stamp = engine.PackedBlock.stamp_of(blk)[0]
     st.invalidate()
-    assert pk.stamp is None and pk.u4_stamp is None
+    assert pk.stamp is None and pk.prepared["u4"].stamp is None
 
 
 @pytest.mark.gpu
@@ -261,14 +261,14 @@ def test_eval_plan_hands_the_tile_15_layers_their_filters(built):
     for i in ready:
         e = plan.table[i]
         pk = st.packed(plan.blocks[i], dev)
-        assert L.lib().yolo_conv_pick_tile(C.byref(e.d)) == 15 and e.w_packed == pk.u4.data_ptr() and pk.u4_stamp is None
+        assert L.lib().yolo_conv_pick_tile(C.byref(e.d)) == 15 and e.w_packed == pk.prepared["u4"].buf.data_ptr() and pk.prepared["u4"].stamp is None
         assert e.workspace_bytes >= L.lib().yolo_conv_workspace_bytes(C.byref(e.d)) > 0
     others = [i for i in range(len(plan.table)) if i not in ready]
     assert all(plan.table[i].w_packed == st.packed(plan.blocks[i], dev).w.data_ptr() for i in others)
-    total = sum(pk.u4.numel() for per in st._packed.values() for pk in per.values() if pk.u4 is not None)
+    total = sum(pk.prepared["u4"].buf.numel() for per in st._packed.values() for pk in per.values() if "u4" in pk.prepared)
     assert total == 261_881_856
     plan2 = engine.Plan(engine.build_network_program(m, 8, 416), st, dev)
-    assert sum(pk.u4.numel() for per in st._packed.values() for pk in per.values() if pk.u4 is not None) == total
+    assert sum(pk.prepared["u4"].buf.numel() for per in st._packed.values() for pk in per.values() if "u4" in pk.prepared) == total
     assert sum(1 for i in range(len(plan2.table)) if plan2.table[i].d.flags & L.FLAG_FILTERS_READY) == 24
     plan13 = engine.Plan(engine.build_network_program(m, 1, 416), st, dev, tile_override=13)
     assert not any(plan13.table[i].d.flags & L.FLAG_FILTERS_READY for i in range(len(plan13.table)))

@@ -107,7 +107,7 @@ def test_forced_tile_15_takes_any_multiple_of_four_channels(built):
 
 def test_packed_block_keeps_room_for_appended_filters(built):
     """The 512 -> 1024 3x3 stride-1 block gets the room at creation (the buffer cannot grow later); the filters are a view of w,
-    start stale, and `invalidate` makes them stale again. Other blocks have no room and want_u4a says so."""
+    start stale, and `invalidate` makes them stale again. Other blocks have no room and want("u4a") says so."""
     import yolo_for_turbines_amd as yt
     from yolo_for_turbines_amd import engine
     L = built
@@ -116,17 +116,17 @@ def test_packed_block_keeps_room_for_appended_filters(built):
     blk = yt.model.CNNBlock(512, 1024, kernel_size=3, padding=1)
     pk = st.packed(blk, torch.device("cpu"))
     d = _desc(L, 32, 13, 512, 1024)
-    assert pk.w.numel() == lib.yolo_wino4_appended_bytes(d) and pk.u4a is None and pk.u4 is None
-    u = pk.want_u4a(d)
+    assert pk.w.numel() == lib.yolo_wino4_appended_bytes(d) and "u4a" not in pk.prepared and "u4" not in pk.prepared
+    u = pk.want("u4a", d)
     off = (lib.yolo_packed_weight_bytes(1024, 512, 3, L.F32) + 15) // 16 * 16
-    assert u.data_ptr() == pk.w.data_ptr() + off and u.numel() == 75_497_472 and pk.u4a_stamp is None
-    assert pk.want_u4a(_desc(L, 1, 19, 512, 1024)) is u
-    pk.u4a_stamp = pk.stamp = engine.PackedBlock.stamp_of(blk)[0]
+    assert u.data_ptr() == pk.w.data_ptr() + off and u.numel() == 75_497_472 and pk.prepared["u4a"].stamp is None
+    assert pk.want("u4a", _desc(L, 1, 19, 512, 1024)) is u
+    pk.prepared["u4a"].stamp = pk.stamp = engine.PackedBlock.stamp_of(blk)[0]
     st.invalidate()
-    assert pk.stamp is None and pk.u4a_stamp is None
+    assert pk.stamp is None and pk.prepared["u4a"].stamp is None
     small = st.packed(yt.model.CNNBlock(256, 512, kernel_size=3, padding=1), torch.device("cpu"))
     assert small.w.numel() == lib.yolo_packed_weight_bytes(512, 256, 3, L.F32)
-    assert small.want_u4a(_desc(L, 1, 13, 256, 512)) is None
+    assert small.want("u4a", _desc(L, 1, 13, 256, 512)) is None
     assert st.packed(blk, torch.device("cpu"), "bf16").w.numel() == lib.yolo_packed_weight_bytes(1024, 512, 3, L.BF16)   # fp32 only
 
 
@@ -151,7 +151,7 @@ def test_eval_plan_routes_the_13x13_layers(built):
         e = plan.table[i]
         pk = st.packed(plan.blocks[i], dev)
         assert (e.d.h, e.d.w, e.d.cin, e.d.cout, e.d.ksize, e.d.stride, e.d.tile) == (13, 13, 512, 1024, 3, 1, 0)
-        assert e.w_packed == pk.w.data_ptr() and pk.u4a is not None and pk.u4 is None and pk.u4a_stamp is None
+        assert e.w_packed == pk.w.data_ptr() and "u4a" in pk.prepared and "u4" not in pk.prepared and pk.prepared["u4a"].stamp is None
         assert not e.d.flags & (L.FLAG_FILTERS_READY | L.FLAG_SPLIT_BF16 | L.FLAG_SPLIT_WEIGHTS_READY | L.FLAG_SPLIT_K)
         assert lib.yolo_conv_pick_tile(C.byref(e.d)) == 15
         assert e.workspace and e.workspace_bytes >= lib.yolo_conv_workspace_bytes(C.byref(e.d)) > 0

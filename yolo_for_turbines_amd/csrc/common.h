@@ -195,7 +195,7 @@ template <> struct Vec16<_Float16> {
 // numbers are the public header's; some mean one kernel for fp32 and another for bf16 / fp16, so those names carry the dtype.
 constexpr int kNumTiles = 10;                // what yolo_conv_num_tiles reports: the ids of the plain tiled kernels, 1 .. 10
 constexpr int kMaxTileId = 15;               // validate() refuses anything above
-// fp32 (conv_f32.hip routes them)
+// fp32 (conv_dispatch.hip routes them)
 constexpr int kTileF32Reg128x128 = 1;        // conv_igemm_f32, register-staged, BM x BN
 constexpr int kTileF32Reg128x64 = 2;
 constexpr int kTileF32Reg64x128 = 3;
@@ -244,7 +244,6 @@ bool wino4_supported(const yolo_conv_desc* d);
 bool wino4_eligible(const yolo_conv_desc* d);
 size_t wino4_workspace_bytes(const yolo_conv_desc* d);
 size_t wino4_filter_bytes(const yolo_conv_desc* d);
-size_t wino4_appended_offset(const yolo_conv_desc* d);   // YOLO_FLAG_FILTERS_APPENDED: where U4 begins in the packed buffer
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)
@@ -294,7 +293,14 @@ size_t wgrad_dma_workspace(int n, int h, int w, int cin, int cout);
 WgradGeom wgrad_dma_geom(int n, int h, int w, int cin, int cout);
 int wgrad_dma_launch(const void* dz, int dz_ld, int dz_off, const void* x, int x_ld, int x_off, float* partial, float* dw, int n, int h,
                      int w, int cin, int cout, int dtype, hipStream_t s);
-// offset (elements) of the fragment-order copy inside a packed weight buffer
-inline size_t v0_packed_elems(int cout, int cin, int ks) { return (size_t)coutpad_of(cout) * kpad_of(cin, ks); }
+// Sections of a packed fp32 weight buffer (yolo_pack_weights; yolo_pack_weights_dgrad packs the gradient convolution, whose (cout, cin)
+// are the layer's (cin, cout rounded up to 32)). In elements: the row-major matrix at 0, the fragment-order copy at `frag`, the F(2x2)
+// filters U at `wino`, the end of the packed part at `end`. In bytes: the 16-byte-aligned tail behind the packed part, where a
+// caller with room there keeps the bf16 planes (yolo_split3_weights) or U4 (YOLO_FLAG_FILTERS_APPENDED).
+struct PackedF32 { size_t frag, wino, end, tail_bytes; };
+inline PackedF32 packed_f32(int cout, int cin, int ks) {
+    const size_t frag = (size_t)coutpad_of(cout) * kpad_of(cin, ks), wino = frag + v2_frag_elems(cout, cin, ks), end = wino + wino_weight_elems(cout, cin, ks);
+    return {frag, wino, end, (end * sizeof(float) + 15) & ~(size_t)15};
+}
 
 }  // namespace yolo

@@ -30,12 +30,13 @@ struct ConvArgs {
 
 constexpr int BK = 32;       // one K step: 32 consecutive input channels of one filter tap
 
+int conv_igemm_launch(const ConvArgs& a, int tile, hipStream_t s);   // conv_f32.hip: tile is one of kTileF32Reg*, anything else runs 64x64
+
 // conv_split3_f32.hip (fp32 operands split into three bf16 each, six bf16 MFMAs per product; YOLO_FLAG_SPLIT_BF16)
 bool split3_supported(const yolo_conv_desc* d);
 bool split3_eligible(const yolo_conv_desc* d);
-// a.w_planes set: a.w is the buffer split3_weights_launch made (YOLO_FLAG_SPLIT_WEIGHTS_READY), the planes split3_planes_offset in
+// a.w_planes set: a.w is the buffer split3_weights_launch made (YOLO_FLAG_SPLIT_WEIGHTS_READY), the planes in its tail (packed_f32)
 int conv_split3_launch(const ConvArgs& a, int tile, hipStream_t s);
-size_t split3_planes_offset(const yolo_conv_desc* d);
 size_t split3_weight_bytes(const yolo_conv_desc* d);
 int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* out, hipStream_t s);
 

@@ -18,7 +18,7 @@
 //  Occupancy        BN = 128: two patch buffers (64.5 KB LDS, 224 registers) -> 2 blocks per CU. BN = 64 can run with ONE
 //      patch buffer (36.9 KB, 148 registers, one more barrier per chunk) -> 3 blocks per CU, which covers prologue /
 //      epilogue better and fills 768 slots in one round at 13x13: the configuration measured fastest at 208 / 104 / 52 /
-//      13 (conv_f32.hip:pick_direct_tile).
+//      13 (conv_dispatch.hip:pick_direct_tile).
 #include "common.h"
 
 namespace yolo {

@@ -367,17 +367,13 @@ static int launch_split3(const ConvArgs& a, hipStream_t s) {
 }
 
 // ---- prepared weights (yolo_split3_weights): layout in the comment at the top of this file
-size_t split3_planes_offset(const yolo_conv_desc* d) {
-    return (yolo_packed_weight_bytes(d->cout, d->cin, d->ksize, YOLO_F32) + 15) & ~(size_t)15;
-}
-
 size_t split3_weight_bytes(const yolo_conv_desc* d) {
     const size_t cp = coutpad_of(d->cout), KT = kpad_of(d->cin, d->ksize) / BK;
-    return split3_planes_offset(d) + KT * 3 * cp * S3_ROWB + cp / 32 * sizeof(unsigned);
+    return packed_f32(d->cout, d->cin, d->ksize).tail_bytes + KT * 3 * cp * S3_ROWB + cp / 32 * sizeof(unsigned);
 }
 
 int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* out, hipStream_t s) {
-    const size_t off = split3_planes_offset(d);
+    const size_t off = packed_f32(d->cout, d->cin, d->ksize).tail_bytes;
     if (out != w_packed) {                           // not in place: the packed weights go in front
         const char *a = static_cast<const char*>(w_packed), *b = static_cast<const char*>(out);
         if (a < b + split3_weight_bytes(d) && b < a + off) return fail(YOLO_ERR_ARG, "yolo_split3_weights: out overlaps w_packed (pass the same pointer to prepare in place)");

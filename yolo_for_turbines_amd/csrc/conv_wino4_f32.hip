@@ -561,11 +561,6 @@ size_t wino4_filter_bytes(const yolo_conv_desc* d) {
     return (size_t)36 * round_up(d->cin / 4, 2) * round_up(d->cout, 64) * 4 * sizeof(float);
 }
 
-// YOLO_FLAG_FILTERS_APPENDED: U4 lies in the packed buffer itself, behind the packed weights
-size_t wino4_appended_offset(const yolo_conv_desc* d) {
-    return (yolo_packed_weight_bytes(d->cout, d->cin, d->ksize, YOLO_F32) + 15) & ~(size_t)15;
-}
-
 // w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad); U4_ready: the
 // filters transformed before (yolo_wino4_filters), or NULL: this launch transforms them into the workspace behind V4
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
@@ -617,7 +612,7 @@ extern "C" {
 size_t yolo_wino4_filter_bytes(const yolo_conv_desc* d) { return d ? yolo::wino4_filter_bytes(d) : 0; }
 
 size_t yolo_wino4_appended_bytes(const yolo_conv_desc* d) {
-    return d && yolo::wino4_supported(d) ? yolo::wino4_appended_offset(d) + yolo::wino4_filter_bytes(d) : 0;
+    return d && yolo::wino4_supported(d) ? yolo::packed_f32(d->cout, d->cin, d->ksize).tail_bytes + yolo::wino4_filter_bytes(d) : 0;
 }
 
 int yolo_wino4_appended_wanted(const yolo_conv_desc* d) {

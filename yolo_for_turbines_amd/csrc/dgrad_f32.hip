@@ -212,7 +212,8 @@ size_t yolo_packed_dgrad_bytes(int cout, int cin, int ksize, int flip, int dtype
     const int coutp = round_up(cout, 32);
     if (flip && dtype != YOLO_F32) return h16_frag_elems(cin, coutp, ksize) * 2;
     if (!flip && dtype != YOLO_F32) return (ksize == 3 && cout % 32 == 0) ? h16_dgrad_s2_elems(cout, cin) * 2 : 0;
-    return (v0_packed_elems(cin, coutp, ksize) + v2_frag_elems(cin, coutp, ksize) + (flip ? wino_weight_elems(cin, coutp, ksize) : 0)) * sizeof(float);
+    const PackedF32 sec = packed_f32(cin, coutp, ksize);
+    return (flip ? sec.end : sec.wino) * sizeof(float);
 }
 
 int yolo_pack_weights_dgrad(const float* w_oihw, void* w_packed, int cout, int cin, int ksize, int flip, int dtype, void* stream) {
@@ -221,20 +222,21 @@ int yolo_pack_weights_dgrad(const float* w_oihw, void* w_packed, int cout, int c
     if (!flip && dtype != YOLO_F32) return h16_pack_dgrad_s2(w_oihw, w_packed, cout, cin, dtype, (hipStream_t)stream);
     const int coutp = round_up(cout, 32);
     const int kpad = kpad_of(coutp, ksize);
-    const long long total = (long long)v0_packed_elems(cin, coutp, ksize);
+    const PackedF32 sec = packed_f32(cin, coutp, ksize);
+    const long long total = (long long)sec.frag;
     hipStream_t s = (hipStream_t)stream;
     int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(pack_dgrad_rowmajor, dim3(grid), dim3(256), 0, s, w_oihw, (float*)w_packed, cout, cin, ksize, coutp, kpad, flip, total);
     int rc = check_launch("pack_dgrad_rowmajor");
     if (rc || !flip) return rc;
-    const long long ftotal = (long long)v2_frag_elems(cin, coutp, ksize);
+    const long long ftotal = (long long)(sec.wino - sec.frag);
     const int KT = (coutp / 32) * ksize * ksize;
     grid = (int)((ftotal + 255) / 256 < 8192 ? (ftotal + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pack_dgrad_frag, dim3(grid), dim3(256), 0, s, w_oihw, (float*)w_packed + total, cout, cin, ksize, KT, ftotal);
+    hipLaunchKernelGGL(pack_dgrad_frag, dim3(grid), dim3(256), 0, s, w_oihw, (float*)w_packed + sec.frag, cout, cin, ksize, KT, ftotal);
     rc = check_launch("pack_dgrad_frag");
     // third section, as in yolo_pack_weights: the Winograd-domain filters of the gradient convolution (yolo_conv_fwd_ws)
-    if (rc || !wino_weight_elems(cin, coutp, ksize)) return rc;
-    return wino_pack_dgrad(w_oihw, (float*)w_packed + total + ftotal, cout, cin, s);
+    if (rc || sec.end == sec.wino) return rc;
+    return wino_pack_dgrad(w_oihw, (float*)w_packed + sec.wino, cout, cin, s);
 }
 
 /* dx (N,2Ho,2Wo,cin) = transposed 3x3 stride-2 conv of dz (N,Ho,Wo,cout) [+ residual]; w_packed from

@@ -177,7 +177,7 @@ size_t yolo_packed_weight_bytes(int cout, int cin, int ksize, int dtype) {
 
 size_t yolo_packed_weight_elems(int cout, int cin, int ksize) {
     if (cout <= 0 || cin <= 0 || (ksize != 1 && ksize != 3)) return 0;
-    return v0_packed_elems(cout, cin, ksize) + v2_frag_elems(cout, cin, ksize) + wino_weight_elems(cout, cin, ksize);
+    return packed_f32(cout, cin, ksize).end;
 }
 
 int yolo_pack_weights(const float* w_oihw, void* w_packed, int cout, int cin, int ksize, int dtype, void* stream) {
@@ -188,15 +188,15 @@ int yolo_pack_weights(const float* w_oihw, void* w_packed, int cout, int cin, in
     }
     if (dtype != YOLO_F32) return fail(YOLO_ERR_UNSUPPORTED, "pack_weights: dtype %d", dtype);
     if (!yolo_packed_weight_elems(cout, cin, ksize)) return fail(YOLO_ERR_ARG, "pack_weights: bad shape");
-    const long long total = (long long)v0_packed_elems(cout, cin, ksize);
+    const PackedF32 sec = packed_f32(cout, cin, ksize);
+    const long long total = (long long)sec.frag;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_weights_f32, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, (float*)w_packed, cout, cin,
                        ksize, cin_pad_of(cin), kpad_of(cin, ksize), total);
     int rc = check_launch("pack_weights");
     if (rc) return rc;
-    const size_t frag = v2_frag_elems(cout, cin, ksize);
-    if (frag && (rc = v2_pack(w_oihw, (float*)w_packed + total, cout, cin, ksize, (hipStream_t)stream))) return rc;
-    if (wino_weight_elems(cout, cin, ksize)) return wino_pack(w_oihw, (float*)w_packed + total + frag, cout, cin, (hipStream_t)stream);
+    if (sec.wino > sec.frag && (rc = v2_pack(w_oihw, (float*)w_packed + sec.frag, cout, cin, ksize, (hipStream_t)stream))) return rc;
+    if (sec.end > sec.wino) return wino_pack(w_oihw, (float*)w_packed + sec.wino, cout, cin, (hipStream_t)stream);
     return YOLO_OK;
 }
 

@@ -17,6 +17,7 @@ import ctypes as C
 import os
 import weakref
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -182,6 +183,38 @@ def build_network_program(model, B, H, ch_align=4, W=None):
 
 
 # ----------------------------------------------------------------------------------------
+# The forms of a block's packed fp32 weights that the library prepares once per weight update for the eval plans, not per launch. They
+# depend on (cout, cin, ksize) only, so one of each serves every plan; PackedBlock.prepared keeps them by kind, and they follow the
+# weight stamp. Per kind: the call that sizes it (bytes from the start of its buffer), where it lives, the call that makes it.
+#   "u4"   Winograd F(4x4) filters U4 = G g G^T, for the launches that pick tile 15 (YOLO_FLAG_FILTERS_READY): a buffer of its own,
+#          and a layer that cannot have one is an error.
+#   "s3"   the bf16 planes behind the packed weights (YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY): the front of ``w``,
+#          packed weights then planes, made in place; None where ``w`` has no room.
+#   "u4a"  the same filters U4 behind the packed weights (YOLO_FLAG_FILTERS_APPENDED): the last yolo_wino4_filter_bytes of that
+#          front of ``w``, made in place; None where ``w`` has no room.
+_PREPARED = {
+    "u4": ("yolo_wino4_filter_bytes", "own", "yolo_wino4_filters"),
+    "s3": ("yolo_split3_weight_bytes", "front", "yolo_split3_weights"),
+    "u4a": ("yolo_wino4_appended_bytes", "tail", "yolo_wino4_filters"),
+}
+
+
+def _prepared_room(cv, code):
+    """Bytes a new fp32 block keeps for the form that lives behind its packed weights: ``w`` cannot grow later, plans hold its address."""
+    lib = L.lib()
+    k, s = cv.kernel_size[0], cv.stride[0]
+    d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=k, stride=s,
+                   x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=code)
+    # "s3", 6 bytes per weight: the layers that never run as Winograd (1x1, stride 2, fewer than 64 channels on a side), if split-3 runs them
+    if k == 1 or s == 2 or min(cv.in_channels, cv.out_channels) < 64:
+        return lib.yolo_split3_weight_bytes(C.byref(d))
+    # "u4a": the 3x3 stride-1 blocks whose small maps run as Winograd F(4x4) once their filters lie behind the packed weights (the
+    # library names them by their channel counts: the seven 512 -> 1024 blocks of YOLOv3, 75.5 MB each)
+    if k == 3 and s == 1 and lib.yolo_wino4_appended_wanted(C.byref(d)):
+        return lib.yolo_wino4_appended_bytes(C.byref(d))
+    return 0
+
+
 class PackedBlock:
     """Device-side packed weights + folded BN of one CNNBlock."""
 
@@ -195,21 +228,7 @@ class PackedBlock:
         if n == 0 and not (stem_ok and dtype != "fp32"):
             raise NotImplementedError(f"conv {cv.in_channels}->{cv.out_channels} k{cv.kernel_size[0]} has no {dtype} kernel "
                                       "(16-bit needs cin % 32 == 0)")
-        # fp32 layers that never run as Winograd (1x1, stride 2, fewer than 64 channels on a side) and that conv_split3_f32 can run
-        # get room behind the packed weights for their bf16 planes (want_s3; 6 bytes per weight): the buffer cannot grow
-        # later, plans hold its address
-        room = 0
-        if dtype == "fp32" and n and (cv.kernel_size[0] == 1 or cv.stride[0] == 2 or min(cv.in_channels, cv.out_channels) < 64):
-            d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=cv.kernel_size[0], stride=cv.stride[0],
-                           x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=self.code)
-            room = lib.yolo_split3_weight_bytes(C.byref(d))
-        # ... and the fp32 3x3 stride-1 blocks whose small maps run as Winograd F(4x4) once their filters lie behind the packed
-        # weights (want_u4a; the library names them by their channel counts: the seven 512 -> 1024 blocks of YOLOv3, 75.5 MB each)
-        elif dtype == "fp32" and n and cv.kernel_size[0] == 3 and cv.stride[0] == 1:
-            d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=3, stride=1,
-                           x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=self.code)
-            if lib.yolo_wino4_appended_wanted(C.byref(d)):
-                room = lib.yolo_wino4_appended_bytes(C.byref(d))
+        room = _prepared_room(cv, self.code) if dtype == "fp32" and n else 0
         self.w = torch.empty(max(n, room, 16), dtype=torch.uint8, device=device)
         self.scale = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.shift = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
@@ -218,23 +237,9 @@ class PackedBlock:
         if stem_ok:
             self.stem_w = torch.empty(27 * cv.out_channels, dtype=torch.float32, device=device)   # [27][cout]
         self.stamp = None                 # conv weight (data_ptr, version) the packed copy was made from
-        # Winograd F(4x4) filters U4 = G g G^T of the packed weights (yolo_wino4_filters), for the eval plans whose launch of
-        # this block picks tile 15: they depend on (cout, cin) only, so one buffer serves every plan. Made in
-        # ModelState._refresh_weights_slow whenever u4_stamp falls behind stamp.
-        self.u4 = None
-        self.u4_desc = None
-        self.u4_stamp = None
-        # The bf16 planes of the packed weights (yolo_split3_weights), for the eval plans whose launch of this block carries
-        # YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY: a view of w (packed weights, then planes) once a plan wants them;
-        # they too depend on (cout, cin, ksize) only and follow the stamp.
-        self.s3 = None
-        self.s3_desc = None
-        self.s3_stamp = None
-        # The same filters U4 behind the packed weights in w (yolo_wino4_filters in place), for the eval plans whose launch of this
-        # block carries YOLO_FLAG_FILTERS_APPENDED: a view of w once a plan wants them; they follow the stamp like u4 and s3.
-        self.u4a = None
-        self.u4a_desc = None
-        self.u4a_stamp = None
+        # kind of _PREPARED -> (buf: its buffer or view, desc: the descriptor it was sized with, stamp: the weight stamp it was made
+        # from, None = stale), once a plan wanted it
+        self.prepared = {}
         self.fold_stamp = None            # same for the tensors behind scale / shift; None = not folded
         self.folded = False
 
@@ -273,55 +278,34 @@ class PackedBlock:
             return ((conv._parameters, "weight"), (pr, "weight"), (pr, "bias"), (bf, "running_mean"), (bf, "running_var"))
         return ((conv._parameters, "weight"), (conv._parameters, "bias"))
 
-    def want_u4(self, desc):
-        """An eval plan runs this block as Winograd F(4x4) with YOLO_FLAG_FILTERS_READY: own the transformed filters."""
-        if self.u4 is None:
-            n = L.lib().yolo_wino4_filter_bytes(C.byref(desc))
-            if n == 0:
-                raise L.YoloLibError("yolo_wino4_filter_bytes: the layer cannot run as tile 15")
-            self.u4_desc = L.ConvDesc.from_buffer_copy(desc)
-            self.u4 = torch.empty(n, dtype=torch.uint8, device=self.w.device)
-            self.u4_stamp = None
-        return self.u4
-
-    def refresh_u4(self, stream):
-        """U4 from the packed weights as they are now (call after the pack on the same stream)."""
-        L.check(L.lib().yolo_wino4_filters(C.byref(self.u4_desc), self.w.data_ptr(), self.u4.data_ptr(), stream), "yolo_wino4_filters")
-        self.u4_stamp = self.stamp
-
-    def want_s3(self, desc):
-        """An eval plan runs this block as split products with YOLO_FLAG_SPLIT_WEIGHTS_READY: the bf16 planes are made in place,
-        behind the packed weights in ``w`` (the launch keeps its ``w_packed``). None: ``w`` has no room for them."""
-        if self.s3 is None:
-            n = L.lib().yolo_split3_weight_bytes(C.byref(desc))
-            if n == 0 or n > self.w.numel():
+    def want(self, kind, desc):
+        """An eval plan runs this block on prepared form ``kind`` (_PREPARED): its buffer or view, sized once from ``desc``. The
+        forms inside ``w`` leave the launch its ``w_packed``, and are None where ``w`` has no room for them."""
+        p = self.prepared.get(kind)
+        if p is None:
+            size, where, _ = _PREPARED[kind]
+            n = getattr(L.lib(), size)(C.byref(desc))
+            if where == "own" and n == 0:
+                raise L.YoloLibError(f"{size}: the layer cannot run as tile 15")
+            if where != "own" and (n == 0 or n > self.w.numel()):
                 return None
-            self.s3_desc = L.ConvDesc.from_buffer_copy(desc)
-            self.s3 = self.w[:n]
-            self.s3_stamp = None
-        return self.s3
+            buf = (torch.empty(n, dtype=torch.uint8, device=self.w.device) if where == "own" else self.w[:n] if where == "front"
+                   else self.w[n - L.lib().yolo_wino4_filter_bytes(C.byref(desc)):n])
+            p = self.prepared[kind] = SimpleNamespace(buf=buf, desc=L.ConvDesc.from_buffer_copy(desc), stamp=None)
+        return p.buf
 
-    def refresh_s3(self, stream):
-        """The planes from the packed weights as they are now (call after the pack on the same stream)."""
-        L.check(L.lib().yolo_split3_weights(C.byref(self.s3_desc), self.w.data_ptr(), self.w.data_ptr(), stream), "yolo_split3_weights")
-        self.s3_stamp = self.stamp
+    def refresh_prepared(self, stream):
+        """Re-make every form whose stamp fell behind the packed weights as they are now (call after the pack on the same stream)."""
+        for kind, p in self.prepared.items():
+            if p.stamp is None or p.stamp != self.stamp:
+                make = _PREPARED[kind][2]
+                L.check(getattr(L.lib(), make)(C.byref(p.desc), self.w.data_ptr(), p.buf.data_ptr(), stream), make)
+                p.stamp = self.stamp
 
-    def want_u4a(self, desc):
-        """An eval plan runs this block as Winograd F(4x4) with YOLO_FLAG_FILTERS_APPENDED: the filters are made in place, behind
-        the packed weights in ``w`` (the launch keeps its ``w_packed``). None: ``w`` has no room for them."""
-        if self.u4a is None:
-            n = L.lib().yolo_wino4_appended_bytes(C.byref(desc))
-            if n == 0 or n > self.w.numel():
-                return None
-            self.u4a_desc = L.ConvDesc.from_buffer_copy(desc)
-            self.u4a = self.w[n - L.lib().yolo_wino4_filter_bytes(C.byref(desc)):n]
-            self.u4a_stamp = None
-        return self.u4a
-
-    def refresh_u4a(self, stream):
-        """U4 behind the packed weights as they are now (call after the pack on the same stream)."""
-        L.check(L.lib().yolo_wino4_filters(C.byref(self.u4a_desc), self.w.data_ptr(), self.u4a.data_ptr(), stream), "yolo_wino4_filters")
-        self.u4a_stamp = self.stamp
+    def stale_prepared(self):
+        """The packed weights are about to change, or can no longer be trusted: every form is re-made by the next eval-side refresh."""
+        for p in self.prepared.values():
+            p.stamp = None
 
     def refresh(self, block, stream, fold_bn=True, conv_packed=False, pack=True):
         """fold_bn=False (training: batch statistics are used, not the running ones) skips the BN fold.
@@ -333,9 +317,7 @@ class PackedBlock:
         if w.dtype != torch.float32 or not w.is_contiguous():
             w = w.float().contiguous()
         if pack:
-            self.u4_stamp = None          # (the training path re-packs every step and never reads U4: it is re-made on the eval side)
-            self.s3_stamp = None          # (likewise the bf16 planes)
-            self.u4a_stamp = None         # (and the filters behind the packed weights)
+            self.stale_prepared()         # (the training path re-packs every step and never reads them: re-made on the eval side)
             if self.packs_conv and not conv_packed:
                 L.check(lib.yolo_pack_weights(w.data_ptr(), self.w.data_ptr(), cv.out_channels, cv.in_channels,
                                               cv.kernel_size[0], self.code, stream), "yolo_pack_weights")
@@ -355,6 +337,37 @@ class PackedBlock:
                                      cv.out_channels, stream), "yolo_bn_fold")
         self.stamp, fstamp = self.stamp_of(block)
         self.fold_stamp = fstamp if self.folded else None
+
+
+def _kernel_variant(state, pk, d, op, tile_override):
+    """(flags to add, w_packed) of one fp32 launch behind the stem in an eval plan: which of the library's kernel variants it runs,
+    on which prepared weights. The first that applies wins, and the order matters: the library refuses the combinations (split-K
+    goes with no other kernel flag, the finished filters with no split), so a launch takes one variant, the one further up."""
+    lib, dp = L.lib(), C.byref(d)
+    wino_shape = op["k"] == 3 and op["s"] == 1
+    # latency mode (ModelState.latency): the layers that measured faster at batch 1 cut along K (the library's splitk_eligible
+    # keeps the list; "all": every layer it can run that way)
+    if state.latency and not tile_override and (lib.yolo_conv_splitk_supported if state.latency == "all" else lib.yolo_conv_splitk_eligible)(dp):
+        return L.FLAG_SPLIT_K, pk.w.data_ptr()
+    # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
+    if (wino_shape and (tile_override or 0) in (0, 15) and lib.yolo_conv_workspace_bytes(dp)
+            and (d.tile == 15 or lib.yolo_conv_pick_tile(dp) == 15)):
+        return L.FLAG_FILTERS_READY, pk.want("u4", d).data_ptr()
+    # ... so do the small maps that measured faster as F(4x4) once nothing transforms their filters per launch: the library picks tile
+    # 15 for them when the filters lie behind the packed weights, where the block keeps room (wino4_small = False keeps F(2x2))
+    if state.wino4_small and not state.latency and not tile_override and wino_shape:
+        probe = L.ConvDesc.from_buffer_copy(d)
+        probe.flags |= L.FLAG_FILTERS_APPENDED
+        if (lib.yolo_conv_pick_tile(C.byref(probe)) == 15 and lib.yolo_conv_workspace_bytes(C.byref(probe)) > 0
+                and pk.want("u4a", d) is not None):
+            return L.FLAG_FILTERS_APPENDED, pk.w.data_ptr()
+    # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
+    # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
+    if state.split3 and not tile_override and (lib.yolo_conv_split3_supported if state.split3 == "all" else lib.yolo_conv_split3_eligible)(dp):
+        # ... on weights split once, in place behind the packed ones ("inflight": by every launch, for A/B runs)
+        ready = state.split3 != "inflight" and pk.want("s3", d) is not None
+        return L.FLAG_SPLIT_BF16 | (L.FLAG_SPLIT_WEIGHTS_READY if ready else 0), pk.w.data_ptr()
+    return 0, pk.w.data_ptr()
 
 
 class Plan:
@@ -436,31 +449,9 @@ class Plan:
             if i >= self.first:
                 e.x = self.phys[x.buf].data_ptr()
             e.w_packed, e.scale, e.shift = pk.w.data_ptr(), pk.scale.data_ptr(), pk.shift.data_ptr()
-            # latency mode (ModelState.latency): the layers that measured faster at batch 1 cut along K (the library's
-            # splitk_eligible keeps the list; "all": every layer it can run that way). Such a launch takes none of the flags below.
-            if (dtype == "fp32" and state.latency and i >= self.first and not tile_override
-                    and (L.lib().yolo_conv_splitk_supported if state.latency == "all" else L.lib().yolo_conv_splitk_eligible)(C.byref(d))):
-                d.flags |= L.FLAG_SPLIT_K
-            # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
-            elif (dtype == "fp32" and i >= self.first and op["k"] == 3 and op["s"] == 1 and (tile_override or 0) in (0, 15)
-                    and L.lib().yolo_conv_workspace_bytes(C.byref(d))
-                    and (d.tile == 15 or L.lib().yolo_conv_pick_tile(C.byref(d)) == 15)):
-                e.w_packed = pk.want_u4(d).data_ptr()
-                d.flags |= L.FLAG_FILTERS_READY
-            # ... so do the small maps that measured faster as F(4x4) once nothing transforms their filters per launch: the
-            # library picks tile 15 for them when the filters lie behind the packed weights, where the block keeps room for them
-            # (ModelState.wino4_small = False keeps F(2x2))
-            elif (dtype == "fp32" and state.wino4_small and not state.latency and i >= self.first and not tile_override
-                    and op["k"] == 3 and op["s"] == 1 and self._picks_wino4_appended(d) and pk.want_u4a(d) is not None):
-                d.flags |= L.FLAG_FILTERS_APPENDED
-            # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
-            # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
-            elif (dtype == "fp32" and state.split3 and i >= self.first and not tile_override
-                    and (L.lib().yolo_conv_split3_supported if state.split3 == "all" else L.lib().yolo_conv_split3_eligible)(C.byref(d))):
-                d.flags |= L.FLAG_SPLIT_BF16
-                # ... on weights split once, in place behind the packed ones ("inflight": by every launch, for A/B runs)
-                if state.split3 != "inflight" and pk.want_s3(d) is not None:
-                    d.flags |= L.FLAG_SPLIT_WEIGHTS_READY
+            if dtype == "fp32" and i >= self.first:
+                flags, e.w_packed = _kernel_variant(state, pk, d, op, tile_override)
+                d.flags |= flags
             if i == 0 and self.stem is not None:
                 self.stem_pk = pk
             if op["pred"] is not None:
@@ -478,13 +469,6 @@ class Plan:
         self.blocks0 = self.blocks[:1]    # the stem block alone (its own freshness check, see ModelState.forward)
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.dropped = False
-
-    @staticmethod
-    def _picks_wino4_appended(d):
-        """Does the library run this launch as tile 15 once YOLO_FLAG_FILTERS_APPENDED is set?"""
-        probe = L.ConvDesc.from_buffer_copy(d)
-        probe.flags |= L.FLAG_FILTERS_APPENDED
-        return L.lib().yolo_conv_pick_tile(C.byref(probe)) == 15 and L.lib().yolo_conv_workspace_bytes(C.byref(probe)) > 0
 
     def load_input(self, xin, stream):
         """NCHW fp32 input -> first activation: stem kernel, or the NHWC boundary copy."""
@@ -511,6 +495,36 @@ class ModelState:
     """Per-model caches (packed weights, plans). Holds no reference to the model so that the
     model stays picklable / deep-copyable."""
 
+    # The settings that travel with a pickled or deep-copied model: name -> (default, written to the pickle also at its default).
+    # __init__ and the three special methods read this table, so a new setting is listed here once; a state pickled before a
+    # setting existed loads with its default.
+    PERSISTED = {
+        # True: the NaN guards of model.py:175,183-184 raise inside the forward that saw the NaN (one host sync per forward).
+        # "deferred" (train mode only): they raise at the start of the next forward, or from flush_nan() - the eager fine-tune
+        # step then never waits for its own forward before enqueueing the backward. False: no guard.
+        "nan_check": (True, True),
+        # Under an active torch.autocast the reference's forward returns its predictions in the autocast dtype (the head
+        # conv runs in fp16 / bf16: model.py:145-148 under train.py:53). True = do the same (the heads are computed with fp32
+        # accumulation and rounded ONCE); False = always hand out the fp32 heads. Outside autocast the heads are fp32 either way
+        # (also with an explicit ``compute_dtype``): detect() / decode read them at full precision.
+        "autocast_heads": (True, True),
+        # fp32 inference: the direct convolutions that measured faster that way run as three-way bf16 split products
+        # (YOLO_FLAG_SPLIT_BF16: fp32 accuracy, other bits). False: plans made from then on keep the exact-f32 kernels.
+        # "all": every launch the library honours the flag on, measured faster or not (A/B runs, tests). True and "all" read
+        # weights split into their bf16 planes once per weight update (YOLO_FLAG_SPLIT_WEIGHTS_READY, PackedBlock.want("s3"));
+        # "inflight": the launches of True, every one splitting the packed weights itself (same bits; A/B runs).
+        "split3": (True, True),
+        # fp32 inference at small batches (single-image detection, demo.py:41-42): True = eval plans made from then on run the
+        # layers that measured faster that way at batch 1 cut along K (YOLO_FLAG_SPLIT_K: fp32 accuracy, other bits; the plan's
+        # workspace grows linearly with the batch). "all": every layer the library can run that way (A/B runs, tests).
+        "latency": (False, True),
+        # fp32 inference: the 3x3 stride-1 layers on small maps that measured faster as Winograd F(4x4) with their filters made
+        # once run that way (YOLO_FLAG_FILTERS_APPENDED; the 13 x 13 and 19 x 19 layers 512 -> 1024). False: plans made from then
+        # on keep F(2x2) there (A/B runs; the rule cannot look at the batch, and a small batch fills fewer CUs with half
+        # workgroups than with F(2x2) blocks: DESIGN 4.12).
+        "wino4_small": (True, False),        # (an A/B setting: written only where it is not the default)
+    }
+
     def __init__(self, model=None):
         # keyed by the block MODULE (weakly): an id()-keyed cache could hand a new block the packed
         # weights of a dead one that happened to reuse its address and parameter storage
@@ -520,35 +534,13 @@ class ModelState:
         self._gen = 0                     # bumped whenever packed state is declared out of date by hand (invalidate, mark_unfolded)
         self._fast = {}                   # (id(blocks), device, dtype) -> (gen, blocks, SlotGuard of the blocks' tensors, [(block, _pack_gen)])
         self._plans = {}
-        # True: the NaN guards of model.py:175,183-184 raise inside the forward that saw the NaN (one host sync per forward).
-        # "deferred" (train mode only): they raise at the start of the next forward, or from flush_nan() - the eager fine-tune
-        # step then never waits for its own forward before enqueueing the backward. False: no guard.
-        self.nan_check = True
+        for name, (default, _) in self.PERSISTED.items():
+            setattr(self, name, default)
         self._train_nan_pending = None   # not None: deferred guards are queued (see defer_nan)
         self._nan_host, self._nan_queue, self._nan_next = None, [], 0
         self.tile_override = None
-        # fp32 inference: the direct convolutions that measured faster that way run as three-way bf16 split products
-        # (YOLO_FLAG_SPLIT_BF16: fp32 accuracy, other bits). False: plans made from then on keep the exact-f32 kernels.
-        # "all": every launch the library honours the flag on, measured faster or not (A/B runs, tests). True and "all" read
-        # weights split into their bf16 planes once per weight update (YOLO_FLAG_SPLIT_WEIGHTS_READY, PackedBlock.want_s3);
-        # "inflight": the launches of True, every one splitting the packed weights itself (same bits; A/B runs).
-        self.split3 = True
-        # fp32 inference: the 3x3 stride-1 layers on small maps that measured faster as Winograd F(4x4) with their filters made
-        # once run that way (YOLO_FLAG_FILTERS_APPENDED; the 13 x 13 and 19 x 19 layers 512 -> 1024). False: plans made from then
-        # on keep F(2x2) there (A/B runs; the rule cannot look at the batch, and a small batch fills fewer CUs with half
-        # workgroups than with F(2x2) blocks: DESIGN 4.12).
-        self.wino4_small = True
-        # fp32 inference at small batches (single-image detection, demo.py:41-42): True = eval plans made from then on run the
-        # layers that measured faster that way at batch 1 cut along K (YOLO_FLAG_SPLIT_K: fp32 accuracy, other bits; the plan's
-        # workspace grows linearly with the batch). "all": every layer the library can run that way (A/B runs, tests).
-        self.latency = False
         self.compute_dtype = None        # None: follow torch.autocast (fp32 outside it); or "fp32" / "fp16" / "bf16"
         self.ddp = None                  # (torch.distributed module, bucket MB) when data-parallel (dist.data_parallel)
-        # Under an active torch.autocast the reference's forward returns its predictions in the autocast dtype (the head
-        # conv runs in fp16 / bf16: model.py:145-148 under train.py:53). True = do the same (the heads are computed with fp32
-        # accumulation and rounded ONCE); False = always hand out the fp32 heads. Outside autocast the heads are fp32 either way
-        # (also with an explicit ``compute_dtype``): detect() / decode read them at full precision.
-        self.autocast_heads = True
         # Plans own their activation buffers (a batch-64 608x608 training plan is ~60 GB): keep the most recently
         # used few, so multi-scale training (train.py:45-46 switches S every 10 batches) does not accumulate one
         # full set of buffers per size.
@@ -569,28 +561,11 @@ class ModelState:
         return plan
 
     def __getstate__(self):
-        st = {"nan_check": self.nan_check, "autocast_heads": self.autocast_heads, "split3": self.split3,
-              "latency": self.latency}
-        if not self.wino4_small:          # (an A/B setting: written only where it is not the default)
-            st["wino4_small"] = False
-        return st
+        return {k: getattr(self, k) for k, (default, always) in self.PERSISTED.items() if always or getattr(self, k) != default}
 
-    def __setstate__(self, st):
+    def __setstate__(self, st):           # (copy.deepcopy comes here too, with what __getstate__ gave: no __deepcopy__ of its own)
         self.__init__()
-        self.nan_check = st.get("nan_check", True)
-        self.autocast_heads = st.get("autocast_heads", True)
-        self.split3 = st.get("split3", True)
-        self.latency = st.get("latency", False)
-        self.wino4_small = st.get("wino4_small", True)
-
-    def __deepcopy__(self, memo):
-        new = ModelState()
-        new.nan_check = self.nan_check
-        new.autocast_heads = self.autocast_heads
-        new.split3 = self.split3
-        new.latency = self.latency
-        new.wino4_small = self.wino4_small
-        return new
+        self.__dict__.update({k: v for k, v in st.items() if k in self.PERSISTED})
 
     def head_dtype(self):
         """dtype the prediction tensors are handed out in (see ``autocast_heads``)."""
@@ -604,9 +579,7 @@ class ModelState:
         for per_dev in self._packed.values():
             for pk in per_dev.values():
                 pk.stamp = None
-                pk.u4_stamp = None
-                pk.s3_stamp = None
-                pk.u4a_stamp = None
+                pk.stale_prepared()
                 pk.fold_stamp = None
                 pk.folded = False
         if drop_plans:
@@ -676,13 +649,7 @@ class ModelState:
             pk.refresh(blk, stream, True, pack=False)
         if fold_bn:                       # eval: the transformed filters of the blocks that keep some follow the packed weights
             for blk in blocks:
-                pk = self.packed(blk, device, dtype)
-                if pk.u4 is not None and (pk.u4_stamp is None or pk.u4_stamp != pk.stamp):
-                    pk.refresh_u4(stream)
-                if pk.s3 is not None and (pk.s3_stamp is None or pk.s3_stamp != pk.stamp):
-                    pk.refresh_s3(stream)
-                if pk.u4a is not None and (pk.u4a_stamp is None or pk.u4a_stamp != pk.stamp):
-                    pk.refresh_u4a(stream)
+                self.packed(blk, device, dtype).refresh_prepared(stream)
 
     def mark_unfolded(self, blocks):
         """The BatchNorm running statistics of ``blocks`` were just written by a kernel (train-mode forward): every folded
