@@ -69,9 +69,18 @@ enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
  * yolo_conv_workspace_bytes asks for (16-byte aligned), else YOLO_ERR_WORKSPACE (always from yolo_conv_fwd, which has none).
  * Together with YOLO_FLAG_FILTERS_READY, YOLO_FLAG_FILTERS_APPENDED, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, with a forced tile, on a 16-bit
  * descriptor or with cin of 3 or 4 the flag is refused with YOLO_ERR_UNSUPPORTED and nothing is launched. Without the flag nothing
- * changes. */
+ * changes.
+ * YOLO_FLAG_WINO_SPLIT_BF16 (fp32 descriptors that run as tile 15 with its workspace, cin a multiple of 32, together with
+ * YOLO_FLAG_FILTERS_READY or YOLO_FLAG_FILTERS_APPENDED): the 36 Winograd GEMMs run on the bf16 matrix cores. The transform pass
+ * writes V4 as three bf16 planes per value (the exact split of YOLO_FLAG_SPLIT_BF16) and splits the caller's fp32 U4 the same way,
+ * on every launch, into the workspace behind them; six of the nine partial products are accumulated in fp32 in one fixed order. fp32
+ * accuracy (measured: DESIGN 4.15) but not the bits of the launch without the flag. Deterministic; an image's bits do not depend on
+ * its batch on finite data. An Inf or a NaN in x or in the filters turns every output it reaches into NaN (YOLO_FLAG_NANCHECK sees
+ * it). w_packed stays what the filter flag says; yolo_conv_workspace_bytes reports the planes, 36 * cin * (tiles_pad64 + cout_pad64)
+ * * 6 bytes. Together with YOLO_FLAG_SPLIT_K, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, without a filter flag, or on any
+ * other descriptor the flag is refused with YOLO_ERR_UNSUPPORTED. Without the flag nothing changes. */
 enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8,
-       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32, YOLO_FLAG_FILTERS_APPENDED = 64 };
+       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32, YOLO_FLAG_FILTERS_APPENDED = 64, YOLO_FLAG_WINO_SPLIT_BF16 = 128 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -239,6 +248,11 @@ int yolo_wino4_appended_wanted(const yolo_conv_desc* d);
  * *half tile blocks, those of a last round that would fill at most half the compute units, run as two workgroups of 32 tiles.
  * The result of a tile does not depend on the cut. */
 int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half);
+/* YOLO_FLAG_WINO_SPLIT_BF16 for plans (flags and tile of d are not looked at; the layer's shape only, never the batch).
+ * yolo_conv_wino4_split_supported: 1 when the library honours the flag on the layer once it runs as tile 15 on finished filters.
+ * yolo_conv_wino4_split_eligible: 1 when, in addition, the shape measured faster that way at batch 32 (the eval plan's list). */
+int yolo_conv_wino4_split_supported(const yolo_conv_desc* d);
+int yolo_conv_wino4_split_eligible(const yolo_conv_desc* d);
 
 /* ---- training: batch-statistics BatchNorm, activation, and the conv gradients ------------- */
 /* All of these replace pieces of `grad_scaler.scale(loss).backward()` / the train-mode forward of

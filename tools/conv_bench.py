@@ -6,6 +6,8 @@
   python tools/conv_bench.py --layer c52_s2 --tile 1,2,4 --split3-ready --rounds 5    (the same on weights split once: yolo_split3_weights)
   python tools/conv_bench.py --layer c13_3x3 --filters-ready --rounds 7 --reps 20    (tile 15 on filters transformed once: yolo_wino4_filters)
   python tools/conv_bench.py --layer c13_3x3,c19_3x3 --tile 0 --filters-appended --rounds 7    (the eval plan's route on the small maps)
+  python tools/conv_bench.py --layer c52_3x3 --filters-ready --wino-split both --rounds 7 --reps 20    (tile 15 with its GEMMs on f32 MFMAs,
+                                                                  then on bf16 planes: YOLO_FLAG_WINO_SPLIT_BF16, one process)
   python tools/conv_bench.py --splitk --rounds 7 --reps 100      (batch 1: every fp32 conv shape of the 416 and 608 networks on the
                                                                   default plan's launch and as YOLO_FLAG_SPLIT_K, alternating)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
@@ -52,7 +54,8 @@ LAYERS = {   # name: (H, cin, cout, k, stride)
 OUT_MODES = {"nhwc": L.OUT_NHWC, "up2x": L.OUT_UPSAMPLE2X, "head": L.OUT_HEAD}
 
 
-def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False, filters_ready=False, filters_appended=False):
+def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False, filters_ready=False, filters_appended=False,
+        wino_split=False):
     H, cin, cout, k, s = LAYERS[name]
     lib = L.lib()
     cpad = (cin + 3) // 4 * 4
@@ -89,6 +92,9 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
         L.check(lib.yolo_wino4_filters(d, wa.data_ptr(), wa.data_ptr() + wa.numel() - lib.yolo_wino4_filter_bytes(d), stream), "yolo_wino4_filters")
         wp = wa
 
+    if wino_split:                                                # the 36 GEMMs of tile 15 on bf16 planes (with either filter flag)
+        d.flags |= L.FLAG_WINO_SPLIT_BF16
+
     need = lib.yolo_conv_workspace_bytes(d)                       # > 0: Winograd (tile 13, or the heuristic's choice for tile 0)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
 
@@ -122,7 +128,7 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     if picked == 15:                                              # Winograd F(4x4): how the launch is cut on this device
         whole, half = C.c_int(), C.c_int()
         L.check(lib.yolo_conv_wino4_blocks(d, C.byref(whole), C.byref(half)), "yolo_conv_wino4_blocks")
-        cut += f"  tile blocks: {whole.value} whole + {half.value} in halves" + ("  filters ready" if filters_ready else "") + ("  filters appended" if filters_appended else "")
+        cut += f"  tile blocks: {whole.value} whole + {half.value} in halves" + ("  filters ready" if filters_ready else "") + ("  filters appended" if filters_appended else "") + ("  bf16 planes" if wino_split else "")
     print(f"{name:12s} tile={picked} {ms * 1e3:8.1f} us  {gflop / ms:7.2f} TFLOP/s  ({gflop:.1f} GFLOP){cut}", flush=True)
     return ms
 
@@ -205,6 +211,8 @@ def main():
     ap.add_argument("--split3-ready", action="store_true", help="YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY on prepared weights")
     ap.add_argument("--filters-ready", action="store_true", help="tile 15 with YOLO_FLAG_FILTERS_READY on filters made once (yolo_wino4_filters)")
     ap.add_argument("--filters-appended", action="store_true", help="YOLO_FLAG_FILTERS_APPENDED: U4 made in place behind the packed weights (tile 0: the eval plan's route)")
+    ap.add_argument("--wino-split", nargs="?", const="on", default="off", choices=["off", "on", "both"],
+                    help="YOLO_FLAG_WINO_SPLIT_BF16 on a --filters-ready / --filters-appended launch; 'both': without it, then with it")
     ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
     ap.add_argument("--splitk", action="store_true", help="batch-1 table: the default plan's launch against YOLO_FLAG_SPLIT_K, per conv shape")
@@ -218,7 +226,8 @@ def main():
     tiles = list(range(1, nt + 1)) if a.tile == "all" else [int(t) for t in a.tile.split(",")]
     for n in names:
         for t in tiles:
-            run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready, a.filters_ready, a.filters_appended)
+            for ws in {"off": (False,), "on": (True,), "both": (False, True)}[a.wino_split]:
+                run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready, a.filters_ready, a.filters_appended, ws)
 
 
 if __name__ == "__main__":

@@ -246,6 +246,15 @@ size_t wino4_workspace_bytes(const yolo_conv_desc* d);
 size_t wino4_filter_bytes(const yolo_conv_desc* d);
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
+// ... and the same layers with YOLO_FLAG_WINO_SPLIT_BF16 (cin % 32 == 0, the caller's finished fp32 U4): the transform pass of
+// conv_wino4_f32.hip writes V4 and U4 as bf16 planes (wino4_planes_launch), conv_wino4s_f32.hip runs the 36 GEMMs on them as three-way
+// split products. wino4_split_eligible: the shapes the eval plan runs that way
+bool wino4_split_supported(const yolo_conv_desc* d);
+bool wino4_split_eligible(const yolo_conv_desc* d);
+size_t wino4_split_workspace_bytes(const yolo_conv_desc* d);
+int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, void* workspace, hipStream_t s);
+int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const float* scale, const float* shift, const void* residual,
+                       void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)
 size_t h16_frag_elems(int cout, int cin, int ks);
 int h16_pack(const float* w_oihw, void* wf, int cout, int cin, int ks, int dtype, hipStream_t s);

@@ -1,6 +1,6 @@
 // conv_dispatch.hip — host side of yolo_conv_fwd, yolo_conv_fwd_ws, yolo_conv_fwd_batch and the queries next to them: which fp32 kernel
 // a descriptor runs, which flags may stand on it, where in the packed buffer that kernel's weights begin. No kernel lives here: they
-// are in conv_f32.hip, conv_f32_v2.hip, conv1_rs_f32.hip, conv_wino_f32.hip, conv_wino4_f32.hip, conv_split3_f32.hip, conv_splitk_f32.hip.
+// are in conv_f32.hip, conv_f32_v2.hip, conv1_rs_f32.hip, conv_wino_f32.hip, conv_wino4_f32.hip, conv_wino4s_f32.hip, conv_split3_f32.hip, conv_splitk_f32.hip.
 #include "conv_f32_epilogue.h"
 
 namespace yolo {
@@ -66,7 +66,8 @@ static F32Route f32_route(const yolo_conv_desc* d, const void* residual, size_t 
         if (d->flags & YOLO_FLAG_SPLIT_WEIGHTS_READY) r.weights_offset = sec().tail_bytes;
         break;
     case F32Kind::Wino4:            // (appended filters: U4 lies behind the packed weights; YOLO_FLAG_FILTERS_READY: w_packed is U4 itself)
-        r.workspace_need = wino4_workspace_bytes(d);
+        // (YOLO_FLAG_WINO_SPLIT_BF16: the bf16 planes of V4 and U4 instead; check_flags says where the flag may stand)
+        r.workspace_need = (d->flags & YOLO_FLAG_WINO_SPLIT_BF16) && wino4_split_supported(d) ? wino4_split_workspace_bytes(d) : wino4_workspace_bytes(d);
         if (d->flags & YOLO_FLAG_FILTERS_APPENDED) r.weights_offset = sec().tail_bytes;
         break;
     case F32Kind::Wino: r.workspace_need = wino_workspace_bytes(d); r.weights_offset = sec().wino * sizeof(float); break;
@@ -129,6 +130,17 @@ static int check_flags(const yolo_conv_desc* d, const F32Route& r, const void* w
                                           "ksize 1 or 3, stride 1 or 2 and cin %% 32 == 0");
     if ((d->flags & YOLO_FLAG_SPLIT_WEIGHTS_READY) && !split3)
         return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_WEIGHTS_READY goes with YOLO_FLAG_SPLIT_BF16 only");
+    // the Winograd F(4x4) GEMMs on bf16 planes: a variant of the launch on finished filters, and of nothing else
+    if (d->flags & YOLO_FLAG_WINO_SPLIT_BF16) {
+        if (!wino4 || !wino4_split_supported(d))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_WINO_SPLIT_BF16 needs an fp32 layer that runs as Winograd F(4x4) (tile 15 with its "
+                                              "workspace) with cin %% 32 == 0");
+        if (!(d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED)))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_WINO_SPLIT_BF16 goes with YOLO_FLAG_FILTERS_READY or YOLO_FLAG_FILTERS_APPENDED");
+        if (d->flags & (YOLO_FLAG_SPLIT_K | YOLO_FLAG_SPLIT_BF16 | YOLO_FLAG_SPLIT_WEIGHTS_READY))
+            return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_WINO_SPLIT_BF16 goes with none of YOLO_FLAG_SPLIT_K, YOLO_FLAG_SPLIT_BF16, "
+                                              "YOLO_FLAG_SPLIT_WEIGHTS_READY");
+    }
     return YOLO_OK;
 }
 
@@ -168,6 +180,7 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     case F32Kind::Wino4: {          // the filters are transformed per launch from the row-major section, unless the caller brings U4
         if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         const float* U4 = d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED) ? (const float*)wr : nullptr;
+        if (d->flags & YOLO_FLAG_WINO_SPLIT_BF16) return conv_wino4s_launch(d, x, U4, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
         return conv_wino4_launch(d, x, U4 ? nullptr : (const float*)w, U4, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
     }
     case F32Kind::Wino:
@@ -205,6 +218,17 @@ int yolo_conv_split3_supported(const yolo_conv_desc* d) {
 }
 
 int yolo_conv_split3_eligible(const yolo_conv_desc* d) { return yolo_conv_split3_supported(d) && yolo::split3_eligible(d); }
+
+// YOLO_FLAG_WINO_SPLIT_BF16 is honoured on the launches that run as tile 15 on finished filters (here: what the heuristic routes there
+// with either filter flag) with cin % 32 == 0
+int yolo_conv_wino4_split_supported(const yolo_conv_desc* d) {
+    if (yolo::validate(d) || d->dtype != YOLO_F32 || !yolo::wino4_split_supported(d)) return 0;
+    yolo_conv_desc h = *d;
+    h.flags = 0;
+    return yolo::heuristic_route(&h, 0).kind == yolo::F32Kind::Wino4 || yolo::heuristic_route(&h, YOLO_FLAG_FILTERS_APPENDED).kind == yolo::F32Kind::Wino4;
+}
+
+int yolo_conv_wino4_split_eligible(const yolo_conv_desc* d) { return yolo_conv_wino4_split_supported(d) && yolo::wino4_split_eligible(d); }
 
 int yolo_conv_splitk_supported(const yolo_conv_desc* d) { return !yolo::validate(d) && yolo::splitk_supported(d); }
 

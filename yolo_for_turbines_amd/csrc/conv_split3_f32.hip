@@ -43,11 +43,9 @@
 // 64x64 blocks have the two slots already (48 KB), a 128x128 block takes 72 KB with them (still two workgroups per CU), a 128x64
 // block would take 48 KB and lose its fourth workgroup, so that tile copies through registers (ds_write_b128, 36 KB as before).
 #include "conv_f32_epilogue.h"
+#include "split3.h"
 
 namespace yolo {
-
-typedef __bf16 s3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int s3_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int S3_ROWB = 64;      // bytes per LDS row: 32 bf16 as four 16-byte slots, slot s of row r stored at s ^ ((r >> 2) & 3)
 
@@ -57,24 +55,6 @@ __device__ __forceinline__ int s3_row_off(int r, int chunk) { return r * S3_ROWB
 typedef const __attribute__((address_space(1))) void* s3_gptr;
 typedef __attribute__((address_space(3))) void* s3_lptr;
 __device__ __forceinline__ void s3_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((s3_gptr)g, (s3_lptr)l, 16, 0, 0); }
-
-// two floats' upper halves as one bf16 pair, `a` in the low half (the lower k)
-__device__ __forceinline__ unsigned s3_pack(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
-// v = hi + mid + lo exactly, each with 8 significand bits; chk turns NaN when v holds an Inf or a NaN
-__device__ __forceinline__ void s3_split(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo, f32x4& chk) {
-    const s3_u32x4 vb = __builtin_bit_cast(s3_u32x4, v);
-    const f32x4 h = __builtin_bit_cast(f32x4, vb & 0xffff0000u);
-    const f32x4 r1 = v - h;
-    const s3_u32x4 r1b = __builtin_bit_cast(s3_u32x4, r1);
-    const f32x4 m = __builtin_bit_cast(f32x4, r1b & 0xffff0000u);
-    const f32x4 r2 = r1 - m;
-    const s3_u32x4 r2b = __builtin_bit_cast(s3_u32x4, r2);
-    chk += r2 * 0.f;
-    hi[0] = s3_pack(vb[0], vb[1]); hi[1] = s3_pack(vb[2], vb[3]);
-    mid[0] = s3_pack(r1b[0], r1b[1]); mid[1] = s3_pack(r1b[2], r1b[3]);
-    lo[0] = s3_pack(r2b[0], r2b[1]); lo[1] = s3_pack(r2b[2], r2b[3]);
-}
 
 // Prepared weights of yolo_split3_weights: one block per 32 output channels, the staging geometry of conv_split3_f32 (thread =
 // row tid >> 3, 16-byte chunk tid & 7 of every K step), so that the bytes written are the ones store_lds would have written.

@@ -18,6 +18,8 @@
 //                    computed per launch and lives in the workspace behind V4: the packed weight format stays as it is.
 //                    Inference, whose weights stay the same from call to call, makes U4 once instead (wino4_filters_f32 through
 //                    yolo_wino4_filters, YOLO_FLAG_FILTERS_READY): the launch then has no filter blocks.
+//                    wino4_xform_f32<true> (YOLO_FLAG_WINO_SPLIT_BF16) writes the same V4, and the caller's finished U4, as bf16 planes
+//                    for conv_wino4s_f32.hip instead (wino4_planes.h).
 //   conv_wino4_f32   per workgroup 64 tiles x 64 output channels (the block of conv_wino_f32: the same operand bytes per MFMA, so
 //                    the same LDS-DMA price per matrix cycle): 36 GEMMs D_xi[co][tile] = sum_ci U4_xi[co][ci] V4_xi[tile][ci] in SIX
 //                    passes over K, one row a of the 6x6 product matrix M per pass (xi = 6a .. 6a + 5). Y = A^T M A is linear in the
@@ -30,6 +32,8 @@
 //                    One workgroup per CU and round: the tile blocks of a last round that would fill at most half the CUs run as
 //                    two workgroups of 32 tiles each (wino4_whole_blocks), the same 16 x 16 MFMA blocks in the same order on half
 //                    the waves, so a tile's bits do not depend on the cut.
+#include "split3.h"
+#include "wino4_planes.h"
 #include "wino_dma.h"
 
 namespace yolo {
@@ -105,9 +109,35 @@ __global__ __launch_bounds__(256) void wino4_filters_f32(const Wino4XArgs p) {
     wino4_filter_elems(p, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
+// The same filters as bf16 planes (wino4_planes.h), from the finished fp32 U4 that p.w points at here, into p.U: element i =
+// (xi, chunk, co, channel quad of the chunk), the quad running fastest so that eight threads write one 64-byte row of each plane
+__device__ __forceinline__ void wino4_filter_planes(const Wino4XArgs& p, long long first, long long stride) {
+    const int nkc = p.C4p / 8, n_nt = p.coutp / 64;
+    char* out = reinterpret_cast<char*>(p.U);
+    for (long long i = first; i < 9 * p.utotal; i += stride) {      // 36 xi x C4p x coutp
+        const int q = (int)(i & 7);
+        const long long r = i >> 3;
+        const int co = (int)(r % p.coutp);
+        const int kx = (int)(r / p.coutp), kc = kx % nkc, xi = kx / nkc;
+        const f32x4 u = *reinterpret_cast<const f32x4*>(p.w + (((size_t)xi * p.C4p + 8 * kc + q) * p.coutp + co) * 4);
+        u32x2 h, m, l;
+        f32x4 chk = {0.f, 0.f, 0.f, 0.f};
+        s3_split(u, h, m, l, chk);
+        char* d = out + w4s_offset(xi, 32 * kc + 4 * q, co, 0, nkc, n_nt);
+        *reinterpret_cast<u32x2*>(d) = h;
+        *reinterpret_cast<u32x2*>(d + W4S_PLANE) = m;
+        *reinterpret_cast<u32x2*>(d + 2 * W4S_PLANE) = l;
+    }
+}
+
+// PLANES (YOLO_FLAG_WINO_SPLIT_BF16, C4 % 8 == 0): the same values v, each split into three bf16 (s3_split) and stored as the planes
+// of wino4_planes.h in place of V4; the blocks behind the input transform split the caller's finished U4 the same way
+template <bool PLANES>
 __global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
     if ((int)blockIdx.x >= p.nxb) {
-        wino4_filter_elems(p, (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x, (long long)(gridDim.x - p.nxb) * blockDim.x);
+        const long long first = (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x, stride = (long long)(gridDim.x - p.nxb) * blockDim.x;
+        if constexpr (PLANES) wino4_filter_planes(p, first, stride);
+        else wino4_filter_elems(p, first, stride);
         return;
     }
     // 8 lanes = the 8 channel quads of one pixel's 128-byte line, 8 tiles per wave (the access pattern of wino_xform_f32)
@@ -156,6 +186,24 @@ __global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
             if (W4_BT[i][k] != 0.f)
 #pragma unroll
                 for (int l = 0; l < 6; ++l) v[i][l] += W4_BT[i][k] * e[l];
+    }
+    if constexpr (PLANES) {                              // the eight lanes of a tile write one 64-byte row of each plane
+        const int nkc = p.C4p / 8, n_mt = p.Tpad / 64;
+        char* dst = reinterpret_cast<char*>(p.V) + w4s_offset(0, 4 * c4, t, 0, nkc, n_mt);
+        const size_t xs = (size_t)nkc * n_mt * W4S_PIECE;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int l = 0; l < 6; ++l) {
+                u32x2 h, m, lo;
+                f32x4 chk = {0.f, 0.f, 0.f, 0.f};
+                s3_split(v[i][l], h, m, lo, chk);
+                char* d = dst + (6 * i + l) * xs;
+                *reinterpret_cast<u32x2*>(d) = h;
+                *reinterpret_cast<u32x2*>(d + W4S_PLANE) = m;
+                *reinterpret_cast<u32x2*>(d + 2 * W4S_PLANE) = lo;
+            }
+        return;
     }
     float* dst = p.V + ((size_t)c4 * p.Tpad + t) * 4;
     const size_t xs = (size_t)p.C4p * p.Tpad * 4;
@@ -561,6 +609,32 @@ size_t wino4_filter_bytes(const yolo_conv_desc* d) {
     return (size_t)36 * round_up(d->cin / 4, 2) * round_up(d->cout, 64) * 4 * sizeof(float);
 }
 
+// ---- YOLO_FLAG_WINO_SPLIT_BF16: the transform pass writes bf16 planes (wino4_planes.h) for conv_wino4s_f32.hip
+bool wino4_split_supported(const yolo_conv_desc* d) { return wino4_supported(d) && d->cin % 32 == 0; }
+
+size_t wino4_split_workspace_bytes(const yolo_conv_desc* d) {
+    if (!wino4_split_supported(d)) return 0;
+    const size_t nkc = d->cin / 32, n_mt = (size_t)(wino4_tiles(d) + 63) / 64, n_nt = (size_t)round_up(d->cout, 64) / 64;
+    return 36 * nkc * (n_mt + n_nt) * W4S_PIECE;
+}
+
+// V planes at the start of the workspace, the planes of the caller's finished U4 behind them (made again by every launch: the plans
+// keep the fp32 U4 as the launch's weights)
+int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, void* workspace, hipStream_t s) {
+    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
+    const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4;
+    Wino4XArgs xa;
+    wino4_filter_args(xa, d, U4, nullptr);
+    xa.x = (const float*)x; xa.V = (float*)workspace; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
+    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = C4 / 8;
+    xa.nxb = (Tpad / 32) * xa.ncg;
+    xa.U = reinterpret_cast<float*>(static_cast<char*>(workspace) + (size_t)36 * (C4 / 8) * (Tpad / 64) * W4S_PIECE);
+    const long long ub = (9 * xa.utotal + 255) / 256;
+    const int nub = (int)(ub < 1024 ? ub : 1024);                     // (the grid bound that wino4_supported checked)
+    hipLaunchKernelGGL(wino4_xform_f32<true>, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
+    return check_launch("wino4_xform_f32 (planes)");
+}
+
 // w_rm: the row-major section at the start of the packed weights (yolo_pack_weights / yolo_pack_weights_dgrad); U4_ready: the
 // filters transformed before (yolo_wino4_filters), or NULL: this launch transforms them into the workspace behind V4
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
@@ -581,7 +655,7 @@ int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm,
     xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = ceil_div(C4p, 8);
     xa.nxb = (Tpad / 32) * xa.ncg;
     const int nub = U4_ready ? 0 : wino4_filter_blocks(xa);
-    hipLaunchKernelGGL(wino4_xform_f32, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
+    hipLaunchKernelGGL(wino4_xform_f32<false>, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
     if (int rc = check_launch("wino4_xform_f32")) return rc;
 
     Wino4Args a;

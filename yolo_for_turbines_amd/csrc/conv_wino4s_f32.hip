@@ -1,0 +1,258 @@
+// conv_wino4s_f32.hip — the 36 GEMMs of Winograd F(4x4, 3x3) on the bf16 matrix cores (YOLO_FLAG_WINO_SPLIT_BF16).
+//
+// conv_wino4_f32.hip multiplies on v_mfma_f32_16x16x4_f32, whose rate is the vector FMA rate. Here every fp32 value of V4 and U4
+// is the exact sum of three bf16 values (split3.h), split once where it is produced: the transform pass (wino4_xform_f32<true>)
+// writes the planes of wino4_planes.h. Six of the nine partial products in the fixed order of conv_split3_f32, smallest first,
+// (hi, lo) (lo, hi) (mid, mid) (hi, mid) (mid, hi) (hi, hi) with the U part named first, go into one fp32 accumulator by
+// v_mfma_f32_16x16x32_bf16: per 32 input channels, xi and 16 x 16 block six MFMAs of ~16 cycles instead of eight of 32. The kernel
+// has no split arithmetic and no finiteness vote: an Inf or a NaN of x becomes a NaN in the planes (Inf - Inf) and in every
+// output it reaches, which the epilogue's NaN flag reports.
+//
+// The skeleton is conv_wino4_f32's: 64 tiles x 64 output channels per workgroup, 8 waves, wave (wm, wn) owns tiles 32 wm .. + 31 and
+// channels 16 wn .. + 15 as two 16 x 16 blocks (the C/D layout of the two MFMAs is the same), six passes over K, one row of M each,
+// 48 accumulators per pass, the fold into 128 partial-tile registers parked in AGPRs, the tile table and the epilogue
+// (wino4_epilogue.h). Only the K loop and the ring differ:
+//   stage    one xi x 32 input channels: the 12 KiB piece of V (3 planes x 64 tiles x 64 bytes), then the 12 KiB piece of U. Both are
+//            contiguous in global memory and byte for byte the LDS image: 24 LDS-DMA wave-instructions of 1 KiB, three per wave
+//            (waves 0 - 3 move V, 4 - 7 move U). Stages run xi-fastest inside a pass: g = 6 chunk + x.
+//   ring     four slots of 24 KiB. Stage g + 3 is requested during stage g into the slot of stage g - 1.
+//   step g   wait for the own pieces of stage g + 1 (vmcnt), barrier: stage g + 1 is in LDS for everybody, and everybody has read
+//            stage g - 1 out of its slot. Then: request one piece of stage g + 3 behind each of the first MFMA pairs, read the nine
+//            fragments of stage g + 1 (3 U + 2 x 3 V, ds_read_b128, into the other fragment set), wait for those of stage g
+//            (lgkmcnt(9)), twelve MFMAs.
+// All workgroups are whole (no half workgroups: wino4_split_eligible names large maps only).
+#include "split3.h"
+#include "wino4_planes.h"
+#include "wino4_epilogue.h"
+
+namespace yolo {
+
+struct Wino4SArgs {
+    Wino4Args e;             // V / U: the plane buffers; C4p is unused
+    int nkc;                 // chunks of 32 input channels
+};
+
+constexpr int W4S_STAGE = 2 * W4S_PIECE; // bytes per ring stage: the V piece, then the U piece
+constexpr int W4S_SLOTS = 4;             // (a power of two: slot arithmetic by mask)
+constexpr int W4S_DMA = 3;               // DMA wave-instructions per wave and stage
+
+template <int OFF>
+__device__ __forceinline__ void w4s_read_at(s3_u32x4& f, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(f) : "v"(addr), "n"(OFF));
+}
+
+template <int ACT, bool RES>
+__global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Wino4Args& p = q.e;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15, kq = lane >> 4;
+    // block map of conv_wino4_f32: 8 tile blocks (one per XCD) x all channel blocks per row
+    const int xcd = blockIdx.x & 7, bq = blockIdx.x >> 3;
+    const int nt = bq % p.n_nt, mt = (bq / p.n_nt) * 8 + xcd;
+    if (mt >= p.n_mt) return;
+    const int wm = wave & 1, wn = wave >> 1;
+
+    int* tab = reinterpret_cast<int*>(smem + W4S_SLOTS * W4S_STAGE);
+    wino4_tile_table(p, tab, tid, mt, false, 0);
+
+    // ---- DMA roles: wave w moves KiB 3 w .. 3 w + 2 of a stage (lane = 16 bytes)
+    const bool dv = wave < 4;
+    const char* src = (dv ? reinterpret_cast<const char*>(p.V) + (size_t)mt * W4S_PIECE : reinterpret_cast<const char*>(p.U) + (size_t)nt * W4S_PIECE)
+                      + 3072 * (wave & 3);
+    const size_t s_st = (size_t)(dv ? p.n_mt : p.n_nt) * W4S_PIECE;          // bytes from one (xi, chunk) to the next
+    const unsigned lane16 = lane * 16;
+    const unsigned lds0 = (unsigned)(size_t)(wn_lptr)smem;
+    const int nkc = q.nkc;
+    auto issue_piece = [&](int k, int pass, int g, int slot) {               // stage g = 6 chunk + x of the pass
+        const int kc = g / 6, x = g - 6 * kc;
+        wn_glds16_s(src + ((size_t)(6 * pass + x) * nkc + kc) * s_st + k * 1024, lane16, lds0 + slot * W4S_STAGE + (3 * wave + k) * 1024);
+    };
+    auto issue = [&](int pass, int g, int slot) { wn_for<0, W4S_DMA>([&](auto K) { issue_piece(decltype(K)::value, pass, g, slot); }); };
+
+    // ---- fragment addresses in slot 0: rows 32 wm + l16 (+ 16) of the V planes, row 16 wn + l16 of the U planes, channels 8 kq ..
+    const unsigned sw = w4s_slot(l16, kq) * 16;          // (blocks start at multiples of 16 rows: the row quad is l16's)
+    const unsigned vb = lds0 + (32 * wm + l16) * 64 + sw;
+    const unsigned ub = lds0 + W4S_PIECE + (16 * wn + l16) * 64 + sw;
+
+    f32x4 py[2][4][4];
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) py[bb][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto run_pass = [&](auto PASS) {
+        constexpr int a = decltype(PASS)::value;
+        // Fragments of a stage: the U row and the V rows of the two tile blocks, per part. 48 accumulators leave the VGPR half no room
+        // for two whole sets (2 x 36), so only the hi parts, which the first and the last product of a stage read, have two (by
+        // stage parity); mid and lo are read again, for the next stage, as soon as their last product has been issued.
+        s3_u32x4 uh[2], vh[2][2], um, ul, vm[2], vl[2];
+        auto rd_hi = [&](auto SET, unsigned sb) {        // R1
+            constexpr int S = decltype(SET)::value;
+            w4s_read_at<0>(uh[S], ub + sb);
+            w4s_read_at<0>(vh[S][0], vb + sb);
+            w4s_read_at<1024>(vh[S][1], vb + sb);
+        };
+        auto rd_vlo = [&](unsigned sb) {                 // R2
+            w4s_read_at<2 * W4S_PLANE>(vl[0], vb + sb);
+            w4s_read_at<2 * W4S_PLANE + 1024>(vl[1], vb + sb);
+        };
+        auto rd_ulo = [&](unsigned sb) { w4s_read_at<2 * W4S_PLANE>(ul, ub + sb); };        // R3
+        auto rd_vmid = [&](unsigned sb) {                // R4
+            w4s_read_at<W4S_PLANE>(vm[0], vb + sb);
+            w4s_read_at<W4S_PLANE + 1024>(vm[1], vb + sb);
+        };
+        auto rd_umid = [&](unsigned sb) { w4s_read_at<W4S_PLANE>(um, ub + sb); };           // R5
+        auto mma = [&](f32x4 (&c)[2], const s3_u32x4& u, const s3_u32x4 (&v)[2]) {
+            const s3_bf16x8 fa = __builtin_bit_cast(s3_bf16x8, u);
+            c[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, __builtin_bit_cast(s3_bf16x8, v[0]), c[0], 0, 0, 0);
+            c[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, __builtin_bit_cast(s3_bf16x8, v[1]), c[1], 0, 0, 0);
+        };
+        if constexpr (a == 0) {              // (the first stages of passes 1 .. 5 are requested before the previous pass's fold)
+            issue(0, 0, 0);
+            issue(0, 1, 1);
+            issue(0, 2, 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 acc[6][2];
+#pragma unroll
+        for (int x = 0; x < 6; ++x)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) acc[x][bb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int x = 0; x < 6; ++x) asm volatile("" : "+v"(acc[x][0]), "+v"(acc[x][1]));
+        __builtin_amdgcn_sched_barrier(0);
+        wn_wait_vmcnt<2 * W4S_DMA>();                    // stage 0 has landed (mine), ...
+        __builtin_amdgcn_s_barrier();                    // ... everybody's
+        __builtin_amdgcn_sched_barrier(0);
+        rd_hi(std::integral_constant<int, 0>{}, 0u);     // the order R1 .. R5 in which every stage requests the next one's
+        rd_vlo(0u);
+        rd_ulo(0u);
+        rd_vmid(0u);
+        rd_umid(0u);
+
+        for (int kc = 0; kc < nkc; ++kc) {
+            const bool more = kc + 1 < nkc;              // another chunk behind this one
+            wn_for<0, 6>([&](auto X) {
+                constexpr int x = decltype(X)::value, set = x & 1;       // (6 is even: the hi set of stage g is x & 1)
+                const int g = 6 * kc + x;
+                const bool next = x < 5 || more;         // stage g + 1 exists
+                const bool ahead = x < 3 || more;        // stage g + 3 exists: it goes into the slot of stage g - 1
+                const unsigned nb = (unsigned)((g + 1) & (W4S_SLOTS - 1)) * W4S_STAGE;
+                const int as = (g + 3) & (W4S_SLOTS - 1);
+                __builtin_amdgcn_sched_barrier(0);
+                // The six products (U part, V part), smallest terms first, the order of conv_split3_f32. The waits count the reads
+                // requested behind the ones a product needs (LDS reads return in order): R3 R4 R5 of the stage before and R1 behind
+                // R2 = 7, and so on. The last stage of a pass reads the same way, from a slot that nothing is written to any
+                // more, into registers that nothing uses: no branch around the reads, one count for every stage.
+                if (next) {
+                    // stage g + 1 has to be in LDS for everybody before its fragments are read (the only requests younger than its
+                    // pieces are those of stage g + 2); the slot of stage g - 1 is free once everybody is here
+                    if (x < 4 || more) wn_wait_vmcnt<W4S_DMA>();
+                    else wn_wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                rd_hi(std::integral_constant<int, set ^ 1>{}, nb);
+                asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(uh[set]), "+v"(vl[0]), "+v"(vl[1]));
+                mma(acc[x], uh[set], vl);                // hi lo
+                __builtin_amdgcn_sched_barrier(0);
+                if (ahead) issue_piece(0, a, g + 3, as);
+                rd_vlo(nb);
+                asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(ul), "+v"(vh[set][0]), "+v"(vh[set][1]));
+                __builtin_amdgcn_sched_barrier(0);
+                mma(acc[x], ul, vh[set]);                // lo hi
+                __builtin_amdgcn_sched_barrier(0);
+                if (ahead) issue_piece(1, a, g + 3, as);
+                rd_ulo(nb);
+                asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(um), "+v"(vm[0]), "+v"(vm[1]));
+                __builtin_amdgcn_sched_barrier(0);
+                mma(acc[x], um, vm);                     // mid mid
+                __builtin_amdgcn_sched_barrier(0);
+                if (ahead) issue_piece(2, a, g + 3, as);
+                __builtin_amdgcn_sched_barrier(0);
+                mma(acc[x], uh[set], vm);                // hi mid
+                __builtin_amdgcn_sched_barrier(0);
+                rd_vmid(nb);
+                __builtin_amdgcn_sched_barrier(0);
+                mma(acc[x], um, vh[set]);                // mid hi
+                __builtin_amdgcn_sched_barrier(0);
+                rd_umid(nb);
+                __builtin_amdgcn_sched_barrier(0);
+                mma(acc[x], uh[set], vh[set]);           // hi hi
+            });
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();                                     // everybody is done with the ring: the next pass's first stages / the staging may overwrite it
+        if constexpr (a < 5) {                               // ... and they are requested now: in flight during the fold below
+            issue(a + 1, 0, 0);
+            issue(a + 1, 1, 1);
+            issue(a + 1, 2, 2);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        wino4_fold_row<a>(acc, py);
+    };
+    run_pass(std::integral_constant<int, 0>{});
+    run_pass(std::integral_constant<int, 1>{});
+    run_pass(std::integral_constant<int, 2>{});
+    run_pass(std::integral_constant<int, 3>{});
+    run_pass(std::integral_constant<int, 4>{});
+    run_pass(std::integral_constant<int, 5>{});
+
+    wino4_epilogue<ACT, RES>(p, smem, tab, py, tid, nt, wm, wn, l16, kq, true);
+}
+
+// ------------------------------------------------------------------------------ host side
+// Shapes that the eval plan runs on this kernel: looks at the layer's shape only, never at the batch. The rule of split3_eligible: a
+// shape is listed once its median at batch 32 (tools/conv_bench.py --filters-ready --wino-split both, 7 rounds of 20 launches,
+// transform pass and per-launch filter planes included) improved by more than the spread of its own baseline's rounds
+// (profiles/wino4_split/conv_bench.txt; medians in us, f32 GEMMs -> bf16 planes):
+//   256 -> 512 at 26 x 26     189 - 193 -> 134 - 136, with residual 197 - 199 -> 141 - 145 (baseline spread 15 - 18): listed.
+//   128 -> 256 at 52 x 52     185 - 195 -> 170 - 172, with residual 213 - 217 -> 199 - 203. Every round on planes beat every round
+//                             of its baseline, but the baseline's rounds spread 17 - 27 in six of the eight runs, more than the gain:
+//                             not listed.
+//   64 -> 128 at 104 x 104    253 -> 260 (V4 grows from 199 to 299 MB and is read by two channel blocks only): stays.
+//   512 -> 1024 at 13 x 13    220 -> 238 (128 whole workgroups on 256 CUs, and every launch splits 75.5 MB of U4): stays.
+// Nothing else was measured (the 38 x 38 and 76 x 76 maps of the 608 network stay on the f32 GEMMs).
+bool wino4_split_eligible(const yolo_conv_desc* d) {
+    return wino4_split_supported(d) && d->h == 26 && d->w == 26 && d->cin == 256 && d->cout == 512;
+}
+
+int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const float* scale, const float* shift, const void* residual,
+                       void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
+    if (!wino4_split_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4) on bf16 planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
+    const size_t need = wino4_split_workspace_bytes(d);
+    if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4) on bf16 planes: workspace %zu < %zu bytes", workspace_bytes, need);
+    if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: workspace must be 16-byte aligned");
+    if (!U4 || ((size_t)U4 & 15)) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: transformed filters must be 16-byte aligned");
+    if (int rc = wino4_planes_launch(d, x, U4, workspace, s)) return rc;
+
+    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
+    const int T = d->n * th * tw, Tpad = round_up(T, 64), CoutPad = round_up(d->cout, 64);
+    Wino4SArgs q;
+    Wino4Args& a = q.e;
+    q.nkc = d->cin / 32;
+    a.V = (const float*)workspace;
+    a.U = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + (size_t)36 * q.nkc * (Tpad / 64) * W4S_PIECE);
+    a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y; a.nan_flag = nan_flag;
+    a.T = T; a.Tpad = Tpad; a.C4p = d->cin / 4; a.Cout = d->cout; a.CoutPad = CoutPad;
+    a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
+    a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
+    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64; a.n_whole = a.n_mt;
+    const int grid = 8 * a.n_nt * ceil_div(a.n_mt, 8);
+    const bool res = d->flags & YOLO_FLAG_RESIDUAL;
+    const size_t lds = (size_t)W4S_SLOTS * W4S_STAGE + W4_TAB;       // (the epilogue's staging, 256 x 68 x 4, lies over the idle ring)
+    auto go = [&](auto kern) -> int {
+        static LdsOnce once;
+        if (int rc = reserve_lds(once, reinterpret_cast<const void*>(kern), lds, "conv_wino4s_f32")) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, q);
+        return check_launch("conv_wino4s_f32");
+    };
+    YOLO_SWITCH_ACT(d->act, return res ? go(&conv_wino4s_f32<ACT, true>) : go(&conv_wino4s_f32<ACT, false>));
+    return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: activation");
+}
+
+}  // namespace yolo

@@ -339,6 +339,17 @@ class PackedBlock:
         self.fold_stamp = fstamp if self.folded else None
 
 
+def _wino4_split_flag(state, d, tile_override):
+    """YOLO_FLAG_WINO_SPLIT_BF16 for a launch that runs as Winograd F(4x4) on finished filters: the 36 GEMMs on bf16 planes, on the
+    shapes that measured faster that way (the library's wino4_split_eligible keeps the list; ModelState.wino4_split = "all": wherever
+    the library honours the flag, False: nowhere). Never in latency mode or with a forced tile."""
+    if not state.wino4_split or state.latency or tile_override:
+        return 0
+    lib = L.lib()
+    ok = (lib.yolo_conv_wino4_split_supported if state.wino4_split == "all" else lib.yolo_conv_wino4_split_eligible)(C.byref(d))
+    return L.FLAG_WINO_SPLIT_BF16 if ok else 0
+
+
 def _kernel_variant(state, pk, d, op, tile_override):
     """(flags to add, w_packed) of one fp32 launch behind the stem in an eval plan: which of the library's kernel variants it runs,
     on which prepared weights. The first that applies wins, and the order matters: the library refuses the combinations (split-K
@@ -352,7 +363,7 @@ def _kernel_variant(state, pk, d, op, tile_override):
     # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
     if (wino_shape and (tile_override or 0) in (0, 15) and lib.yolo_conv_workspace_bytes(dp)
             and (d.tile == 15 or lib.yolo_conv_pick_tile(dp) == 15)):
-        return L.FLAG_FILTERS_READY, pk.want("u4", d).data_ptr()
+        return L.FLAG_FILTERS_READY | _wino4_split_flag(state, d, tile_override), pk.want("u4", d).data_ptr()
     # ... so do the small maps that measured faster as F(4x4) once nothing transforms their filters per launch: the library picks tile
     # 15 for them when the filters lie behind the packed weights, where the block keeps room (wino4_small = False keeps F(2x2))
     if state.wino4_small and not state.latency and not tile_override and wino_shape:
@@ -360,7 +371,7 @@ def _kernel_variant(state, pk, d, op, tile_override):
         probe.flags |= L.FLAG_FILTERS_APPENDED
         if (lib.yolo_conv_pick_tile(C.byref(probe)) == 15 and lib.yolo_conv_workspace_bytes(C.byref(probe)) > 0
                 and pk.want("u4a", d) is not None):
-            return L.FLAG_FILTERS_APPENDED, pk.w.data_ptr()
+            return L.FLAG_FILTERS_APPENDED | _wino4_split_flag(state, d, tile_override), pk.w.data_ptr()
     # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
     # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
     if state.split3 and not tile_override and (lib.yolo_conv_split3_supported if state.split3 == "all" else lib.yolo_conv_split3_eligible)(dp):
@@ -523,6 +534,11 @@ class ModelState:
         # on keep F(2x2) there (A/B runs; the rule cannot look at the batch, and a small batch fills fewer CUs with half
         # workgroups than with F(2x2) blocks: DESIGN 4.12).
         "wino4_small": (True, False),        # (an A/B setting: written only where it is not the default)
+        # fp32 inference: the Winograd F(4x4) launches on finished filters whose shape measured faster that way run their 36 GEMMs
+        # as three-way bf16 split products on planes that the transform pass writes (YOLO_FLAG_WINO_SPLIT_BF16: fp32 accuracy,
+        # other bits). False: plans made from then on keep the f32 GEMMs. "all": every launch the library honours the
+        # flag on, measured faster or not (A/B runs, tests).
+        "wino4_split": (True, False),        # (an A/B setting: written only where it is not the default)
     }
 
     def __init__(self, model=None):
@@ -685,7 +701,7 @@ class ModelState:
             stream = L.current_stream()
             dt = resolve_dtype(self.compute_dtype)
             latency = self.latency if dt == "fp32" and not self.tile_override else False
-            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt, self.split3, latency)
+            key = ("eval", B, (H, W), x.device.index, self.tile_override, dt, self.split3, latency, self.wino4_split)
             plan = self._plans.get(key)
             if plan is None:
                 prog = build_network_program(model, B, H, ch_align=8 if dt != "fp32" else 4, W=W)
