@@ -811,6 +811,79 @@ size_t yolo_anchor_fitness_workspace_bytes(int n, int k);
 int yolo_anchor_fitness(const float* wh, int n, const float* anchors, int k, float iou_threshold, double* mean_iou_and_recall,
                         int32_t* counts, int32_t* labels, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- multi-object tracking (csrc/track.hip; nothing of the reference) ---------------------------------------------------- */
+/* A ByteTrack-style tracker (Zhang et al.) for b independent streams: one call per frame carries every stream's tracks one frame on.
+ * This comment is the contract (DESIGN.md 7.23 has it step by step; tests/track_ref.py restates it in numpy). All fp32, every
+ * operation rounded once (written fl), no fused multiply-add, IEEE division. Comparisons of obj with a threshold are in double.
+ *
+ * State: one device buffer of yolo_track_state_bytes = b (4 + 26 max_tracks) 4 bytes (4-byte aligned) that the caller owns and only
+ * these calls write. Per stream 4 + 26 max_tracks 32-bit words: [frame, next_id, overflow, 0] (int32), then per slot 26 words:
+ *   0 state (int32: 0 Free, 1 Tentative, 2 Tracked, 3 Lost)   1 id (int32)   2 cls (float)   3 score (float)   4 lost_frames (int32)
+ *   5..12 mean = cx, cy, w, h, then their velocities   13..24 cov = (P00, P01, P11) of cx, of cy, of w, of h   25 zero
+ * yolo_track_reset zeroes the streams whose stream_mask byte is not 0 (NULL: all) and sets their next_id to 1. Every word of a Free
+ * slot is zero.
+ *
+ * Detections of stream s, from boxes (b, n, 6) fp32 rows [x, y, w, h, obj, cls]: with keep_idx (b, n) and keep_count (b) (the output
+ * of yolo_nms) the rows boxes[s][keep_idx[s][j]], j < keep_count[s], detection index j (an index outside [0, n) is no detection);
+ * with keep_count alone (the output of yolo_fuse_boxes) the first keep_count[s] rows; with neither every row. keep_count is clamped
+ * to [0, n]; keep_idx without keep_count is YOLO_ERR_ARG. A detection is HIGH iff (double) obj > high_threshold, LOW iff
+ * low_threshold < (double) obj <= high_threshold (NaN fails both). Its measurement is z = (cx, cy, w, h): center != 0: cx = x,
+ * cy = y; else cx = fl(x + fl(w / 2)), cy = fl(y + fl(h / 2)). Its corners and area are the NMS's (as for yolo_fuse_boxes).
+ *
+ * A slot's filter is four independent constant-velocity filters, one per coordinate c of (cx, cy, w, h), with mean (p, v) and
+ * covariance (P00, P01, P11): the block structure of the usual 8-state filter with diagonal noise. wp = 0.05f, wv = 0.00625f;
+ * s_c = the slot's w for cx and w, its h for cy and h, read before the step changes them.
+ * Predict: a Lost slot first sets the velocities of w and h to 0. q_p = fl(fl(wp s_c) fl(wp s_c)), q_v likewise with wv;
+ *   p = fl(p + v); P00 = fl(fl(fl(P00 + fl(2 P01)) + P11) + q_p); P01 = fl(P01 + P11); P11 = fl(P11 + q_v) (old P01, P11 on the right).
+ * Update with z_c (s_c from the predicted mean): r = fl(fl(wp s_c) fl(wp s_c)); S = fl(P00 + r); K0 = fl(P00 / S); K1 = fl(P01 / S);
+ *   y = fl(z_c - p); p = fl(p + fl(K0 y)); v = fl(v + fl(K1 y)); from the old P00, P01: P00' = fl(P00 - fl(K0 P00)),
+ *   P01' = fl(P01 - fl(K0 P01)), P11' = fl(P11 - fl(K1 P01)).
+ * Found from z (s_c from z): p = z_c, v = 0, P00 = fl(t t) with t = fl(fl(2 wp) s_c), P01 = 0, P11 = fl(u u) with u = fl(fl(10 wv) s_c).
+ *
+ * IoU of a slot's predicted box against a detection, the NMS's expression: the slot's x1 = fl(cx - fl(w / 2)), y1 likewise,
+ * x2 = fl(x1 + w), y2 = fl(y1 + h), ak = fl(w h); inter = max(min(x2, X2) - max(x1, X1), 0) max(min(y2, Y2) - max(y1, Y1), 0),
+ * iou = inter / (((a + ak) - inter) + 1e-6f). A pair is eligible at threshold m iff iou > (float) m and (class_agnostic != 0 or the
+ * slot's cls == the detection's cls, float equality). The matching of a slot set against a detection set is the greedy one: walk
+ * the eligible pairs in the order (iou descending, slot index ascending, detection index ascending) and take a pair iff neither
+ * side is taken yet.
+ *
+ * One call, per stream: 1. predict every slot that is not Free. 2. Match the Tracked and Lost slots against the HIGH detections at
+ * match_iou[0]. 3. Match the Tracked (not Lost) slots still unmatched against the LOW detections at match_iou[1]. 4. Match the
+ * Tentative slots against the HIGH detections still unmatched at match_iou[2]; an unmatched Tentative slot becomes Free. 5. An
+ * unmatched Tracked or Lost slot becomes Lost with lost_frames += 1, and Free if then lost_frames > max_age. 6. Every matched slot is
+ * updated with its detection and becomes Tracked, score = the detection's obj, lost_frames = 0. 7. Every HIGH detection still
+ * unmatched with (double) obj > new_threshold founds a track, in ascending detection index, in the lowest Free slot (those freed in
+ * 4 and 5 included): id = next_id++ (ids start at 1 per stream), cls and score the detection's, Tracked if frame == 0 else
+ * Tentative; without a Free slot the detection is dropped and overflow += 1. 8. frame += 1.
+ *
+ * Outputs, fully written by the call: out_boxes (b, max_tracks, 6), out_ids (b, max_tracks), out_count (b): the slots that are
+ * Tracked and were matched or founded in this call, in ascending id, as rows [x, y, w, h, score, cls] from the updated mean
+ * (center != 0: x = cx, y = cy; else x = fl(cx - fl(w / 2)), y = fl(cy - fl(h / 2))); zero behind out_count. det_ids (b, n), per
+ * input row: the id of the track it updated or founded, negated if that track is Tentative after the call; 0 for none and for a
+ * row that is no detection.
+ *
+ * Limits: 1 <= max_tracks <= 512, 1 <= b <= 2047, 0 <= n <= 163,456, else YOLO_ERR_UNSUPPORTED and nothing is launched. A null
+ * pointer (boxes may be NULL for n == 0; keep_idx, keep_count as above), a NaN threshold, a match_iou outside [0, 1] or max_age < 0:
+ * YOLO_ERR_ARG. Workspace: 4-byte aligned, yolo_track_workspace_bytes = 8 b n bytes (two int32 per detection index; 0, and then
+ * it may be NULL, for n == 0; 0 outside the limits), else YOLO_ERR_WORKSPACE; every byte that is read was written by the call.
+ * Both size functions are HOST ONLY. One workgroup per stream; one launch; stream-ordered, nothing is read back, so the call can
+ * be captured in a graph. Outside the bit contract, but terminating and in bounds: non-finite coordinates, an index that occurs
+ * twice in keep_idx. */
+typedef struct {
+    double high_threshold, low_threshold, new_threshold;
+    double match_iou[3];     /* steps 2, 3, 4 */
+    int32_t max_age;
+    int32_t center;          /* box format of boxes and out_boxes: != 0 centre, 0 corner */
+    int32_t class_agnostic;
+    int32_t reserved;        /* 0 */
+} yolo_track_params;         /* 64 bytes */
+size_t yolo_track_state_bytes(int b, int max_tracks);
+size_t yolo_track_workspace_bytes(int b, int n, int max_tracks);
+int yolo_track_reset(void* state, int b, int max_tracks, const uint8_t* stream_mask_dev, void* stream);
+int yolo_track_update(void* state, int b, int max_tracks, const float* boxes, int n, const int32_t* keep_idx, const int32_t* keep_count,
+                      const yolo_track_params* p, float* out_boxes, int32_t* out_ids, int32_t* out_count, int32_t* det_ids,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,384 @@
+"""yolo_track_update / Tracker on the GPU, bit for bit against the numpy restatement of its contract (tests/track_ref.py): every
+frame of every case compares out_boxes, out_ids, out_count, det_ids and every field of the state; the output buffers are pre-filled
+with 0xA5 and have guard bytes behind them, and so have the state and the workspace."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import track_ref as R
+
+pytestmark = pytest.mark.gpu
+SPARE = 4096            # guard bytes behind every buffer
+F32 = np.float32
+FIELDS = ("frame", "next_id", "overflow", "state", "id", "cls", "score", "lost_frames", "mean", "cov")
+
+
+@pytest.fixture(scope="module")
+def L():
+    import yolo_for_turbines_amd  # noqa: F401
+    from yolo_for_turbines_amd import _lib
+    _lib.lib()                       # must load: no fallback
+    assert torch.cuda.is_available()
+    return _lib
+
+
+@pytest.fixture(scope="module")
+def yt():
+    import yolo_for_turbines_amd
+    return yolo_for_turbines_amd
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int32) if a.dtype == F32 else a
+
+
+def filled(nbytes, value=0xA5):
+    return torch.full((nbytes + SPARE,), value, dtype=torch.uint8, device="cuda")
+
+
+def decode_state(words, B, M):
+    """The header's state layout: (B, 4 + 26 M) int32 -> the fields of TrackerRef.slots()."""
+    words = np.ascontiguousarray(words, np.int32).reshape(B, R.HDR_WORDS + R.SLOT_WORDS * M)
+    assert not words[:, 3].any()
+    sl = words[:, R.HDR_WORDS:].reshape(B, M, R.SLOT_WORDS)
+    assert not sl[..., 25].any()
+    f = sl.view(F32)
+    return dict(frame=words[:, 0], next_id=words[:, 1], overflow=words[:, 2], state=sl[..., 0], id=sl[..., 1], cls=f[..., 2],
+                score=f[..., 3], lost_frames=sl[..., 4], mean=f[..., 5:13], cov=f[..., 13:25])
+
+
+def same(got, want, what):
+    for name, g, w in zip(("out_boxes", "out_ids", "out_count", "det_ids"), got[:4], want[:4]):
+        np.testing.assert_array_equal(bits(g), bits(w), err_msg=f"{what}: {name}")
+    for name in FIELDS:
+        np.testing.assert_array_equal(bits(got[4][name]), bits(want[4][name]), err_msg=f"{what}: slots()[{name!r}]")
+
+
+class Driver:
+    """A tracker through the C ABI, with guarded buffers, beside its reference: step() runs a frame on both and compares."""
+
+    def __init__(self, L, B, M, **kw):
+        self.L, self.lib, self.B, self.M = L, L.lib(), B, M
+        self.ref = R.TrackerRef(B, M, **kw)
+        r = self.ref
+        self.params = L.TrackParams(r.high, r.low, r.new, (C.c_double * 3)(*r.match_iou), r.max_age, int(r.center), int(r.agnostic), 0)
+        self.state_bytes = self.lib.yolo_track_state_bytes(B, M)
+        assert self.state_bytes == 4 * B * (R.HDR_WORDS + R.SLOT_WORDS * M)
+        self.state = filled(self.state_bytes, 0x5A)
+        self.stream = torch.cuda.current_stream().cuda_stream
+        L.check(self.lib.yolo_track_reset(self.state.data_ptr(), B, M, None, self.stream), "yolo_track_reset")
+
+    def slots(self):
+        host = self.state.cpu().numpy()
+        assert (host[self.state_bytes:] == 0x5A).all(), "wrote behind the state"
+        return decode_state(host[:self.state_bytes].view(np.int32), self.B, self.M)
+
+    def step(self, boxes, keep=None, count=None, what=""):
+        boxes = np.ascontiguousarray(boxes, F32)
+        B, N, _ = boxes.shape
+        M = self.M
+        d_boxes = torch.from_numpy(boxes).cuda()
+        d_keep = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, np.int32)).cuda()
+        d_count = None if count is None else torch.from_numpy(np.ascontiguousarray(count, np.int32)).cuda()
+        sizes = [B * M * 24, B * M * 4, B * 4, B * N * 4]
+        bufs = [filled(s) for s in sizes]
+        nbytes = self.lib.yolo_track_workspace_bytes(B, N, M)
+        assert nbytes == 8 * B * N
+        ws = filled(nbytes, 0x5A)
+        rc = self.lib.yolo_track_update(self.state.data_ptr(), B, M, d_boxes.data_ptr(), N, self.L.ptr(d_keep), self.L.ptr(d_count),
+                                        C.byref(self.params), *[b.data_ptr() for b in bufs], ws.data_ptr(), nbytes, self.stream)
+        self.L.check(rc, "yolo_track_update")
+        torch.cuda.synchronize()
+        host = [b.cpu().numpy() for b in bufs + [ws]]
+        for h, s in zip(host, sizes + [nbytes]):
+            assert (h[s:] == h[-1]).all() and h[-1] in (0xA5, 0x5A), "wrote behind a buffer"
+        got = (host[0][:sizes[0]].view(F32).reshape(B, M, 6), host[1][:sizes[1]].view(np.int32).reshape(B, M),
+               host[2][:sizes[2]].view(np.int32), host[3][:sizes[3]].view(np.int32).reshape(B, N), self.slots())
+        want = self.ref.update(boxes, keep, count) + (self.ref.slots(),)
+        same(got, want, what)
+        return want
+
+
+def crowd_frames(B, N, M, frames, seed, low_share=0.2, objects=None):
+    """Per frame (boxes (B, N, 6), count (B)): stream s has its own crowd of `objects` objects, by default about 1.2 M (fewer in
+    later streams, never more than N rows), so the table fills up and the counts differ per stream."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for t in range(frames):
+        boxes, count = np.zeros((B, N, 6), F32), np.zeros(B, np.int32)
+        for s in range(B):
+            k = max(1, min(objects or int(1.2 * M) + 2, N + 3) - 2 * s)
+            boxes[s], count[s] = R.crowd(rng, k, N, t + 3 * s, low_share=low_share)
+        out.append((boxes, count))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ geometry
+@pytest.mark.parametrize("M,N,B", [(1, 1, 1), (4, 0, 3), (4, 63, 1), (64, 64, 3), (65, 65, 3), (128, 257, 3), (128, 65, 33), (512, 257, 1),
+                                   (64, 1025, 3), (512, 1025, 1), (512, 64, 3), (1, 65, 33)])
+def test_geometry_edges(L, M, N, B):
+    """The slots against the threads of a wave and of the workgroup, the detections against one and several strides of the
+    workgroup, several streams with different detection counts, 12 frames. The crowds are dense: tables overflow, tracks get lost,
+    come back and die."""
+    d = Driver(L, B, M, max_age=3)
+    listed = 0
+    objects = N if (M, N) == (64, 1025) else None             # there: more detections than two strides of the workgroup
+    for t, (boxes, count) in enumerate(crowd_frames(B, N, M, 12, seed=M * 7 + N, objects=objects)):
+        want = d.step(boxes, None, count, what=f"frame {t}")
+        listed += int(want[2].sum())
+    if N:
+        assert listed > 0
+        assert len(set(count.tolist())) > 1 or B == 1 or N < 3
+    else:
+        assert listed == 0 and (d.ref.frame == 12).all()
+    if N > M + 8:
+        assert d.ref.overflow.sum() > 0
+
+
+@pytest.mark.parametrize("mode", ["keep+count", "count", "all"])
+@pytest.mark.parametrize("fmt", ["center", "corners"])
+@pytest.mark.parametrize("agnostic", [False, True])
+def test_input_modes_formats_and_classes(L, mode, fmt, agnostic):
+    B, N, M = 2, 96, 64
+    d = Driver(L, B, M, box_format=fmt, class_agnostic=agnostic, max_age=2)
+    rng = np.random.default_rng(5)
+    for t, (boxes, count) in enumerate(crowd_frames(B, N, M, 8, seed=11, low_share=0.3)):
+        if t % 3 == 2:
+            boxes[:, ::2, 5] = (boxes[:, ::2, 5] + 1) % 3               # classes flicker: only the class-agnostic tracker follows
+        if fmt == "corners":
+            boxes = R.to_corner(boxes)
+        if mode == "keep+count":
+            keep = np.stack([rng.permutation(N) for _ in range(B)]).astype(np.int32)      # a permutation: rows in any order
+            kc = np.array([N - 7, N // 2], np.int32)                                     # ... and only some of them
+            d.step(boxes, keep, kc, what=f"frame {t}")
+        elif mode == "count":
+            d.step(boxes, None, count, what=f"frame {t}")
+        else:
+            d.step(boxes, what=f"frame {t}")                            # zero rows are below every threshold
+    assert d.ref.next_id.min() > 10 and (d.ref.state == R.LOST).any()
+
+
+def test_keep_entries_outside_the_rows_are_no_detections(L):
+    d = Driver(L, 1, 8, new_threshold=0.5)
+    boxes, _ = R.crowd(np.random.default_rng(0), 6, 6, 0, low_share=0.0, dropout=0.0)
+    keep = np.array([[3, -1, 6, 0, 2, 1 << 30]], np.int32)
+    for t in range(3):
+        want = d.step(boxes[None], keep, np.array([6], np.int32), what=f"frame {t}")
+    assert want[2][0] == 3 and want[3][0].tolist().count(0) == 3
+    want = d.step(boxes[None], keep, np.array([99], np.int32))          # a count above n is clamped
+    assert want[2][0] == 3
+    want = d.step(boxes[None], keep, np.array([-5], np.int32))          # ... and one below 0
+    assert want[2][0] == 0
+
+
+# ------------------------------------------------------------------------------------------ ties
+def test_identical_boxes_and_scores(L):
+    """Eight identical rows per object: every IoU of a row against its object's track ties, the lowest detection index wins, the
+    others found tracks that tie again in the next frame."""
+    rng = np.random.default_rng(2)
+    base, _ = R.crowd(rng, 5, 5, 0, low_share=0.0, dropout=0.0)
+    base[:, 4] = 0.75
+    rows = np.repeat(base, 8, axis=0)
+    d = Driver(L, 2, 64)
+    for t in range(5):
+        boxes = np.stack([rows, rows[::-1]])
+        want = d.step(boxes, what=f"frame {t}")
+    assert want[2].tolist() == [40, 40]
+    d = Driver(L, 1, 64, class_agnostic=True)
+    for t in range(4):
+        d.step(rows[None], what=f"agnostic frame {t}")
+
+
+def test_scores_exactly_at_the_thresholds(L):
+    """high = 0.5, low = 0.125, new = 0.75 (exact in fp32): a score equal to a threshold is not above it."""
+    kw = dict(high_threshold=0.5, low_threshold=0.125, new_threshold=0.75)
+    pos = np.array([[0.1 + 0.2 * i, 0.5] for i in range(4)])
+    size = np.full((4, 2), 0.1)
+    rng = np.random.default_rng(0)
+    d = Driver(L, 1, 8, **kw)
+    first = R.scene_frame(rng, pos, size, 0, [0.9, 0.75, 0.9, 0.9], pos_noise=0, size_noise=0)
+    want = d.step(first[None])
+    assert want[3][0].tolist() == [1, 0, 2, 3]                          # 0.75 == new founds nothing
+    second = R.scene_frame(rng, pos, size, 0, [0.5, 0.9, 0.125, 0.5000001], pos_noise=0, size_noise=0)
+    want = d.step(second[None])
+    # 0.5 == high is a low detection (matched in step 3); 0.125 == low is no detection; the next float above 0.5 is high
+    assert want[3][0].tolist() == [1, -4, 0, 3]
+    assert d.ref.state[0, :4].tolist() == [R.TRACKED, R.LOST, R.TRACKED, R.TENTATIVE]
+
+
+def test_iou_exactly_at_match_iou(L):
+    """A track on the unit square and a detection on its left 5/8: with match_iou[0] at the reference's own fp32 IoU the pair is
+    not eligible; one ulp below, it is."""
+    one = F32(1)
+    iou = (F32(0.625) * one) / (((F32(0.625) + one) - F32(0.625)) + F32(1e-6))
+    first = np.array([[[0.5, 0.5, 1.0, 1.0, 0.9, 0.0]]], F32)
+    second = np.array([[[0.3125, 0.5, 0.625, 1.0, 0.9, 0.0]]], F32)
+    assert R.iou_matrix(R.kf_found(first[0, :, :4])[0], second[0], True)[0, 0] == iou
+    outcomes = []
+    for thr in (float(iou), float(np.nextafter(iou, F32(0)))):
+        d = Driver(L, 1, 4, match_iou=(thr, 0.5, 0.3))
+        d.step(first)
+        outcomes.append(d.step(second)[3][0, 0])
+    assert outcomes == [-2, 1]
+
+
+# ------------------------------------------------------------------------------------------ the table
+def test_full_table_founds_in_the_call_that_frees(L):
+    """Four slots, max_age 0: in frame 1 two tracks are unmatched, die and free their slots, three new objects appear: two found
+    tracks in the freed slots in this very call, the third is dropped."""
+    rng = np.random.default_rng(1)
+    pos = np.array([[0.1 + 0.1 * i, 0.2 + 0.1 * (i % 2)] for i in range(7)])
+    size = np.full((7, 2), 0.05)
+    rows = R.scene_frame(rng, pos, size, np.arange(7) % 2, 0.9, pos_noise=0, size_noise=0)
+    d = Driver(L, 1, 4, max_age=0)
+    d.step(rows[None, :4])
+    want = d.step(rows[None, [0, 4, 2, 5, 6]])
+    assert want[3][0].tolist() == [1, -5, 3, -6, 0] and d.ref.overflow[0] == 1
+    assert d.ref.id[0].tolist() == [1, 5, 3, 6]
+    d.step(rows[None, [6, 5, 4]])                                          # everything confirmed dies, the tentative ones go on
+    assert sorted(d.ref.id[0].tolist()) == [0, 5, 6, 7]
+
+
+def test_frames_without_detections_and_all_slots_lost(L):
+    frames = crowd_frames(2, 40, 32, 3, seed=3)
+    d = Driver(L, 2, 32, max_age=4)
+    for boxes, count in frames:
+        d.step(boxes, None, count)
+    assert (d.ref.state == R.TRACKED).sum() > 20
+    want = d.step(np.zeros((2, 0, 6), F32), what="n = 0")                  # no rows at all
+    assert want[2].tolist() == [0, 0] and not (d.ref.state == R.TRACKED).any() and (d.ref.state == R.LOST).sum() > 20
+    d.step(frames[0][0], None, np.zeros(2, np.int32), what="count = 0")    # rows, none of them a detection
+    boxes, count = frames[1]
+    boxes = boxes.copy()
+    boxes[..., 4] = np.where(boxes[..., 4] > 0, 0.3, 0)                    # only low detections: a Lost track takes none
+    want = d.step(boxes, None, count, what="every slot Lost, low detections")
+    assert want[2].tolist() == [0, 0] and not want[3].any() and (d.ref.state == R.LOST).sum() > 20
+    d.step(frames[2][0], None, frames[2][1], what="lost tracks come back")
+    assert (d.ref.state == R.TRACKED).sum() > 20
+    for _ in range(5):
+        d.step(np.zeros((2, 5, 6), F32))
+    assert not d.ref.state.any() and not d.ref.mean.any()                  # all dead: the table is zero again
+
+
+# ------------------------------------------------------------------------------------------ the Python class
+def py_slots(tracker):
+    return {k: v.cpu().numpy() for k, v in tracker.slots().items()}
+
+
+def py_same(res, tracker, want, ref, what):
+    got = tuple(t.cpu().numpy() for t in res) + (py_slots(tracker),)
+    same(got, want + (ref.slots(),), what)
+
+
+def test_tracker_class_and_reset_of_one_stream(yt):
+    kw = dict(max_tracks=32, max_age=4, match_iou=(0.25, 0.5, 0.3))
+    t, ref = yt.Tracker(3, **kw), R.TrackerRef(3, **kw)
+    frames = crowd_frames(3, 48, 32, 6, seed=9)
+    for i, (boxes, count) in enumerate(frames[:3]):
+        res = t.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+        assert isinstance(res, yt.TrackResult) and res.boxes.shape == (3, 32, 6) and res.det_ids.shape == (3, 48)
+        py_same(res, t, ref.update(boxes, None, count), ref, f"frame {i}")
+    before = py_slots(t)
+    t.reset([1])
+    ref.reset([1])
+    after = py_slots(t)
+    for name in FIELDS:
+        np.testing.assert_array_equal(bits(after[name][[0, 2]]), bits(before[name][[0, 2]]), err_msg=name)
+        assert not after[name][1].any() or name == "next_id"
+    assert after["next_id"][1] == 1 and before["next_id"][1] > 1
+    for i, (boxes, count) in enumerate(frames[3:]):
+        res = t.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+        py_same(res, t, ref.update(boxes, None, count), ref, f"frame {3 + i}")
+    t.reset()
+    assert not py_slots(t)["state"].any() and py_slots(t)["next_id"].tolist() == [1, 1, 1]
+
+
+def test_update_with_the_output_of_nms_and_of_fusion(yt):
+    """keep and count as nms_indices returns them, count as fuse_boxes returns it."""
+    boxes, _ = crowd_frames(2, 80, 64, 1, seed=4)[0]
+    d_boxes = torch.from_numpy(boxes).cuda()
+    keep, count = yt.nms_indices(d_boxes, 0.45, 0.1, "center")
+    t, ref = yt.Tracker(2, max_tracks=64), R.TrackerRef(2, 64)
+    for i in range(2):
+        res = t.update(d_boxes, keep, count)
+        py_same(res, t, ref.update(boxes, keep.cpu().numpy(), count.cpu().numpy()), ref, f"nms frame {i}")
+    assert int(res.count.sum()) > 20
+    fused, fcount, _ = yt.fuse_boxes(d_boxes, 0.55, 0.1)
+    for i in range(2):
+        res = t.update(fused, count=fcount)
+        py_same(res, t, ref.update(fused.cpu().numpy(), None, fcount.cpu().numpy()), ref, f"fused frame {i}")
+
+
+def test_update_in_a_graph_replays_the_bits_of_eager_calls(yt):
+    """update captured once with static input buffers and replayed for 8 frames against 8 eager calls of a second tracker: the
+    capture also shows that the call never waits for the device."""
+    B, N, M = 3, 70, 64
+    frames = crowd_frames(B, N, M, 8, seed=6)
+    graphed, eager = yt.Tracker(B, max_tracks=M, max_age=2), yt.Tracker(B, max_tracks=M, max_age=2)
+    s_boxes = torch.zeros((B, N, 6), device="cuda")
+    s_count = torch.zeros(B, dtype=torch.int32, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        graphed.update(s_boxes, count=s_count)                               # warm-up: the buffers exist before the capture
+    torch.cuda.current_stream().wait_stream(side)
+    graphed.reset()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        res = graphed.update(s_boxes, count=s_count)
+    assert int(graphed.slots()["frame"].sum()) == 0                          # the capture ran nothing
+    for i, (boxes, count) in enumerate(frames):
+        s_boxes.copy_(torch.from_numpy(boxes))
+        s_count.copy_(torch.from_numpy(count))
+        g.replay()
+        want = eager.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+        got = tuple(t.cpu().numpy() for t in res) + (py_slots(graphed),)
+        same(got, tuple(t.cpu().numpy() for t in want) + (py_slots(eager),), f"replay {i}")
+    assert int(res.count.sum()) > 0 and graphed.slots()["frame"].tolist() == [8] * B
+
+
+def test_state_dict_resumes_bit_identically(yt):
+    kw = dict(max_tracks=32, max_age=3, high_threshold=0.55, class_agnostic=True)
+    frames = crowd_frames(2, 50, 32, 10, seed=8)
+    a = yt.Tracker(2, **kw)
+    for boxes, count in frames[:5]:
+        a.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+    sd = a.state_dict()
+    assert int(sd["state"][:, 0].min()) == 5
+    b = yt.Tracker(2, max_tracks=32)                                         # other parameters: they come with the state
+    b.load_state_dict(sd)
+    assert (b.max_age, b.high_threshold, b.class_agnostic) == (3, 0.55, True)
+    for i, (boxes, count) in enumerate(frames[5:]):
+        ra = a.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+        rb = b.update(torch.from_numpy(boxes).cuda(), count=torch.from_numpy(count).cuda())
+        same(tuple(t.cpu().numpy() for t in rb) + (py_slots(b),), tuple(t.cpu().numpy() for t in ra) + (py_slots(a),), f"frame {5 + i}")
+    assert int(sd["state"][:, 0].max()) == 5                                 # the saved copy did not move
+    with pytest.raises(ValueError):
+        yt.Tracker(2, max_tracks=16).load_state_dict(sd)
+
+
+def test_track_images_is_detect_images_then_update(yt):
+    from oracle import net as onet
+    from tests import golden_inputs as gi
+    m = yt.YOLOv3(num_classes=80)
+    m.load_state_dict(onet.synth_state_dict(11, 3, 80, gain=gi.NET_GAIN))
+    m = m.cuda().eval()
+    anchors = [a.cuda() for a in yt.scaled_anchors(gi.COCO_ANCHORS, 96, 96)]
+    xs = [onet.synth_input(seed, 2, 96).cuda() for seed in (1, 2, 2)]
+    scores = np.unique(yt.detect_images(m, xs[0], anchors, 0.45, 0.0)[0][..., 4].cpu().numpy().astype(np.float64))
+    q = scores[int(0.9 * len(scores))]
+    high = float((q + scores[scores > q][0]) / 2)                             # between two scores: no score at a threshold
+    kw = dict(max_tracks=128, high_threshold=high, low_threshold=high / 2, new_threshold=high)
+    a, b = yt.Tracker(2, **kw), yt.Tracker(2, **kw)
+    for i, x in enumerate(xs):
+        res, boxes, keep, count = yt.track_images(m, x, anchors, a, iou_threshold=0.45)
+        wb, wk, wc = yt.detect_images(m, x, anchors, 0.45, high / 2)
+        want = b.update(wb, wk, wc)
+        assert torch.equal(boxes, wb) and torch.equal(count, wc) and int(count.min()) > 0
+        assert all(torch.equal(keep[s, :int(count[s])], wk[s, :int(count[s])]) for s in range(2))
+        same(tuple(t.cpu().numpy() for t in res) + (py_slots(a),), tuple(t.cpu().numpy() for t in want) + (py_slots(b),), f"frame {i}")
+        listed = int(res.count.sum()) if i == 0 else listed
+    assert listed > 0                                                        # frame 0 founds confirmed tracks

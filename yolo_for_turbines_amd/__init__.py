@@ -14,7 +14,9 @@ from .model import CNNBlock, ResidualBlock, ScalePredictionBlock, YOLOv3, layer_
 from .utils import (save_checkpoint, load_checkpoint, accuracy_counts, build_targets, calc_iou, calc_mAP, evaluate_detections, evaluate_model, check_model_accuracy, eval_boxes, get_eval_boxes, letterbox, unletterbox_boxes, augment_params, augment_batch, train_batch, scaled_anchors, anchor_draws, kmeans_anchors, anchor_fitness, anchors_layout, cells_to_boxes, decode_boxes, detect, detect_images, detect_tiled, tile_grid, tile_pyramid, iou_aligned, nms_indices,
                     fuse_boxes, tta_views, tta_boxes, detect_tta,
                     non_max_suppression)
+from .track import Tracker, TrackResult, track_images
 
 __all__ = ["YOLOLoss", "FusedYOLOLoss", "GraphedTrainStep", "SGD", "Adam", "AdamW", "clip_grad_norm_", "GradScaler", "ModelEMA", "CNNBlock", "ResidualBlock", "ScalePredictionBlock", "YOLOv3", "layer_config", "calc_iou",
            "cells_to_boxes", "decode_boxes", "detect", "detect_images", "detect_tiled", "fuse_boxes", "tta_views", "tta_boxes", "detect_tta", "tile_grid", "tile_pyramid", "iou_aligned", "nms_indices", "non_max_suppression", "build_targets", "calc_mAP", "evaluate_detections", "evaluate_model", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes", "augment_params",
-           "augment_batch", "train_batch", "scaled_anchors", "anchor_draws", "kmeans_anchors", "anchor_fitness", "anchors_layout"]
+           "augment_batch", "train_batch", "scaled_anchors", "anchor_draws", "kmeans_anchors", "anchor_fitness", "anchors_layout",
+           "Tracker", "TrackResult", "track_images"]

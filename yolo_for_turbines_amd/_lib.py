@@ -51,6 +51,12 @@ class ClipState(C.Structure):
     _fields_ = [("max_norm", C.c_float), ("total_norm", C.c_float), ("coef", C.c_float), ("norm_type", C.c_int32)]
 
 
+class TrackParams(C.Structure):
+    """`yolo_track_params` (include/yolo_mi355x.h): the thresholds and switches of yolo_track_update, 64 bytes."""
+    _fields_ = [("high_threshold", C.c_double), ("low_threshold", C.c_double), ("new_threshold", C.c_double), ("match_iou", C.c_double * 3),
+                ("max_age", C.c_int32), ("center", C.c_int32), ("class_agnostic", C.c_int32), ("reserved", C.c_int32)]
+
+
 NORM_KINDS = {2.0: 0, float("inf"): 1}                                 # YOLO_NORM_L2 / YOLO_NORM_INF of the header
 
 CALL_MAX_ARGS = 24
@@ -231,6 +237,11 @@ _SIGS = {
     "yolo_fuse_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_fuse_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_track_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "yolo_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "yolo_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "yolo_track_update": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackParams),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_tta_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_boxes_unflip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_tile_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
