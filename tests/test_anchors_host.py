@@ -139,7 +139,7 @@ def test_anchor_draws(built):
 
 
 def test_filter_drops_exactly_the_invalid_rows(built):
-    from yolo_for_turbines_amd import utils
+    from yolo_for_turbines_amd import boxes as utils
     nan = float("nan")
     rows = [[0.5, 0.5, 0.2, 0.3, 1], [0.5, 0.5, 0.0, 0.3, 0], [0.5, 0.5, 0.2, -0.1, 0], [0.5, 0.5, 1.0, 1.0, 2], [0.5, 0.5, 1.0000001, 0.5, 2],
             [0.5, 0.5, nan, 0.5, 0], [0.5, 0.5, 0.5, nan, 0], [0.1, 0.1, 1e-6, 0.999, 0], [9.0, -3.0, 0.4, 0.4, 0], [0.5, 0.5, 0.3, 1.5, 0]]

@@ -1134,7 +1134,7 @@ def test_sort_u64_and_stable_two_level_order(yt, n):
     two-level stable order calc_mAP builds on it against Python's own two stable list sorts (utils.py:206,232) with many ties,
     negative zeros and negative scores."""
     from yolo_for_turbines_amd import _lib as L
-    from yolo_for_turbines_amd.utils import _stable_order
+    from yolo_for_turbines_amd.metrics import _stable_order
     g = torch.Generator().manual_seed(n)
     keys = (torch.randint(0, 2 ** 62, (n,), generator=g, dtype=torch.int64) & ~0xfffff) | torch.arange(n, dtype=torch.int64)
     kd = keys.cuda()

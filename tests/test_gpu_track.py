@@ -382,3 +382,27 @@ def test_track_images_is_detect_images_then_update(yt):
         same(tuple(t.cpu().numpy() for t in res) + (py_slots(a),), tuple(t.cpu().numpy() for t in want) + (py_slots(b),), f"frame {i}")
         listed = int(res.count.sum()) if i == 0 else listed
     assert listed > 0                                                        # frame 0 founds confirmed tracks
+
+
+def test_track_images_nan_frame_raises_and_leaves_the_engine_usable(yt):
+    """track_images reads the forward's NaN guard after detection and update are enqueued: a frame with one NaN pixel raises the
+    forward's AssertionError (model.py:175), the engine guards every forward by itself again afterwards, and the next clean frame
+    gives what detect_images gives at the tracker's low threshold, bit for bit."""
+    from oracle import net as onet
+    from tests import golden_inputs as gi
+    m = yt.YOLOv3(num_classes=80)
+    m.load_state_dict(onet.synth_state_dict(11, 3, 80, gain=gi.NET_GAIN))
+    m = m.cuda().eval()
+    anchors = [a.cuda() for a in yt.scaled_anchors(gi.COCO_ANCHORS, 96, 96)]
+    x = onet.synth_input(1, 2, 96).cuda()
+    tracker = yt.Tracker(2, max_tracks=128, high_threshold=0.5, low_threshold=0.1, new_threshold=0.6)
+    xn = x.clone()
+    xn[1, 0, 5, 5] = float("nan")
+    with pytest.raises(AssertionError, match="NaN in the input tensor"):
+        yt.track_images(m, xn, anchors, tracker, iou_threshold=0.45)
+    assert m._engine._defer_nan is False and m._engine._pending_flag is None
+    res, boxes, keep, count = yt.track_images(m, x, anchors, tracker, iou_threshold=0.45)
+    wb, wk, wc = yt.detect_images(m, x, anchors, 0.45, tracker.low_threshold)
+    assert torch.equal(boxes, wb) and torch.equal(count, wc)
+    assert all(torch.equal(keep[s, :int(count[s])], wk[s, :int(count[s])]) for s in range(2))      # (the rows behind count are not written)
+    assert m._engine._defer_nan is False and m._engine._pending_flag is None

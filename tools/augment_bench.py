@@ -59,7 +59,7 @@ def main():
             pd = p.cuda()
             name = f"{'mosaic' if mosaic else 'standard'} {w}x{h} -> {S}x{S}"
             # kernels only: tables and images on the device, REP launches back to back between two events
-            _, _, _, launch = yt.utils._augment_prepare(dev_imgs, boxes, S, pd, None, mo, None)
+            _, _, _, launch = yt.data._augment_prepare(dev_imgs, boxes, S, pd, None, mo, None)
             med, best = _events(lambda: [launch() for _ in range(REP)], a.iters)
             med, best = med / REP, best / REP
             lines.append({"case": name + " (kernels)", "batch": B, "ms_median": round(med, 4), "ms_min": round(best, 4),

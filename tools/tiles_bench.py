@@ -12,7 +12,7 @@ Per (dtype, frames):
   * one round of ``detect_tiled`` on frames in pageable host memory (adds the pinned staging copy and the upload).
   * each stage alone, HIP events around --reps back-to-back launches on one full chunk: gather, forward, decode, collect, and the one NMS
     over (frames, max_candidates, 6). ``exposed`` is what the stages do not account for: (call - sum of the stages) per chunk, i.e. host
-    time and idle gaps that the device sees.
+    time and idle gaps that the device sees. (``decode`` now marshals its arguments on every launch: not comparable with older records.)
 With --scales (more than the native level) or --edge-margin, per (dtype, frames) in addition:
   * ``yolo_tile_gather_scaled`` on one chunk of tiles of every level that is not the frame itself, beside the plain gather (the
     origins of the level's grid, repeated when the level has fewer tiles than a chunk);
@@ -21,7 +21,6 @@ With --scales (more than the native level) or --edge-margin, per (dtype, frames)
 The objectness threshold is taken from the model's own scores on the first chunk (--pass-rate of the rows pass), since synthetic
 weights have no meaningful 0.5."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -143,19 +142,11 @@ def main():
 
             # ---- the stages, on one full chunk
             x = pre[:B].contiguous()
-            eng._defer_nan = True
-            try:
-                with torch.no_grad():
-                    preds = m(x)
-                    fwd = event_ms(lambda: m(x), a.reps, torch)
-            finally:
-                eng._defer_nan, eng._pending_flag = False, None
+            with eng.deferred_nan(), torch.no_grad():
+                preds = m(x)
+                fwd = event_ms(lambda: m(x), a.reps, torch)
             n_per = sum(3 * p.shape[2] * p.shape[3] for p in preds)
             boxes = torch.empty((B, n_per, 6), dtype=torch.float32, device=dev)
-            pp = (C.c_void_p * 3)(*[p.data_ptr() for p in preds])
-            st = (C.c_int64 * 15)(*[v for p in preds for v in p.stride()])
-            ap_ = (C.c_void_p * 3)(*[s.data_ptr() for s in sa])
-            gg = (C.c_int * 6)(*[v for p in preds for v in (p.shape[2], p.shape[3])])
             xg = torch.empty_like(x)
             gather = event_ms(lambda: L.check(lib.yolo_tile_gather(frame.data_ptr(), a.height, a.width, d_origins.data_ptr(), B, T_, T_,
                                                                    xg.data_ptr(), stream)), a.reps, torch)
@@ -167,7 +158,7 @@ def main():
                 gather_scaled[f"{lh}x{lw}"] = event_ms(
                     lambda: L.check(lib.yolo_tile_gather_scaled(frame.data_ptr(), a.height, a.width, lh, lw, d_org.data_ptr(), B, T_, T_,
                                                                 xg.data_ptr(), stream)), a.reps, torch)
-            decode = event_ms(lambda: L.check(lib.yolo_decode3_hw(pp, st, ap_, gg, B, a.classes, 0, boxes.data_ptr(), n_per, stream)), a.reps, torch)
+            decode = event_ms(lambda: yt.boxes._decode3(preds, sa, B, boxes, n_per, stream=stream), a.reps, torch)
             d_tiles = torch.tensor([[0, int(y), int(x0), 0] for y, x0 in origins[:B].tolist()], dtype=torch.int32).cuda()
             d_hw = torch.tensor([[a.height, a.width]], dtype=torch.int32).cuda()
             cand1 = torch.zeros((1, cap, 6), dtype=torch.float32, device=dev)

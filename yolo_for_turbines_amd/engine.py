@@ -13,7 +13,9 @@ Data layout in HBM (fp32 path)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import os
 import weakref
 from dataclasses import dataclass
@@ -790,6 +792,30 @@ class ModelState:
         # event wait, the same with a Python busy-poll on the event, ROC_ACTIVE_WAIT_TIMEOUT and HSA_ENABLE_INTERRUPT=0 -
         # 1,673-1,690 images/s either way, so the gap is not the host's wake-up)
         self._raise_flag(int(flag_tensor.item()))
+
+    @contextlib.contextmanager
+    def deferred_nan(self):
+        """Eval forwards inside leave their NaN flag for :meth:`take_pending_flag` instead of reading it; every exit undoes it."""
+        self._defer_nan, self._pending_flag = True, None
+        try:
+            yield self
+        finally:
+            self._defer_nan, self._pending_flag = False, None
+
+    def take_pending_flag(self):
+        """The flag tensor the last forward under :meth:`deferred_nan` left (None: ``nan_check`` off, or taken already); clears it."""
+        flag, self._pending_flag = self._pending_flag, None
+        return flag
+
+    def keep_pending_flag(self, tail_ptr, slot, stream):
+        """:meth:`take_pending_flag` into the 32-bit slot ``slot`` of a device buffer, stream-ordered: a slot per forward, one read."""
+        flag = self.take_pending_flag()
+        if flag is not None:
+            L.check(L.lib().yolo_copy_d2d(tail_ptr + 4 * slot, flag.data_ptr(), 4, stream), "nan flag copy")
+
+    def raise_on_flags(self, flags):
+        """Raise as the forwards would have, from the host values of the slots :meth:`keep_pending_flag` filled."""
+        self._raise_flag(functools.reduce(int.__or__, flags, 0))
 
     @staticmethod
     def _raise_flag(flag):

@@ -8,7 +8,7 @@ backward kernels. Same constructor, same `forward(predictions, targets, anchors)
 import torch
 import torch.nn as nn
 
-from .utils import calc_iou
+from .boxes import calc_iou
 
 
 class YOLOLoss(nn.Module):

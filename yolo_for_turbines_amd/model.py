@@ -240,3 +240,34 @@ class YOLOv3(nn.Module):
             np.asarray(header, np.int32).tofile(f)
             for t in parts:
                 t.detach().float().cpu().contiguous().numpy().ravel().tofile(f)
+
+
+def save_checkpoint(model, optimizer, filename="YOLOv3TurbineCheckpoint.pth.tar", ema=None):
+    """`utils.py:383-396`: ``{"state_dict": model.state_dict(), "optimizer": optimizer.state_dict()}`` through ``torch.save``.
+    The model's 438 ``state_dict`` entries and its parameter order are the reference's, so a file written here loads with
+    the reference's ``load_checkpoint`` and the other way round (pinned by ``tests/golden/checkpoint.npz``).
+    ``ema`` (a ``ModelEMA``): the file gains one key, ``"ema"`` (``ema.state_dict()``); without it the file is the reference's."""
+    checkpoint = {"state_dict": model.state_dict(), "optimizer": optimizer.state_dict()}
+    if ema is not None:
+        checkpoint["ema"] = ema.state_dict()
+    torch.save(checkpoint, filename)
+
+
+def load_checkpoint(model, optimizer, lr, filename="", model_folder=None, map_location=None, ema=None):
+    """`utils.py:398-416`: restore model and optimizer, then force every param group's ``lr``. The reference prefixes
+    ``config.MODEL_FOLDER`` and maps to ``config.DEVICE``; there is no global config here, so both are arguments
+    (``model_folder=None``: ``filename`` is the path; ``map_location=None``: the model's own device). ``ema``: restored from the
+    file's ``"ema"`` entry; a file written without one raises ``KeyError``."""
+    path = filename if model_folder is None else f"{model_folder}/{filename}"
+    if map_location is None:
+        map_location = next(model.parameters()).device
+    checkpoint = torch.load(path, map_location=map_location)
+    if ema is not None and "ema" not in checkpoint:
+        raise KeyError(f"{path} holds no weight average (no \"ema\" entry: it was saved without ema=)")
+    model.load_state_dict(checkpoint["state_dict"])          # invalidates the packed-weight cache (post-hook in model.py)
+    optimizer.load_state_dict(checkpoint["optimizer"])
+    for param_group in optimizer.param_groups:
+        param_group["lr"] = lr
+    if ema is not None:
+        ema.load_state_dict(checkpoint["ema"])
+    print(f"Checkpoint loaded from {filename}")

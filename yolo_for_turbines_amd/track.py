@@ -9,7 +9,7 @@ import math
 import torch
 
 from . import _lib as L
-from .utils import detect
+from .boxes import detect
 
 __all__ = ["Tracker", "TrackResult", "track_images"]
 
@@ -178,13 +178,9 @@ def track_images(model, x, scaled_anchors, tracker, iou_threshold=0.45):
     if tracker.box_format != "center":
         raise ValueError("track_images decodes centre-format boxes: the tracker must have box_format='center'")
     eng = model._engine
-    eng._defer_nan, eng._pending_flag = True, None
-    try:
-        with torch.no_grad():
-            preds = model(x)
-        flag = eng._pending_flag
-    finally:
-        eng._defer_nan, eng._pending_flag = False, None
+    with eng.deferred_nan(), torch.no_grad():
+        preds = model(x)
+        flag = eng.take_pending_flag()
     boxes, keep, count = detect(preds, scaled_anchors, iou_threshold, tracker.low_threshold, "center")
     res = tracker.update(boxes, keep, count)
     if flag is not None:
