@@ -78,9 +78,18 @@ enum { YOLO_OUT_NHWC = 0, YOLO_OUT_UPSAMPLE2X = 1, YOLO_OUT_HEAD = 2 };
  * its batch on finite data. An Inf or a NaN in x or in the filters turns every output it reaches into NaN (YOLO_FLAG_NANCHECK sees
  * it). w_packed stays what the filter flag says; yolo_conv_workspace_bytes reports the planes, 36 * cin * (tiles_pad64 + cout_pad64)
  * * 6 bytes. Together with YOLO_FLAG_SPLIT_K, YOLO_FLAG_SPLIT_BF16 or YOLO_FLAG_SPLIT_WEIGHTS_READY, without a filter flag, or on any
- * other descriptor the flag is refused with YOLO_ERR_UNSUPPORTED. Without the flag nothing changes. */
+ * other descriptor the flag is refused with YOLO_ERR_UNSUPPORTED. Without the flag nothing changes.
+ * YOLO_FLAG_FILTER_PLANES (next to YOLO_FLAG_FILTERS_READY or YOLO_FLAG_FILTERS_APPENDED, on fp32 descriptors that run as tile 15 with
+ * its workspace and cin a multiple of 32): directly behind the U4 this launch uses, at U4 + yolo_wino4_filter_bytes(d), lie its bf16
+ * planes, yolo_wino4_filter_plane_bytes(d) of them, as yolo_wino4_filter_planes made them. It describes the buffer, as the two
+ * filter flags do. With YOLO_FLAG_WINO_SPLIT_BF16 the transform pass then splits no filters (its trailing blocks only read the planes,
+ * so that they come from the memory-side cache when the GEMMs ask for them), the GEMMs read the filter planes from there, and the
+ * part of the workspace behind the V planes is not touched: the same bits as the launch without the flag.
+ * Without YOLO_FLAG_WINO_SPLIT_BF16 it is accepted and ignored. yolo_conv_workspace_bytes does not change with it. Anywhere else
+ * (without a filter flag, on a layer that does not run as tile 15, with cin not a multiple of 32) it is an argument error. */
 enum { YOLO_FLAG_RESIDUAL = 1, YOLO_FLAG_NANCHECK = 2, YOLO_FLAG_FILTERS_READY = 4, YOLO_FLAG_SPLIT_BF16 = 8,
-       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32, YOLO_FLAG_FILTERS_APPENDED = 64, YOLO_FLAG_WINO_SPLIT_BF16 = 128 };
+       YOLO_FLAG_SPLIT_WEIGHTS_READY = 16, YOLO_FLAG_SPLIT_K = 32, YOLO_FLAG_FILTERS_APPENDED = 64, YOLO_FLAG_WINO_SPLIT_BF16 = 128,
+       YOLO_FLAG_FILTER_PLANES = 256 };
 
 /* One fused block: y = [residual +] act(scale[c] * conv(x, w)[c] + shift[c]).
  * Replaces CNNBlock.forward (model.py:80-86: Conv2d -> BatchNorm2d(eval) -> LeakyReLU/Mish, or
@@ -253,6 +262,14 @@ int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half);
  * yolo_conv_wino4_split_eligible: 1 when, in addition, the shape measured faster that way at batch 32 (the eval plan's list). */
 int yolo_conv_wino4_split_supported(const yolo_conv_desc* d);
 int yolo_conv_wino4_split_eligible(const yolo_conv_desc* d);
+/* The bf16 planes of U4 made once instead of on every YOLO_FLAG_WINO_SPLIT_BF16 launch, for weights that stay the same from call to
+ * call. yolo_wino4_filter_plane_bytes: 36 * cin * cout_pad64 * 6 (cin and cout only), or 0 where tile 15 does not honour
+ * YOLO_FLAG_WINO_SPLIT_BF16 on the layer (not fp32 3x3 stride 1 with NHWC output, or cin not a multiple of 32).
+ * yolo_wino4_filter_planes reads the finished fp32 U4 (yolo_wino4_filters) and writes its planes (both 16-byte aligned, not
+ * overlapping): the very bytes a YOLO_FLAG_WINO_SPLIT_BF16 launch leaves behind the V planes in its workspace. Written directly
+ * behind U4, at U4 + yolo_wino4_filter_bytes(d), they are what YOLO_FLAG_FILTER_PLANES names. */
+size_t yolo_wino4_filter_plane_bytes(const yolo_conv_desc* d);
+int yolo_wino4_filter_planes(const yolo_conv_desc* d, const void* U4, void* planes, void* stream);
 
 /* ---- training: batch-statistics BatchNorm, activation, and the conv gradients ------------- */
 /* All of these replace pieces of `grad_scaler.scale(loss).backward()` / the train-mode forward of

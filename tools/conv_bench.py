@@ -8,6 +8,8 @@
   python tools/conv_bench.py --layer c13_3x3,c19_3x3 --tile 0 --filters-appended --rounds 7    (the eval plan's route on the small maps)
   python tools/conv_bench.py --layer c52_3x3 --filters-ready --wino-split both --rounds 7 --reps 20    (tile 15 with its GEMMs on f32 MFMAs,
                                                                   then on bf16 planes: YOLO_FLAG_WINO_SPLIT_BF16, one process)
+  python tools/conv_bench.py --layer c13_3x3 --tile 0 --filters-appended --wino-split both --filter-planes both --rounds 7 --reps 20
+                                                                 (... and then on filter planes made once: YOLO_FLAG_FILTER_PLANES)
   python tools/conv_bench.py --splitk --rounds 7 --reps 100      (batch 1: every fp32 conv shape of the 416 and 608 networks on the
                                                                   default plan's launch and as YOLO_FLAG_SPLIT_K, alternating)
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES ... -- python3 tools/conv_bench.py ...
@@ -55,7 +57,7 @@ OUT_MODES = {"nhwc": L.OUT_NHWC, "up2x": L.OUT_UPSAMPLE2X, "head": L.OUT_HEAD}
 
 
 def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out="nhwc", rounds=1, ready=False, filters_ready=False, filters_appended=False,
-        wino_split=False):
+        wino_split=False, filter_planes=False):
     H, cin, cout, k, s = LAYERS[name]
     lib = L.lib()
     cpad = (cin + 3) // 4 * 4
@@ -82,15 +84,20 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     if filters_ready:                                             # Winograd F(4x4) on filters transformed once, in place of wp
         d.flags |= L.FLAG_FILTERS_READY
         d.tile = 15
-        u4 = torch.empty(lib.yolo_wino4_filter_bytes(d), dtype=torch.uint8, device=dev)
+        nu = lib.yolo_wino4_filter_bytes(d)
+        u4 = torch.empty(nu + (lib.yolo_wino4_filter_plane_bytes(d) if filter_planes else 0), dtype=torch.uint8, device=dev)
         L.check(lib.yolo_wino4_filters(d, wp.data_ptr(), u4.data_ptr(), stream), "yolo_wino4_filters")
-        wp = u4
+        wp, u4_at = u4, u4.data_ptr()
     if filters_appended:                                         # the route of the eval plan: U4 in place behind the packed weights, tile as given
         d.flags |= L.FLAG_FILTERS_APPENDED
-        wa = torch.empty(lib.yolo_wino4_appended_bytes(d), dtype=torch.uint8, device=dev)
+        na, nu = lib.yolo_wino4_appended_bytes(d), lib.yolo_wino4_filter_bytes(d)
+        wa = torch.empty(na + (lib.yolo_wino4_filter_plane_bytes(d) if filter_planes else 0), dtype=torch.uint8, device=dev)
         wa[:wp.numel()] = wp
-        L.check(lib.yolo_wino4_filters(d, wa.data_ptr(), wa.data_ptr() + wa.numel() - lib.yolo_wino4_filter_bytes(d), stream), "yolo_wino4_filters")
-        wp = wa
+        L.check(lib.yolo_wino4_filters(d, wa.data_ptr(), wa.data_ptr() + na - nu, stream), "yolo_wino4_filters")
+        wp, u4_at = wa, wa.data_ptr() + na - nu
+    if filter_planes:                                             # the bf16 planes of U4 made once, directly behind it
+        d.flags |= L.FLAG_FILTER_PLANES
+        L.check(lib.yolo_wino4_filter_planes(d, u4_at, u4_at + nu, stream), "yolo_wino4_filter_planes")
 
     if wino_split:                                                # the 36 GEMMs of tile 15 on bf16 planes (with either filter flag)
         d.flags |= L.FLAG_WINO_SPLIT_BF16
@@ -128,7 +135,7 @@ def run(name, batch, tile, reps, residual, dev, dtype="fp32", split3=False, out=
     if picked == 15:                                              # Winograd F(4x4): how the launch is cut on this device
         whole, half = C.c_int(), C.c_int()
         L.check(lib.yolo_conv_wino4_blocks(d, C.byref(whole), C.byref(half)), "yolo_conv_wino4_blocks")
-        cut += f"  tile blocks: {whole.value} whole + {half.value} in halves" + ("  filters ready" if filters_ready else "") + ("  filters appended" if filters_appended else "") + ("  bf16 planes" if wino_split else "")
+        cut += f"  tile blocks: {whole.value} whole + {half.value} in halves" + ("  filters ready" if filters_ready else "") + ("  filters appended" if filters_appended else "") + ("  bf16 planes" if wino_split else "") + ("  filter planes once" if filter_planes else "")
     print(f"{name:12s} tile={picked} {ms * 1e3:8.1f} us  {gflop / ms:7.2f} TFLOP/s  ({gflop:.1f} GFLOP){cut}", flush=True)
     return ms
 
@@ -213,6 +220,9 @@ def main():
     ap.add_argument("--filters-appended", action="store_true", help="YOLO_FLAG_FILTERS_APPENDED: U4 made in place behind the packed weights (tile 0: the eval plan's route)")
     ap.add_argument("--wino-split", nargs="?", const="on", default="off", choices=["off", "on", "both"],
                     help="YOLO_FLAG_WINO_SPLIT_BF16 on a --filters-ready / --filters-appended launch; 'both': without it, then with it")
+    ap.add_argument("--filter-planes", nargs="?", const="on", default="off", choices=["off", "on", "both"],
+                    help="YOLO_FLAG_FILTER_PLANES on a --wino-split launch: the planes of U4 made once (yolo_wino4_filter_planes); 'both': "
+                         "every launch splitting its filters, then on the planes made once")
     ap.add_argument("--out", default="nhwc", choices=list(OUT_MODES))
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds of --reps launches; the median is reported")
     ap.add_argument("--splitk", action="store_true", help="batch-1 table: the default plan's launch against YOLO_FLAG_SPLIT_K, per conv shape")
@@ -227,7 +237,9 @@ def main():
     for n in names:
         for t in tiles:
             for ws in {"off": (False,), "on": (True,), "both": (False, True)}[a.wino_split]:
-                run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready, a.filters_ready, a.filters_appended, ws)
+                for fp in {"off": (False,), "on": (True,), "both": (False, True)}[a.filter_planes] if ws else (False,):
+                    run(n, a.batch, t, a.reps, a.residual, dev, a.dtype, a.split3, a.out, a.rounds, a.split3_ready, a.filters_ready, a.filters_appended,
+                        ws, fp)
 
 
 if __name__ == "__main__":

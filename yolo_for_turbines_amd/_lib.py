@@ -18,6 +18,7 @@ FLAG_RESIDUAL, FLAG_NANCHECK, FLAG_FILTERS_READY, FLAG_SPLIT_BF16, FLAG_SPLIT_WE
 FLAG_SPLIT_K = 32
 FLAG_FILTERS_APPENDED = 64
 FLAG_WINO_SPLIT_BF16 = 128
+FLAG_FILTER_PLANES = 256
 WGRAD_KERNEL_F32, WGRAD_KERNEL_PATCH, WGRAD_KERNEL_DMA, WGRAD_KERNEL_STEM = 0, 1, 2, 3      # YOLO_WGRAD_KERNEL_* of the header
 LOSS_BOX_KINDS = {"mse": 0, "giou": 1, "diou": 2, "ciou": 3}          # YOLO_LOSS_BOX_* / YOLO_LOSS_OBJ_* of the header
 LOSS_OBJ_KINDS = {"mse": 0, "bce": 1}
@@ -140,6 +141,8 @@ _SIGS = {
     "yolo_conv_wino4_blocks": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "yolo_conv_wino4_split_supported": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_wino4_split_eligible": (C.c_int, [C.POINTER(ConvDesc)]),
+    "yolo_wino4_filter_plane_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "yolo_wino4_filter_planes": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_bn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_bn_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

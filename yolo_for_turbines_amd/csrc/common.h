@@ -252,9 +252,15 @@ int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm,
 bool wino4_split_supported(const yolo_conv_desc* d);
 bool wino4_split_eligible(const yolo_conv_desc* d);
 size_t wino4_split_workspace_bytes(const yolo_conv_desc* d);
-int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, void* workspace, hipStream_t s);
-int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const float* scale, const float* shift, const void* residual,
-                       void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
+// how both GEMM kernels cut a launch into whole and half workgroups (conv_wino4_f32.hip): compute units of the current device (0: none);
+// the tile blocks that stay whole
+int wino4_num_cus();
+int wino4_whole_blocks(int n_mt, int n_nt, int cus);
+// (U_planes: the filter planes made once, yolo_wino4_filter_planes, which the transform pass only reads ahead of the GEMMs; NULL: this
+// launch splits U4 into the workspace behind the V planes)
+int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace, hipStream_t s);
+int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, const float* scale, const float* shift,
+                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)
 size_t h16_frag_elems(int cout, int cin, int ks);
 int h16_pack(const float* w_oihw, void* wf, int cout, int cin, int ks, int dtype, hipStream_t s);

@@ -124,6 +124,10 @@ static int check_flags(const yolo_conv_desc* d, const F32Route& r, const void* w
                                           "YOLO_FLAG_SPLIT_WEIGHTS_READY, YOLO_FLAG_SPLIT_K");
     if (filters_appended && !wino4)
         return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTERS_APPENDED on a layer that does not run as Winograd F(4x4) (tile 15 with its workspace)");
+    // ... with its bf16 planes behind it: describes the buffer of either filter flag, where the planes kernel could read it
+    if ((d->flags & YOLO_FLAG_FILTER_PLANES) && !(wino4 && wino4_split_supported(d) && (d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED))))
+        return fail(YOLO_ERR_ARG, "conv: YOLO_FLAG_FILTER_PLANES goes with YOLO_FLAG_FILTERS_READY or YOLO_FLAG_FILTERS_APPENDED on a layer that runs as "
+                                  "Winograd F(4x4) (tile 15 with its workspace) with cin %% 32 == 0");
     const bool split3 = d->flags & YOLO_FLAG_SPLIT_BF16;
     if (split3 && r.kind != F32Kind::Split3)
         return fail(YOLO_ERR_UNSUPPORTED, "conv: YOLO_FLAG_SPLIT_BF16 needs an fp32 layer of the direct kernels (no Winograd workspace in play) with "
@@ -180,7 +184,10 @@ static int conv_fwd_impl(const yolo_conv_desc* d, const void* x, const void* w, 
     case F32Kind::Wino4: {          // the filters are transformed per launch from the row-major section, unless the caller brings U4
         if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile 15 needs fp32 3x3 stride 1 with NHWC output and channel counts %% 4 == 0");
         const float* U4 = d->flags & (YOLO_FLAG_FILTERS_READY | YOLO_FLAG_FILTERS_APPENDED) ? (const float*)wr : nullptr;
-        if (d->flags & YOLO_FLAG_WINO_SPLIT_BF16) return conv_wino4s_launch(d, x, U4, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
+        if (d->flags & YOLO_FLAG_WINO_SPLIT_BF16) {         // (YOLO_FLAG_FILTER_PLANES: the planes of U4 lie directly behind it; ignored on the f32 GEMMs)
+            const void* planes = d->flags & YOLO_FLAG_FILTER_PLANES ? wr + wino4_filter_bytes(d) : nullptr;
+            return conv_wino4s_launch(d, x, U4, planes, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
+        }
         return conv_wino4_launch(d, x, U4 ? nullptr : (const float*)w, U4, scale, shift, residual, y, ws, ws_bytes, nan_flag, s);
     }
     case F32Kind::Wino:

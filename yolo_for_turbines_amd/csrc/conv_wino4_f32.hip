@@ -19,7 +19,8 @@
 //                    Inference, whose weights stay the same from call to call, makes U4 once instead (wino4_filters_f32 through
 //                    yolo_wino4_filters, YOLO_FLAG_FILTERS_READY): the launch then has no filter blocks.
 //                    wino4_xform_f32<true> (YOLO_FLAG_WINO_SPLIT_BF16) writes the same V4, and the caller's finished U4, as bf16 planes
-//                    for conv_wino4s_f32.hip instead (wino4_planes.h).
+//                    for conv_wino4s_f32.hip instead (wino4_planes.h); where the caller keeps the filter planes too
+//                    (YOLO_FLAG_FILTER_PLANES, made once by yolo_wino4_filter_planes) its trailing blocks only read them ahead.
 //   conv_wino4_f32   per workgroup 64 tiles x 64 output channels (the block of conv_wino_f32: the same operand bytes per MFMA, so
 //                    the same LDS-DMA price per matrix cycle): 36 GEMMs D_xi[co][tile] = sum_ci U4_xi[co][ci] V4_xi[tile][ci] in SIX
 //                    passes over K, one row a of the 6x6 product matrix M per pass (xi = 6a .. 6a + 5). Y = A^T M A is linear in the
@@ -130,14 +131,35 @@ __device__ __forceinline__ void wino4_filter_planes(const Wino4XArgs& p, long lo
     }
 }
 
+// Filter planes made once (YOLO_FLAG_FILTER_PLANES) lie in HBM when their layer's turn comes: a forward reads more filter bytes than
+// the caches hold. conv_wino4s_f32 requests a stage three stages ahead, which covers the memory-side cache but not HBM (measured in
+// the forward, DESIGN 4.15: 151 against 114 us at 26 x 26). So the blocks behind the input transform read the planes once, one dword
+// per 64 bytes, while the input is transformed: p.U points at them, element i = 64 bytes
+__device__ __forceinline__ void wino4_touch_planes(const Wino4XArgs& p, long long first, long long stride) {
+    const char* pl = reinterpret_cast<const char*>(p.U);
+    const long long n = p.utotal * 27 / 8;                           // 36 xi x 6 bytes x utotal / 64
+    for (long long i = first; i < n; i += stride) {
+        unsigned v;
+        asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(pl + i * 64) : "memory");
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// the filter planes alone, once per weight update (yolo_wino4_filter_planes): the same device function, so the same bytes
+__global__ __launch_bounds__(256) void wino4_filter_planes_f32(const Wino4XArgs p) {
+    wino4_filter_planes(p, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
 // PLANES (YOLO_FLAG_WINO_SPLIT_BF16, C4 % 8 == 0): the same values v, each split into three bf16 (s3_split) and stored as the planes
 // of wino4_planes.h in place of V4; the blocks behind the input transform split the caller's finished U4 the same way
 template <bool PLANES>
 __global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
     if ((int)blockIdx.x >= p.nxb) {
         const long long first = (long long)(blockIdx.x - p.nxb) * blockDim.x + threadIdx.x, stride = (long long)(gridDim.x - p.nxb) * blockDim.x;
-        if constexpr (PLANES) wino4_filter_planes(p, first, stride);
-        else wino4_filter_elems(p, first, stride);
+        if constexpr (PLANES) {
+            if (p.w) wino4_filter_planes(p, first, stride);
+            else wino4_touch_planes(p, first, stride);                // (the planes were made once: p.U)
+        } else wino4_filter_elems(p, first, stride);
         return;
     }
     // 8 lanes = the 8 channel quads of one pixel's 128-byte line, 8 tiles per wave (the access pattern of wino_xform_f32)
@@ -570,7 +592,7 @@ size_t wino4_workspace_bytes(const yolo_conv_desc* d) {
 }
 
 // compute units of the current device, asked once per device (0: no device)
-static int wino4_num_cus() {
+int wino4_num_cus() {
     static std::atomic<int> cus[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -585,7 +607,7 @@ static int wino4_num_cus() {
 // stay whole (all channel blocks of a tile block together). If the rest is at most half a round of workgroups, each of its tile
 // blocks runs as two workgroups of 32 tiles, so the short last round uses twice the CUs for half the multiply work each.
 // Looks at (n_mt, n_nt, CUs) only; the arithmetic of a tile does not depend on the cut.
-static int wino4_whole_blocks(int n_mt, int n_nt, int cus) {
+int wino4_whole_blocks(int n_mt, int n_nt, int cus) {
     if (cus <= 0) return n_mt;
     const long long wgs = (long long)n_mt * n_nt;
     const int whole = (int)(wgs / cus * cus / n_nt);
@@ -618,19 +640,30 @@ size_t wino4_split_workspace_bytes(const yolo_conv_desc* d) {
     return 36 * nkc * (n_mt + n_nt) * W4S_PIECE;
 }
 
-// V planes at the start of the workspace, the planes of the caller's finished U4 behind them (made again by every launch: the plans
-// keep the fp32 U4 as the launch's weights)
-int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, void* workspace, hipStream_t s) {
+size_t wino4_filter_plane_bytes(const yolo_conv_desc* d) {
+    if (!wino4_split_supported(d)) return 0;
+    return (size_t)36 * (d->cin / 32) * (round_up(d->cout, 64) / 64) * W4S_PIECE;
+}
+
+static long long wino4_filter_plane_blocks(const Wino4XArgs& xa) {
+    const long long ub = (9 * xa.utotal + 255) / 256;
+    return ub < 1024 ? ub : 1024;                                     // (the grid bound that wino4_supported checked)
+}
+
+// V planes at the start of the workspace, the planes of the caller's finished U4 behind them (made again by this launch), unless the
+// caller keeps them (U_planes: nothing behind the V planes is written; the trailing blocks only read U_planes, wino4_touch_planes)
+int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace, hipStream_t s) {
     const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
     const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4;
     Wino4XArgs xa;
-    wino4_filter_args(xa, d, U4, nullptr);
+    wino4_filter_args(xa, d, U_planes ? nullptr : U4, nullptr);
     xa.x = (const float*)x; xa.V = (float*)workspace; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
     xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = C4 / 8;
     xa.nxb = (Tpad / 32) * xa.ncg;
-    xa.U = reinterpret_cast<float*>(static_cast<char*>(workspace) + (size_t)36 * (C4 / 8) * (Tpad / 64) * W4S_PIECE);
-    const long long ub = (9 * xa.utotal + 255) / 256;
-    const int nub = (int)(ub < 1024 ? ub : 1024);                     // (the grid bound that wino4_supported checked)
+    xa.U = U_planes ? const_cast<float*>(static_cast<const float*>(U_planes))
+                    : reinterpret_cast<float*>(static_cast<char*>(workspace) + (size_t)36 * (C4 / 8) * (Tpad / 64) * W4S_PIECE);
+    const long long tb = (xa.utotal * 27 / 8 + 255) / 256;            // blocks that touch 64 bytes per thread once
+    const int nub = (int)(U_planes ? (tb < 1024 ? tb : 1024) : wino4_filter_plane_blocks(xa));
     hipLaunchKernelGGL(wino4_xform_f32<true>, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
     return check_launch("wino4_xform_f32 (planes)");
 }
@@ -707,6 +740,21 @@ int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, 
     wino4_filter_args(xa, d, (const float*)w_packed, (float*)U4);
     hipLaunchKernelGGL(wino4_filters_f32, dim3((unsigned)wino4_filter_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);
     return check_launch("wino4_filters_f32");
+}
+
+size_t yolo_wino4_filter_plane_bytes(const yolo_conv_desc* d) { return d ? yolo::wino4_filter_plane_bytes(d) : 0; }
+
+int yolo_wino4_filter_planes(const yolo_conv_desc* d, const void* U4, void* planes, void* stream) {
+    using namespace yolo;
+    if (!d || !U4 || !planes) return fail(YOLO_ERR_ARG, "wino4 filter planes: null pointer");
+    if (!wino4_split_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filter planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
+    if (((size_t)U4 | (size_t)planes) & 15) return fail(YOLO_ERR_ARG, "wino4 filter planes: U4 and planes must be 16-byte aligned");
+    const char *u = (const char*)U4, *pl = (const char*)planes;
+    if (pl < u + wino4_filter_bytes(d) && u < pl + wino4_filter_plane_bytes(d)) return fail(YOLO_ERR_ARG, "wino4 filter planes: planes overlap the U4 they are made from");
+    Wino4XArgs xa{};
+    wino4_filter_args(xa, d, (const float*)U4, (float*)planes);
+    hipLaunchKernelGGL(wino4_filter_planes_f32, dim3((unsigned)wino4_filter_plane_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);
+    return check_launch("wino4_filter_planes_f32");
 }
 
 int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half) {

@@ -20,7 +20,8 @@
 //            stage g - 1 out of its slot. Then: request one piece of stage g + 3 behind each of the first MFMA pairs, read the nine
 //            fragments of stage g + 1 (3 U + 2 x 3 V, ds_read_b128, into the other fragment set), wait for those of stage g
 //            (lgkmcnt(9)), twelve MFMAs.
-// All workgroups are whole (no half workgroups: wino4_split_eligible names large maps only).
+// One workgroup per CU and round; the tile blocks of a short last round run as two workgroups of 32 tiles each (wino4_whole_blocks, the
+// cut of conv_wino4_f32), and such a half workgroup requests only its own 32 rows of the V piece: 18 KiB per stage instead of 24.
 #include "split3.h"
 #include "wino4_planes.h"
 #include "wino4_epilogue.h"
@@ -30,6 +31,7 @@ namespace yolo {
 struct Wino4SArgs {
     Wino4Args e;             // V / U: the plane buffers; C4p is unused
     int nkc;                 // chunks of 32 input channels
+    int xmap;                // all tile blocks in halves, n_mt and n_nt multiples of 4: an XCD gets 4 tile blocks x 4 channel blocks x both halves
 };
 
 constexpr int W4S_STAGE = 2 * W4S_PIECE; // bytes per ring stage: the V piece, then the U piece
@@ -48,26 +50,51 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, kq = lane >> 4;
-    // block map of conv_wino4_f32: 8 tile blocks (one per XCD) x all channel blocks per row
+    // block map of conv_wino4_f32: 8 tile blocks (one per XCD) x all channel blocks per row. The rows of the whole tile blocks come
+    // first; each row of 8 tail blocks then comes twice, once per half.
     const int xcd = blockIdx.x & 7, bq = blockIdx.x >> 3;
-    const int nt = bq % p.n_nt, mt = (bq / p.n_nt) * 8 + xcd;
-    if (mt >= p.n_mt) return;
-    const int wm = wave & 1, wn = wave >> 1;
+    const int row = bq / p.n_nt, wrows = (p.n_whole + 7) >> 3;
+    int nt = bq % p.n_nt;
+    bool cut = row >= wrows;
+    int half = (row - wrows) & 1;
+    int mt = cut ? p.n_whole + ((row - wrows) >> 1) * 8 + xcd : row * 8 + xcd;
+    if (q.xmap) {
+        // a launch that is all halves: the 32 workgroups of an XCD share 4 tile blocks and 4 channel blocks instead of one tile block
+        // and all channel blocks, so an XCD's L2 streams a quarter of the U planes and half of the V planes (same bits: index
+        // arithmetic only)
+        const int sb = xcd + 8 * (bq >> 5), l = bq & 31, ntg = p.n_mt >> 2;
+        cut = true;
+        half = l & 1;
+        nt = 4 * (sb / ntg) + ((l >> 1) & 3);
+        mt = 4 * (sb % ntg) + (l >> 3);
+    }
+    if (mt >= (cut ? p.n_mt : p.n_whole)) return;
+    // a half workgroup covers tiles 32 half .. + 31 of its block: waves 0 .. 3 (one per SIMD) take the 16 channels each of that
+    // half, the same two 16 x 16 blocks per xi with the same six products in the same order as wave (half, wn) of a whole
+    // workgroup; waves 4 .. 7 only move DMA pieces and meet the barriers
+    const int wm = cut ? half : wave & 1, wn = cut ? wave & 3 : wave >> 1;
+    const bool busy = !cut || wave < 4;
 
     int* tab = reinterpret_cast<int*>(smem + W4S_SLOTS * W4S_STAGE);
-    wino4_tile_table(p, tab, tid, mt, false, 0);
+    wino4_tile_table(p, tab, tid, mt, cut, half);
 
-    // ---- DMA roles: wave w moves KiB 3 w .. 3 w + 2 of a stage (lane = 16 bytes)
-    const bool dv = wave < 4;
+    // ---- DMA roles (lane = 16 bytes). Whole workgroup: wave w moves KiB 3 w .. 3 w + 2 of a stage, waves 0 - 3 the V piece, 4 - 7 the U
+    // piece. Half workgroup: 18 KiB per stage instead of 24. The computing waves 0 - 3 move the U piece, three KiB each as waves 4 - 7
+    // of a whole workgroup do (so their counted waits stay); of the V piece only rows 32 half .. + 31 are requested, 2 KiB per plane,
+    // contiguous in global memory and in LDS, where they go to their usual addresses: waves 4 - 6 move one plane's each, wave 7 nothing.
+    const bool dv = cut ? wave >= 4 : wave < 4;
+    const int dw = cut ? (wave + 4) & 7 : wave;                               // the wave of a whole workgroup whose KiB start this wave's
+    const unsigned own = cut && dv ? (wave - 4) * W4S_PLANE + half * (W4S_PLANE / 2) : 3072 * dw;     // ... or the plane's half: bytes into the stage
     const char* src = (dv ? reinterpret_cast<const char*>(p.V) + (size_t)mt * W4S_PIECE : reinterpret_cast<const char*>(p.U) + (size_t)nt * W4S_PIECE)
-                      + 3072 * (wave & 3);
+                      + (own - (dv ? 0 : W4S_PIECE));
     const size_t s_st = (size_t)(dv ? p.n_mt : p.n_nt) * W4S_PIECE;          // bytes from one (xi, chunk) to the next
     const unsigned lane16 = lane * 16;
     const unsigned lds0 = (unsigned)(size_t)(wn_lptr)smem;
+    const unsigned ldsw = lds0 + own;
     const int nkc = q.nkc;
     auto issue_piece = [&](int k, int pass, int g, int slot) {               // stage g = 6 chunk + x of the pass
         const int kc = g / 6, x = g - 6 * kc;
-        wn_glds16_s(src + ((size_t)(6 * pass + x) * nkc + kc) * s_st + k * 1024, lane16, lds0 + slot * W4S_STAGE + (3 * wave + k) * 1024);
+        wn_glds16_s(src + ((size_t)(6 * pass + x) * nkc + kc) * s_st + k * 1024, lane16, ldsw + slot * W4S_STAGE + k * 1024);
     };
     auto issue = [&](int pass, int g, int slot) { wn_for<0, W4S_DMA>([&](auto K) { issue_piece(decltype(K)::value, pass, g, slot); }); };
 
@@ -195,40 +222,86 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
         }
         wino4_fold_row<a>(acc, py);
     };
-    run_pass(std::integral_constant<int, 0>{});
-    run_pass(std::integral_constant<int, 1>{});
-    run_pass(std::integral_constant<int, 2>{});
-    run_pass(std::integral_constant<int, 3>{});
-    run_pass(std::integral_constant<int, 4>{});
-    run_pass(std::integral_constant<int, 5>{});
+    if (busy) {
+        run_pass(std::integral_constant<int, 0>{});
+        run_pass(std::integral_constant<int, 1>{});
+        run_pass(std::integral_constant<int, 2>{});
+        run_pass(std::integral_constant<int, 3>{});
+        run_pass(std::integral_constant<int, 4>{});
+        run_pass(std::integral_constant<int, 5>{});
+    } else {
+        // the idle waves of a half workgroup: their DMA pieces (two per stage, the 2 KiB of one V plane; wave 7 has none), the waits and
+        // the barriers of run_pass, in the same places
+        constexpr int HD = 2;
+        const bool mover = wave < 7;
+        auto issue_half = [&](int pass, int g, int slot) {
+            if (mover) {
+                issue_piece(0, pass, g, slot);
+                issue_piece(1, pass, g, slot);
+            }
+        };
+        const int ng = 6 * nkc;
+        for (int a = 0; a < 6; ++a) {
+            if (a == 0) {
+                issue_half(0, 0, 0);
+                issue_half(0, 1, 1);
+                issue_half(0, 2, 2);
+            }
+            wn_wait_vmcnt<2 * HD>();
+            __builtin_amdgcn_s_barrier();
+            for (int g = 0; g < ng; ++g) {
+                if (g + 1 < ng) {                            // (run_pass: next)
+                    if (g + 2 < ng) wn_wait_vmcnt<HD>();
+                    else wn_wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();
+                }
+                if (g + 3 < ng) issue_half(a, g + 3, (g + 3) & (W4S_SLOTS - 1));      // (run_pass: ahead)
+            }
+            __syncthreads();
+            if (a < 5) {
+                issue_half(a + 1, 0, 0);
+                issue_half(a + 1, 1, 1);
+                issue_half(a + 1, 2, 2);
+            }
+        }
+    }
 
-    wino4_epilogue<ACT, RES>(p, smem, tab, py, tid, nt, wm, wn, l16, kq, true);
+    wino4_epilogue<ACT, RES>(p, smem, tab, py, tid, nt, wm, wn, l16, kq, busy);
 }
 
 // ------------------------------------------------------------------------------ host side
 // Shapes that the eval plan runs on this kernel: looks at the layer's shape only, never at the batch. The rule of split3_eligible: a
-// shape is listed once its median at batch 32 (tools/conv_bench.py --filters-ready --wino-split both, 7 rounds of 20 launches,
-// transform pass and per-launch filter planes included) improved by more than the spread of its own baseline's rounds
-// (profiles/wino4_split/conv_bench.txt; medians in us, f32 GEMMs -> bf16 planes):
-//   256 -> 512 at 26 x 26     189 - 193 -> 134 - 136, with residual 197 - 199 -> 141 - 145 (baseline spread 15 - 18): listed.
-//   128 -> 256 at 52 x 52     185 - 195 -> 170 - 172, with residual 213 - 217 -> 199 - 203. Every round on planes beat every round
-//                             of its baseline, but the baseline's rounds spread 17 - 27 in six of the eight runs, more than the gain:
-//                             not listed.
-//   64 -> 128 at 104 x 104    253 -> 260 (V4 grows from 199 to 299 MB and is read by two channel blocks only): stays.
-//   512 -> 1024 at 13 x 13    220 -> 238 (128 whole workgroups on 256 CUs, and every launch splits 75.5 MB of U4): stays.
+// shape is listed once its median at batch 32 (tools/conv_bench.py --wino-split both --filter-planes on, 7 rounds of 20 launches,
+// transform pass included, filter planes made once) improved by more than the spread of its own baseline's rounds; where that stays
+// undecided, the whole forward decides (bench.py on builds that differ in the list entry alone). profiles/wino4_planes_once, DESIGN
+// 4.15; medians in us, f32 GEMMs -> bf16 planes:
+//   256 -> 512 at 26 x 26     197 -> 128, with residual 203 -> 135 (baseline spread 23 - 26): listed.
+//   512 -> 1024 at 13 x 13    228 - 236 -> 179 - 181, with residual 230 - 240 -> 182 - 185 (256 half workgroups; baseline spread 43 - 52,
+//                             all of it one slow first round): undecided per shape; the forward with the entry is 0.05 ms faster: listed.
+//   512 -> 1024 at 19 x 19    338 -> 236, with residual 352 -> 293 (baseline spread 47 - 52): listed.
+//   128 -> 256 at 52 x 52     193 - 199 -> 155 - 158, with residual 219 -> 183 - 187 (baseline spread 23 - 29): listed.
+//   64 -> 128 at 104 x 104    253 -> 247, with residual 290 -> 291 (spread 35 - 37): stays.
+// conv_bench.py repeats one layer, whose filters then stay in the memory-side cache; in a forward they come from HBM, which is why the
+// transform pass reads the planes ahead (wino4_touch_planes) and why the forward has the last word.
 // Nothing else was measured (the 38 x 38 and 76 x 76 maps of the 608 network stay on the f32 GEMMs).
 bool wino4_split_eligible(const yolo_conv_desc* d) {
-    return wino4_split_supported(d) && d->h == 26 && d->w == 26 && d->cin == 256 && d->cout == 512;
+    if (!wino4_split_supported(d) || d->h != d->w) return false;
+    if (d->h == 26 && d->cin == 256 && d->cout == 512) return true;
+    if ((d->h == 13 || d->h == 19) && d->cin == 512 && d->cout == 1024) return true;
+    return d->h == 52 && d->cin == 128 && d->cout == 256;
 }
 
-int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const float* scale, const float* shift, const void* residual,
-                       void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
+// U_planes: the planes of U4 made once (YOLO_FLAG_FILTER_PLANES: the transform pass only reads them ahead and the U region of the
+// workspace is left alone), or NULL: this launch makes them there
+int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, const float* scale, const float* shift,
+                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
     if (!wino4_split_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4) on bf16 planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
     const size_t need = wino4_split_workspace_bytes(d);
     if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4) on bf16 planes: workspace %zu < %zu bytes", workspace_bytes, need);
     if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: workspace must be 16-byte aligned");
     if (!U4 || ((size_t)U4 & 15)) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: transformed filters must be 16-byte aligned");
-    if (int rc = wino4_planes_launch(d, x, U4, workspace, s)) return rc;
+    if ((size_t)U_planes & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: filter planes must be 16-byte aligned");
+    if (int rc = wino4_planes_launch(d, x, U4, U_planes, workspace, s)) return rc;
 
     const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
     const int T = d->n * th * tw, Tpad = round_up(T, 64), CoutPad = round_up(d->cout, 64);
@@ -236,13 +309,16 @@ int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, 
     Wino4Args& a = q.e;
     q.nkc = d->cin / 32;
     a.V = (const float*)workspace;
-    a.U = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + (size_t)36 * q.nkc * (Tpad / 64) * W4S_PIECE);
+    a.U = U_planes ? (const float*)U_planes
+                   : reinterpret_cast<const float*>(static_cast<const char*>(workspace) + (size_t)36 * q.nkc * (Tpad / 64) * W4S_PIECE);
     a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y; a.nan_flag = nan_flag;
     a.T = T; a.Tpad = Tpad; a.C4p = d->cin / 4; a.Cout = d->cout; a.CoutPad = CoutPad;
     a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
     a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
-    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64; a.n_whole = a.n_mt;
-    const int grid = 8 * a.n_nt * ceil_div(a.n_mt, 8);
+    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64;
+    a.n_whole = wino4_whole_blocks(a.n_mt, a.n_nt, wino4_num_cus());
+    q.xmap = a.n_whole == 0 && a.n_mt % 4 == 0 && a.n_nt % 4 == 0 && (a.n_mt / 4) * (a.n_nt / 4) % 8 == 0;
+    const int grid = q.xmap ? 2 * a.n_mt * a.n_nt : 8 * a.n_nt * (ceil_div(a.n_whole, 8) + 2 * ceil_div(a.n_mt - a.n_whole, 8));
     const bool res = d->flags & YOLO_FLAG_RESIDUAL;
     const size_t lds = (size_t)W4S_SLOTS * W4S_STAGE + W4_TAB;       // (the epilogue's staging, 256 x 68 x 4, lies over the idle ring)
     auto go = [&](auto kern) -> int {

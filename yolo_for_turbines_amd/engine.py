@@ -194,6 +194,8 @@ def build_network_program(model, B, H, ch_align=4, W=None):
 #          packed weights then planes, made in place; None where ``w`` has no room.
 #   "u4a"  the same filters U4 behind the packed weights (YOLO_FLAG_FILTERS_APPENDED): the last yolo_wino4_filter_bytes of that
 #          front of ``w``, made in place; None where ``w`` has no room.
+# Directly behind a U4 of either kind, in the same allocation, lie its bf16 planes (YOLO_FLAG_FILTER_PLANES, yolo_wino4_filter_planes)
+# where the library can run the layer on them: made right after the U4, by the same stamp. The tensors above keep their sizes.
 _PREPARED = {
     "u4": ("yolo_wino4_filter_bytes", "own", "yolo_wino4_filters"),
     "s3": ("yolo_split3_weight_bytes", "front", "yolo_split3_weights"),
@@ -217,6 +219,15 @@ def _prepared_room(cv, code):
     return 0
 
 
+def _planes_room(cv, code, room):
+    """Bytes a new fp32 block allocates behind ``w`` for the bf16 planes of an appended U4 (YOLO_FLAG_FILTER_PLANES wants them directly
+    behind it): 1.5 x the filters, 113 MB for each of the seven 512 -> 1024 blocks. ``w`` itself keeps its size."""
+    lib = L.lib()
+    d = L.ConvDesc(n=1, h=8, w=8, cin=cv.in_channels, cout=cv.out_channels, ksize=cv.kernel_size[0], stride=cv.stride[0],
+                   x_ld=(cv.in_channels + 3) // 4 * 4, y_ld=cv.out_channels, dtype=code)
+    return lib.yolo_wino4_filter_plane_bytes(C.byref(d)) if room and room == lib.yolo_wino4_appended_bytes(C.byref(d)) else 0
+
+
 class PackedBlock:
     """Device-side packed weights + folded BN of one CNNBlock."""
 
@@ -231,7 +242,10 @@ class PackedBlock:
             raise NotImplementedError(f"conv {cv.in_channels}->{cv.out_channels} k{cv.kernel_size[0]} has no {dtype} kernel "
                                       "(16-bit needs cin % 32 == 0)")
         room = _prepared_room(cv, self.code) if dtype == "fp32" and n else 0
-        self.w = torch.empty(max(n, room, 16), dtype=torch.uint8, device=device)
+        # ``w`` is the front of its allocation; behind it lies the room for the planes of an appended U4
+        nw = max(n, room, 16)
+        self._alloc = torch.empty(nw + (_planes_room(cv, self.code, room) if room else 0), dtype=torch.uint8, device=device)
+        self.w = self._alloc[:nw]
         self.scale = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.shift = torch.empty(cv.out_channels, dtype=torch.float32, device=device)
         self.stem_w = None
@@ -291,10 +305,24 @@ class PackedBlock:
                 raise L.YoloLibError(f"{size}: the layer cannot run as tile 15")
             if where != "own" and (n == 0 or n > self.w.numel()):
                 return None
-            buf = (torch.empty(n, dtype=torch.uint8, device=self.w.device) if where == "own" else self.w[:n] if where == "front"
-                   else self.w[n - L.lib().yolo_wino4_filter_bytes(C.byref(desc)):n])
-            p = self.prepared[kind] = SimpleNamespace(buf=buf, desc=L.ConvDesc.from_buffer_copy(desc), stamp=None)
+            # the bf16 planes of U4 (YOLO_FLAG_FILTER_PLANES) lie directly behind it in the same allocation: ``buf`` is the front of a
+            # larger one ("u4"), or the planes follow ``w`` ("u4a", where the block kept the room); None where the library makes none
+            planes, npl = None, L.lib().yolo_wino4_filter_plane_bytes(C.byref(desc)) if kind in ("u4", "u4a") else 0
+            if where == "own":
+                alloc = torch.empty(n + npl, dtype=torch.uint8, device=self.w.device)
+                buf, planes = alloc[:n], alloc[n:] if npl else None
+            elif where == "front":
+                buf = self.w[:n]
+            else:
+                buf = self.w[n - L.lib().yolo_wino4_filter_bytes(C.byref(desc)):n]
+                if npl and n == self.w.numel() and n + npl <= self._alloc.numel():
+                    planes = self._alloc[n:n + npl]
+            p = self.prepared[kind] = SimpleNamespace(buf=buf, planes=planes, desc=L.ConvDesc.from_buffer_copy(desc), stamp=None)
         return p.buf
+
+    def has_planes(self, kind):
+        """Whether the prepared form ``kind`` (wanted before) keeps the bf16 planes of its U4 behind it."""
+        return self.prepared[kind].planes is not None
 
     def refresh_prepared(self, stream):
         """Re-make every form whose stamp fell behind the packed weights as they are now (call after the pack on the same stream)."""
@@ -302,6 +330,9 @@ class PackedBlock:
             if p.stamp is None or p.stamp != self.stamp:
                 make = _PREPARED[kind][2]
                 L.check(getattr(L.lib(), make)(C.byref(p.desc), self.w.data_ptr(), p.buf.data_ptr(), stream), make)
+                if p.planes is not None:         # ... and the planes right after the U4 they come from
+                    L.check(L.lib().yolo_wino4_filter_planes(C.byref(p.desc), p.buf.data_ptr(), p.planes.data_ptr(), stream),
+                            "yolo_wino4_filter_planes")
                 p.stamp = self.stamp
 
     def stale_prepared(self):
@@ -348,8 +379,18 @@ def _wino4_split_flag(state, d, tile_override):
     if not state.wino4_split or state.latency or tile_override:
         return 0
     lib = L.lib()
-    ok = (lib.yolo_conv_wino4_split_supported if state.wino4_split == "all" else lib.yolo_conv_wino4_split_eligible)(C.byref(d))
+    ok = (lib.yolo_conv_wino4_split_eligible if state.wino4_split is True else lib.yolo_conv_wino4_split_supported)(C.byref(d))
     return L.FLAG_WINO_SPLIT_BF16 if ok else 0
+
+
+def _filter_planes_flag(state, pk, kind, d, tile_override):
+    """YOLO_FLAG_FILTER_PLANES for a launch on the prepared filters ``kind``: set wherever the library honours the split and the planes
+    lie behind the U4, whatever ``wino4_split`` says (the flag describes the buffer; the f32 GEMMs ignore it), so that the plan with
+    ``wino4_split = False`` differs from the default one in YOLO_FLAG_WINO_SPLIT_BF16 alone. ``wino4_split = "perlaunch"``: "all"
+    without it, every launch splitting its filters itself (same bits; A/B runs). Never in latency mode or with a forced tile."""
+    if state.wino4_split == "perlaunch" or state.latency or tile_override:
+        return 0
+    return L.FLAG_FILTER_PLANES if L.lib().yolo_conv_wino4_split_supported(C.byref(d)) and pk.has_planes(kind) else 0
 
 
 def _kernel_variant(state, pk, d, op, tile_override):
@@ -365,7 +406,8 @@ def _kernel_variant(state, pk, d, op, tile_override):
     # inference weights stay the same from call to call: the Winograd F(4x4) layers read filters transformed once
     if (wino_shape and (tile_override or 0) in (0, 15) and lib.yolo_conv_workspace_bytes(dp)
             and (d.tile == 15 or lib.yolo_conv_pick_tile(dp) == 15)):
-        return L.FLAG_FILTERS_READY | _wino4_split_flag(state, d, tile_override), pk.want("u4", d).data_ptr()
+        u4 = pk.want("u4", d).data_ptr()
+        return L.FLAG_FILTERS_READY | _wino4_split_flag(state, d, tile_override) | _filter_planes_flag(state, pk, "u4", d, tile_override), u4
     # ... so do the small maps that measured faster as F(4x4) once nothing transforms their filters per launch: the library picks tile
     # 15 for them when the filters lie behind the packed weights, where the block keeps room (wino4_small = False keeps F(2x2))
     if state.wino4_small and not state.latency and not tile_override and wino_shape:
@@ -373,7 +415,8 @@ def _kernel_variant(state, pk, d, op, tile_override):
         probe.flags |= L.FLAG_FILTERS_APPENDED
         if (lib.yolo_conv_pick_tile(C.byref(probe)) == 15 and lib.yolo_conv_workspace_bytes(C.byref(probe)) > 0
                 and pk.want("u4a", d) is not None):
-            return L.FLAG_FILTERS_APPENDED | _wino4_split_flag(state, d, tile_override), pk.w.data_ptr()
+            return (L.FLAG_FILTERS_APPENDED | _wino4_split_flag(state, d, tile_override) | _filter_planes_flag(state, pk, "u4a", d, tile_override),
+                    pk.w.data_ptr())
     # ... and the direct fp32 layers that measured faster that way run as three-way bf16 split products (the library's
     # split3_eligible keeps the list; ModelState.split3 = False keeps the exact-f32 kernels)
     if state.split3 and not tile_override and (lib.yolo_conv_split3_supported if state.split3 == "all" else lib.yolo_conv_split3_eligible)(dp):
@@ -539,7 +582,9 @@ class ModelState:
         # fp32 inference: the Winograd F(4x4) launches on finished filters whose shape measured faster that way run their 36 GEMMs
         # as three-way bf16 split products on planes that the transform pass writes (YOLO_FLAG_WINO_SPLIT_BF16: fp32 accuracy,
         # other bits). False: plans made from then on keep the f32 GEMMs. "all": every launch the library honours the
-        # flag on, measured faster or not (A/B runs, tests).
+        # flag on, measured faster or not (A/B runs, tests). Every such launch reads filter planes made once per weight update
+        # (YOLO_FLAG_FILTER_PLANES, behind the U4 of PackedBlock.want("u4" / "u4a")); "perlaunch": the launches of "all", every one
+        # splitting its filters itself (same bits; A/B runs).
         "wino4_split": (True, False),        # (an A/B setting: written only where it is not the default)
     }
 
