@@ -256,9 +256,33 @@ size_t wino4_split_workspace_bytes(const yolo_conv_desc* d);
 // the tile blocks that stay whole
 int wino4_num_cus();
 int wino4_whole_blocks(int n_mt, int n_nt, int cus);
-// (U_planes: the filter planes made once, yolo_wino4_filter_planes, which the transform pass only reads ahead of the GEMMs; NULL: this
-// launch splits U4 into the workspace behind the V planes)
-int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace, hipStream_t s);
+// The launch geometry of the F(4x4) family (conv_wino4_f32.hip): made once per call from the descriptor; the size queries and the
+// launchers of both GEMM kernels read it and round nothing themselves. Where ok is false only the byte sizes (0) mean anything.
+struct Wino4Geom {
+    bool ok, planes;                         // wino4_supported (T and the grids fit an int); ... and cin % 32 == 0: wino4_split_supported
+    int th, tw;                              // 4 x 4 output tiles down and across one image
+    long long T;                             // tiles: n th tw
+    int Tpad;                                // ... rounded up to the 64 of a tile block
+    int C4, C4p, CoutPad;                    // input channel quads; rounded up to even (the padding plane); cout rounded up to 64
+    int n_mt, n_nt, nkc;                     // tile blocks and channel blocks of 64; chunks of 32 input channels
+    size_t v4_bytes, u4_bytes;               // fp32 workspace: V4 [36][C4p][Tpad][4], U4 [36][C4p][CoutPad][4] behind it
+    size_t v_plane_bytes, u_plane_bytes;     // workspace of bf16 planes (wino4_planes.h): V, U behind it (0 unless planes)
+};
+Wino4Geom wino4_geom(const yolo_conv_desc* d);
+// the U planes of a launch: the caller's, made once (yolo_wino4_filter_planes), or the workspace behind the V planes
+inline const void* wino4_u_planes(const Wino4Geom& g, const void* U_planes, const void* workspace) {
+    return U_planes ? U_planes : static_cast<const char*>(workspace) + g.v_plane_bytes;
+}
+// the kernel arguments of both GEMM kernels (wino4_epilogue.h): everything but V and U, n_whole for the current device; and the grid
+// of the standard block map (8 tile blocks x all channel blocks per row, the whole rows first, each row of tail blocks once per half)
+struct Wino4Args;
+Wino4Args wino4_gemm_args(const Wino4Geom& g, const yolo_conv_desc* d, const float* scale, const float* shift, const void* residual, void* y,
+                          int32_t* nan_flag);
+int wino4_grid(const Wino4Args& a);
+// the transform pass into planes: V into the workspace, U4 into wino4_u_planes unless they are the caller's (U_planes: the filter
+// planes made once, which the transform pass only reads ahead of the GEMMs)
+int wino4_planes_launch(const Wino4Geom& g, const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace,
+                        hipStream_t s);
 int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, const float* scale, const float* shift,
                        const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s);
 // pack_h16.hip (fp32 OIHW weights -> 16-bit MFMA-fragment streams)

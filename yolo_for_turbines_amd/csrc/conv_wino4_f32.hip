@@ -35,7 +35,7 @@
 //                    the waves, so a tile's bits do not depend on the cut.
 #include "split3.h"
 #include "wino4_planes.h"
-#include "wino_dma.h"
+#include "wino4_epilogue.h"
 
 namespace yolo {
 
@@ -47,12 +47,6 @@ __device__ constexpr float W4_BT[6][6] = {
     {0.f, -0.5f, -1.f, 0.5f, 1.f, 0.f},
     {0.f, 2.f, -1.f, -2.f, 1.f, 0.f},
     {0.f, 1.f, 1.5f, -2.f, -1.5f, 1.f},
-};
-__device__ constexpr float W4_AT[4][6] = {
-    {1.f, 1.f, 1.f, 1.f, 1.f, 0.f},
-    {0.f, 1.f, -1.f, 2.f, -0.5f, 0.f},
-    {0.f, 1.f, 1.f, 4.f, 0.25f, 0.f},
-    {0.f, 1.f, -1.f, 8.f, -0.125f, 1.f},
 };
 __device__ constexpr double W4_G[6][3] = {
     {1.0, 0.0, 0.0},
@@ -236,26 +230,10 @@ __global__ __launch_bounds__(256) void wino4_xform_f32(const Wino4XArgs p) {
 }
 
 // ------------------------------------------------------------------------------ 36 GEMMs in six passes + output transform + epilogue
-struct Wino4Args {
-    const float* V;
-    const float* U;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    float* y;
-    int* nan_flag;
-    int T, Tpad, C4p, Cout, CoutPad;
-    int th, tw, H, W;
-    int y_ld, y_off, r_ld, r_off;
-    int flags;
-    int n_mt, n_nt;
-    int n_whole;             // tile blocks 0 .. n_whole - 1 run as one workgroup each, the rest as two workgroups of 32 tiles
-};
-
+// (Wino4Args, the tile table, the fold of a row and the epilogue: wino4_epilogue.h)
 constexpr int W4_STAGE = 24576;          // bytes per ring stage: V [2 planes][6 xi][64][4] floats, then U the same
 constexpr int W4_SLOTS = 4;              // (a power of two: slot arithmetic by mask)
 constexpr int W4_DMA = 3;                // DMA wave-instructions per wave and stage
-constexpr int W4_TAB = 512;              // bytes behind the ring: the epilogue's tile table
 
 // fragments of one sub-step: the U row (A operand) and the V rows of the wave's two tile blocks (B operands)
 template <int OFF>
@@ -290,20 +268,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
     const int wm = cut ? half : wave & 1, wn = cut ? wave & 3 : wave >> 1;
     const bool busy = !cut || wave < 4;
 
-    // the epilogue's table: [64] first output pixel of the tile, [64] valid rows << 4 | columns (0: no such tile, or the other
-    // half's); visible to everybody after the first barrier of the K loop
     int* tab = reinterpret_cast<int*>(smem + W4_SLOTS * W4_STAGE);
-    if (tid < 64) {
-        const int t = mt * 64 + tid;
-        const bool tv = t < p.T && (!cut || (tid >> 5) == half);
-        const int tt = tv ? t : 0;
-        const int per = p.th * p.tw;
-        const int n = tt / per, rem = tt - n * per;
-        const int ty = rem / p.tw, tx = rem - ty * p.tw;
-        const int nr = p.H - 4 * ty < 4 ? p.H - 4 * ty : 4, nc = p.W - 4 * tx < 4 ? p.W - 4 * tx : 4;
-        tab[tid] = (n * p.H + 4 * ty) * p.W + 4 * tx;
-        tab[64 + tid] = tv ? (nr << 4 | nc) : 0;
-    }
+    wino4_tile_table(p, tab, tid, mt, cut, half);
 
     // ---- DMA roles: waves 2 grp, 2 grp + 1 move part grp of a stage (0 / 1: plane 0 / 1 of V, 2 / 3: the same planes of U),
     // three xi each; lane = row
@@ -408,34 +374,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
             if (nst > 2) issue(a + 1, 2, 2);
             __builtin_amdgcn_sched_barrier(0);
         }
-        // row a of M into the output tiles: t[j] = sum_b M[a][b] A^T[j][b], Y[i][j] += A^T[i][a] t[j]
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb) {
-            f32x4 mb[6];
-#pragma unroll
-            for (int b = 0; b < 6; ++b) mb[b] = acc[b][bb];
-            f32x4 t[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                t[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int b = 0; b < 6; ++b)
-                    if (W4_AT[j][b] != 0.f) t[j] += W4_AT[j][b] * mb[b];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (W4_AT[i][a] != 0.f)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) py[bb][i][j] += W4_AT[i][a] * t[j];
-        }
-        // the partial tiles wait out the next pass in the AGPR half of the register file (the accumulators and everything else
-        // of the K loop use the VGPR half: 2 waves per SIMD leave 256 registers per lane in all)
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(py[bb][i][j]));
+        wino4_fold_row<a>(acc, py);
     };
     if (busy) {
         run_pass(std::integral_constant<int, 0>{});
@@ -473,97 +412,29 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_f32(const Wino4Args p) {
         }
     }
 
-    // ------------------------------------------------------------------ epilogue through LDS, one output row i of the tiles at a time
-    // ([pixel j][tile][64 + 4] over the idle ring, 16 lanes per pixel row: stores and residual loads are 256-byte runs)
-    constexpr int OLD = 68;
-    float* ost = reinterpret_cast<float*>(smem);
-    // scale / shift of the 4 channels this thread STORES (4 (tid % 16) .. of the block); requested here, not at kernel start:
-    // eight registers less through the K loops
-    const int c16 = tid & 15;
-    const int co_t = nt * 64 + 4 * c16;
-    const bool cv = co_t < p.Cout;
-    const f32x4 sc_t = *reinterpret_cast<const f32x4*>(p.scale + (cv ? co_t : 0));
-    const f32x4 sh_t = *reinterpret_cast<const f32x4*>(p.shift + (cv ? co_t : 0));
-    // this thread's 8 rows of staged row i: pixel j = it / 2 of tile (tid / 16) + 32 (it % 2), channels 4 (tid % 16) ..
-    auto row_pixels = [&](int i, int (&pix)[8], bool (&pv)[8]) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int tl = (tid >> 4) + 32 * (it & 1), j = it >> 1;
-            const int fl = tab[64 + tl];
-            pv[it] = cv && j < (fl & 15) && i < (fl >> 4);
-            pix[it] = pv[it] ? tab[tl] + i * p.W + j : 0;
-        }
-    };
-    auto request_res = [&](const int (&pix)[8], f32x4 (&rr)[8]) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it)
-            rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
-    };
-    // the residual runs one output row ahead: row 0 is requested before the first staging barrier, row i + 1 once row i has taken
-    // its residual and before it is stored (rr is free again there, so the look-ahead costs no registers; the loads are older
-    // than the stores, so waiting for them does not wait for the stores)
-    f32x4 rr[8];
-    if (RES) {
-        int pix[8];
-        bool pv[8];
-        row_pixels(0, pix, pv);
-        request_res(pix, rr);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    bool saw_nan = false;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i > 0) __syncthreads();                                  // the previous row's staging has been read back
-        if (busy) {
-            float* dst = ost + (32 * wm + l16) * OLD + 16 * wn + 4 * kq;
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(dst + (j * 64 + 16 * bb) * OLD) = py[bb][i][j];
-        }
-        __syncthreads();
-        int pix[8];
-        bool pv[8];
-        row_pixels(i, pix, pv);
-        f32x4 va[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it)
-            va[it] = *reinterpret_cast<const f32x4*>(ost + ((it >> 1) * 64 + (tid >> 4) + 32 * (it & 1)) * OLD + 4 * c16);
-        // all eight values first, then the eight predicated stores (inside a predicated block the compiler waits for
-        // everything in flight)
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) va[it][e] = act_c<ACT>(va[it][e] * sc_t[e] + sh_t[e]);
-            if (RES) va[it] += rr[it];
-            saw_nan |= pv[it] & ((va[it][0] != va[it][0]) | (va[it][1] != va[it][1]) | (va[it][2] != va[it][2]) | (va[it][3] != va[it][3]));
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) asm volatile("" : "+v"(va[it]));
-        if (RES && i < 3) {
-            int npix[8];
-            bool npv[8];
-            row_pixels(i + 1, npix, npv);
-            request_res(npix, rr);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it)
-            if (pv[it]) *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = va[it];
-    }
-    if ((p.flags & YOLO_FLAG_NANCHECK) && saw_nan) atomicOr(p.nan_flag, 2);
+    wino4_epilogue<ACT, RES>(p, smem, tab, py, tid, nt, wm, wn, l16, kq, busy);
 }
 
 // ------------------------------------------------------------------------------ host side
-static long long wino4_tiles(const yolo_conv_desc* d) { return (long long)d->n * ((d->h + 3) / 4) * ((d->w + 3) / 4); }
-
-bool wino4_supported(const yolo_conv_desc* d) {
-    if (!wino_supported(d)) return false;
-    const long long T = wino4_tiles(d);
-    if (T + 64 > 0x7fffffffLL / 4) return false;
-    const long long C4p = (d->cin / 4 + 1) / 2 * 2, ncg = (C4p + 7) / 8;
-    return (T + 63) / 32 * ncg + 1024 <= 0x7fffffffLL;                  // the transform pass's one-dimensional grid
+Wino4Geom wino4_geom(const yolo_conv_desc* d) {
+    Wino4Geom g{};
+    if (!wino_supported(d)) return g;
+    g.th = (d->h + 3) / 4; g.tw = (d->w + 3) / 4; g.T = (long long)d->n * g.th * g.tw;
+    g.C4 = d->cin / 4; g.C4p = round_up(g.C4, 2); g.CoutPad = round_up(d->cout, 64);
+    // four times the padded tiles as an int, and the transform pass's one-dimensional grid
+    g.ok = g.T + 64 <= 0x7fffffffLL / 4 && (g.T + 63) / 32 * ((g.C4p + 7) / 8) + 1024 <= 0x7fffffffLL;
+    if (!g.ok) return g;
+    g.Tpad = round_up((int)g.T, 64); g.n_mt = g.Tpad / 64; g.n_nt = g.CoutPad / 64;
+    g.v4_bytes = (size_t)36 * g.C4p * g.Tpad * 4 * sizeof(float);
+    g.u4_bytes = (size_t)36 * g.C4p * g.CoutPad * 4 * sizeof(float);
+    g.planes = d->cin % 32 == 0; g.nkc = d->cin / 32;
+    if (!g.planes) return g;
+    g.v_plane_bytes = (size_t)36 * g.nkc * g.n_mt * W4S_PIECE;
+    g.u_plane_bytes = (size_t)36 * g.nkc * g.n_nt * W4S_PIECE;
+    return g;
 }
+
+bool wino4_supported(const yolo_conv_desc* d) { return wino4_geom(d).ok; }
 
 // Looks at the layer's shape only, never at the batch size. Measured at batch 32 (tools/conv_bench.py --tile 13,14,15):
 // F(4x4) 252 / 222 / 196 us against F(2x2)'s best 415 / 330 / 270 at 104 x 104, 52 x 52, 26 x 26 (which pads to 28 x 28: 16 % of
@@ -583,13 +454,9 @@ bool wino4_eligible(const yolo_conv_desc* d) {
     return (d->flags & YOLO_FLAG_FILTERS_APPENDED) && wino4_small_channels(d) && d->h == d->w && (d->h == 13 || d->h == 19);
 }
 
-size_t wino4_workspace_bytes(const yolo_conv_desc* d) {
-    if (!wino4_supported(d)) return 0;
-    const size_t C4p = (size_t)(d->cin / 4 + 1) / 2 * 2;
-    const size_t Tpad = (size_t)(wino4_tiles(d) + 63) / 64 * 64;
-    const size_t CoutPad = (size_t)round_up(d->cout, 64);
-    return 36 * C4p * (Tpad + CoutPad) * 4 * sizeof(float);
-}
+// (the byte sizes of a geometry that is not ok are 0)
+size_t wino4_workspace_bytes(const yolo_conv_desc* d) { const Wino4Geom g = wino4_geom(d); return g.v4_bytes + g.u4_bytes; }
+size_t wino4_filter_bytes(const yolo_conv_desc* d) { return wino4_geom(d).u4_bytes; }
 
 // compute units of the current device, asked once per device (0: no device)
 int wino4_num_cus() {
@@ -615,55 +482,48 @@ int wino4_whole_blocks(int n_mt, int n_nt, int cus) {
     return tail == 0 || 2 * tail > cus ? n_mt : whole;
 }
 
-static void wino4_filter_args(Wino4XArgs& xa, const yolo_conv_desc* d, const float* w_rm, float* U) {
-    const int C4p = round_up(d->cin / 4, 2), CoutPad = round_up(d->cout, 64);
-    xa.C4p = C4p;
-    xa.w = w_rm; xa.U = U; xa.cout = d->cout; xa.cin = d->cin; xa.coutp = CoutPad; xa.cinp = cin_pad_of(d->cin); xa.kpad = kpad_of(d->cin, 3);
-    xa.utotal = (long long)C4p * CoutPad * 4;
-}
-static int wino4_filter_blocks(const Wino4XArgs& xa) {
-    const long long ub = (xa.utotal + 255) / 256;
-    return (int)(ub < 1024 ? ub : 1024);
+Wino4Args wino4_gemm_args(const Wino4Geom& g, const yolo_conv_desc* d, const float* scale, const float* shift, const void* residual, void* y,
+                          int32_t* nan_flag) {
+    Wino4Args a;
+    a.V = a.U = nullptr;
+    a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y; a.nan_flag = nan_flag;
+    a.T = (int)g.T; a.Tpad = g.Tpad; a.C4p = g.C4p; a.Cout = d->cout; a.CoutPad = g.CoutPad;
+    a.th = g.th; a.tw = g.tw; a.H = d->h; a.W = d->w;
+    a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
+    a.n_mt = g.n_mt; a.n_nt = g.n_nt;
+    a.n_whole = wino4_whole_blocks(a.n_mt, a.n_nt, wino4_num_cus());
+    return a;
 }
 
-size_t wino4_filter_bytes(const yolo_conv_desc* d) {
-    if (!wino4_supported(d)) return 0;
-    return (size_t)36 * round_up(d->cin / 4, 2) * round_up(d->cout, 64) * 4 * sizeof(float);
+int wino4_grid(const Wino4Args& a) { return 8 * a.n_nt * (ceil_div(a.n_whole, 8) + 2 * ceil_div(a.n_mt - a.n_whole, 8)); }
+
+// the arguments of the transform pass and of the filter kernels (which read the filter side only), all but the four pointers
+static Wino4XArgs wino4_xform_args(const Wino4Geom& g, const yolo_conv_desc* d) {
+    Wino4XArgs xa{};
+    xa.H = d->h; xa.W = d->w; xa.C4 = g.C4; xa.C4p = g.C4p; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
+    xa.th = g.th; xa.tw = g.tw; xa.T = (int)g.T; xa.Tpad = g.Tpad; xa.ncg = ceil_div(g.C4p, 8);
+    xa.nxb = (g.Tpad / 32) * xa.ncg;
+    xa.cout = d->cout; xa.cin = d->cin; xa.coutp = g.CoutPad; xa.cinp = cin_pad_of(d->cin); xa.kpad = kpad_of(d->cin, 3);
+    xa.utotal = (long long)g.C4p * g.CoutPad * 4;
+    return xa;
 }
+// blocks of 256 threads that stride over n elements: at most 1,024 (the grid bound that wino4_geom checked)
+static int wino4_elem_blocks(long long n) { return (int)std::min<long long>((n + 255) / 256, 1024); }
 
 // ---- YOLO_FLAG_WINO_SPLIT_BF16: the transform pass writes bf16 planes (wino4_planes.h) for conv_wino4s_f32.hip
-bool wino4_split_supported(const yolo_conv_desc* d) { return wino4_supported(d) && d->cin % 32 == 0; }
-
-size_t wino4_split_workspace_bytes(const yolo_conv_desc* d) {
-    if (!wino4_split_supported(d)) return 0;
-    const size_t nkc = d->cin / 32, n_mt = (size_t)(wino4_tiles(d) + 63) / 64, n_nt = (size_t)round_up(d->cout, 64) / 64;
-    return 36 * nkc * (n_mt + n_nt) * W4S_PIECE;
-}
-
-size_t wino4_filter_plane_bytes(const yolo_conv_desc* d) {
-    if (!wino4_split_supported(d)) return 0;
-    return (size_t)36 * (d->cin / 32) * (round_up(d->cout, 64) / 64) * W4S_PIECE;
-}
-
-static long long wino4_filter_plane_blocks(const Wino4XArgs& xa) {
-    const long long ub = (9 * xa.utotal + 255) / 256;
-    return ub < 1024 ? ub : 1024;                                     // (the grid bound that wino4_supported checked)
-}
+bool wino4_split_supported(const yolo_conv_desc* d) { return wino4_geom(d).planes; }
+size_t wino4_split_workspace_bytes(const yolo_conv_desc* d) { const Wino4Geom g = wino4_geom(d); return g.v_plane_bytes + g.u_plane_bytes; }
+size_t wino4_filter_plane_bytes(const yolo_conv_desc* d) { return wino4_geom(d).u_plane_bytes; }
 
 // V planes at the start of the workspace, the planes of the caller's finished U4 behind them (made again by this launch), unless the
 // caller keeps them (U_planes: nothing behind the V planes is written; the trailing blocks only read U_planes, wino4_touch_planes)
-int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace, hipStream_t s) {
-    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
-    const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4;
-    Wino4XArgs xa;
-    wino4_filter_args(xa, d, U_planes ? nullptr : U4, nullptr);
-    xa.x = (const float*)x; xa.V = (float*)workspace; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
-    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = C4 / 8;
-    xa.nxb = (Tpad / 32) * xa.ncg;
-    xa.U = U_planes ? const_cast<float*>(static_cast<const float*>(U_planes))
-                    : reinterpret_cast<float*>(static_cast<char*>(workspace) + (size_t)36 * (C4 / 8) * (Tpad / 64) * W4S_PIECE);
-    const long long tb = (xa.utotal * 27 / 8 + 255) / 256;            // blocks that touch 64 bytes per thread once
-    const int nub = (int)(U_planes ? (tb < 1024 ? tb : 1024) : wino4_filter_plane_blocks(xa));
+int wino4_planes_launch(const Wino4Geom& g, const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, void* workspace,
+                        hipStream_t s) {
+    Wino4XArgs xa = wino4_xform_args(g, d);
+    xa.x = (const float*)x; xa.V = (float*)workspace; xa.w = U_planes ? nullptr : U4;
+    xa.U = static_cast<float*>(const_cast<void*>(wino4_u_planes(g, U_planes, workspace)));
+    // trailing blocks: a thread per 64 bytes of the caller's planes to touch, or per quad of the planes to write (36 xi x C4p x coutp)
+    const int nub = wino4_elem_blocks(U_planes ? xa.utotal * 27 / 8 : 9 * xa.utotal);
     hipLaunchKernelGGL(wino4_xform_f32<true>, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
     return check_launch("wino4_xform_f32 (planes)");
 }
@@ -672,34 +532,23 @@ int wino4_planes_launch(const yolo_conv_desc* d, const void* x, const float* U4,
 // filters transformed before (yolo_wino4_filters), or NULL: this launch transforms them into the workspace behind V4
 int conv_wino4_launch(const yolo_conv_desc* d, const void* x, const float* w_rm, const float* U4_ready, const float* scale, const float* shift,
                       const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
-    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4): needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
-    const size_t need = wino4_workspace_bytes(d);
+    const Wino4Geom g = wino4_geom(d);
+    if (!g.ok) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4): needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    const size_t need = g.v4_bytes + g.u4_bytes;
     if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4): workspace %zu < %zu bytes", workspace_bytes, need);
     if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4): workspace must be 16-byte aligned");
     if ((size_t)U4_ready & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4): transformed filters must be 16-byte aligned");
-    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
-    const int T = d->n * th * tw, Tpad = round_up(T, 64), C4 = d->cin / 4, C4p = round_up(C4, 2);
-    const int CoutPad = round_up(d->cout, 64);
     float* V = (float*)workspace;
-    float* U = V + (size_t)36 * C4p * Tpad * 4;
-    Wino4XArgs xa;
-    wino4_filter_args(xa, d, w_rm, U);
-    xa.x = (const float*)x; xa.V = V; xa.H = d->h; xa.W = d->w; xa.C4 = C4; xa.x_ld = d->x_ld; xa.x_off = d->x_off;
-    xa.th = th; xa.tw = tw; xa.T = T; xa.Tpad = Tpad; xa.ncg = ceil_div(C4p, 8);
-    xa.nxb = (Tpad / 32) * xa.ncg;
-    const int nub = U4_ready ? 0 : wino4_filter_blocks(xa);
+    float* U = reinterpret_cast<float*>(static_cast<char*>(workspace) + g.v4_bytes);
+    Wino4XArgs xa = wino4_xform_args(g, d);
+    xa.x = (const float*)x; xa.V = V; xa.w = w_rm; xa.U = U;
+    const int nub = U4_ready ? 0 : wino4_elem_blocks(xa.utotal);
     hipLaunchKernelGGL(wino4_xform_f32<false>, dim3((unsigned)(xa.nxb + nub)), dim3(256), 0, s, xa);
     if (int rc = check_launch("wino4_xform_f32")) return rc;
 
-    Wino4Args a;
-    a.V = V; a.U = U4_ready ? U4_ready : U; a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y;
-    a.nan_flag = nan_flag;
-    a.T = T; a.Tpad = Tpad; a.C4p = C4p; a.Cout = d->cout; a.CoutPad = CoutPad;
-    a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
-    a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
-    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64;
-    a.n_whole = wino4_whole_blocks(a.n_mt, a.n_nt, wino4_num_cus());
-    const int grid = 8 * a.n_nt * (ceil_div(a.n_whole, 8) + 2 * ceil_div(a.n_mt - a.n_whole, 8));
+    Wino4Args a = wino4_gemm_args(g, d, scale, shift, residual, y, nan_flag);
+    a.V = V; a.U = U4_ready ? U4_ready : U;
+    const int grid = wino4_grid(a);
     const bool res = d->flags & YOLO_FLAG_RESIDUAL;
     const size_t lds = (size_t)W4_SLOTS * W4_STAGE + W4_TAB;         // (the epilogue's staging, 256 x 68 x 4, lies over the idle ring)
     auto go = [&](auto kern) -> int {
@@ -729,16 +578,17 @@ int yolo_wino4_appended_wanted(const yolo_conv_desc* d) {
 int yolo_wino4_filters(const yolo_conv_desc* d, const void* w_packed, void* U4, void* stream) {
     using namespace yolo;
     if (!d || !w_packed || !U4) return fail(YOLO_ERR_ARG, "wino4 filters: null pointer");
-    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filters: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    const Wino4Geom g = wino4_geom(d);
+    if (!g.ok) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filters: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
     if ((size_t)U4 & 15) return fail(YOLO_ERR_ARG, "wino4 filters: U4 must be 16-byte aligned");
     // in place (U4 behind the packed weights of the same buffer, YOLO_FLAG_FILTERS_APPENDED) is fine: only the row-major section at
     // the start of w_packed is read. U4 may not begin inside that section
     const char *rm = (const char*)w_packed, *u = (const char*)U4;
     const size_t rm_bytes = (size_t)d->cout * kpad_of(d->cin, 3) * sizeof(float);
-    if (u < rm + rm_bytes && rm < u + wino4_filter_bytes(d)) return fail(YOLO_ERR_ARG, "wino4 filters: U4 overlaps the weights it is made from");
-    Wino4XArgs xa{};
-    wino4_filter_args(xa, d, (const float*)w_packed, (float*)U4);
-    hipLaunchKernelGGL(wino4_filters_f32, dim3((unsigned)wino4_filter_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);
+    if (u < rm + rm_bytes && rm < u + g.u4_bytes) return fail(YOLO_ERR_ARG, "wino4 filters: U4 overlaps the weights it is made from");
+    Wino4XArgs xa = wino4_xform_args(g, d);
+    xa.w = (const float*)w_packed; xa.U = (float*)U4;
+    hipLaunchKernelGGL(wino4_filters_f32, dim3((unsigned)wino4_elem_blocks(xa.utotal)), dim3(256), 0, (hipStream_t)stream, xa);
     return check_launch("wino4_filters_f32");
 }
 
@@ -747,25 +597,26 @@ size_t yolo_wino4_filter_plane_bytes(const yolo_conv_desc* d) { return d ? yolo:
 int yolo_wino4_filter_planes(const yolo_conv_desc* d, const void* U4, void* planes, void* stream) {
     using namespace yolo;
     if (!d || !U4 || !planes) return fail(YOLO_ERR_ARG, "wino4 filter planes: null pointer");
-    if (!wino4_split_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filter planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
+    const Wino4Geom g = wino4_geom(d);
+    if (!g.planes) return fail(YOLO_ERR_UNSUPPORTED, "wino4 filter planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
     if (((size_t)U4 | (size_t)planes) & 15) return fail(YOLO_ERR_ARG, "wino4 filter planes: U4 and planes must be 16-byte aligned");
     const char *u = (const char*)U4, *pl = (const char*)planes;
-    if (pl < u + wino4_filter_bytes(d) && u < pl + wino4_filter_plane_bytes(d)) return fail(YOLO_ERR_ARG, "wino4 filter planes: planes overlap the U4 they are made from");
-    Wino4XArgs xa{};
-    wino4_filter_args(xa, d, (const float*)U4, (float*)planes);
-    hipLaunchKernelGGL(wino4_filter_planes_f32, dim3((unsigned)wino4_filter_plane_blocks(xa)), dim3(256), 0, (hipStream_t)stream, xa);
+    if (pl < u + g.u4_bytes && u < pl + g.u_plane_bytes) return fail(YOLO_ERR_ARG, "wino4 filter planes: planes overlap the U4 they are made from");
+    Wino4XArgs xa = wino4_xform_args(g, d);
+    xa.w = (const float*)U4; xa.U = (float*)planes;
+    hipLaunchKernelGGL(wino4_filter_planes_f32, dim3((unsigned)wino4_elem_blocks(9 * xa.utotal)), dim3(256), 0, (hipStream_t)stream, xa);
     return check_launch("wino4_filter_planes_f32");
 }
 
 int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half) {
     using namespace yolo;
     if (!d || !whole || !half) return fail(YOLO_ERR_ARG, "wino4 blocks: null pointer");
-    if (!wino4_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "wino4 blocks: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
+    const Wino4Geom g = wino4_geom(d);
+    if (!g.ok) return fail(YOLO_ERR_UNSUPPORTED, "wino4 blocks: needs fp32 3x3 stride 1, NHWC output, channels %% 4 == 0");
     const int cus = wino4_num_cus();
     if (cus <= 0) return fail(YOLO_ERR_LAUNCH, "wino4 blocks: no current device");
-    const int n_mt = (int)((wino4_tiles(d) + 63) / 64), n_nt = round_up(d->cout, 64) / 64;
-    *whole = wino4_whole_blocks(n_mt, n_nt, cus);
-    *half = n_mt - *whole;
+    *whole = wino4_whole_blocks(g.n_mt, g.n_nt, cus);
+    *half = g.n_mt - *whole;
     return YOLO_OK;
 }
 

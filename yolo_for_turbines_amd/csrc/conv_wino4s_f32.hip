@@ -295,30 +295,23 @@ bool wino4_split_eligible(const yolo_conv_desc* d) {
 // workspace is left alone), or NULL: this launch makes them there
 int conv_wino4s_launch(const yolo_conv_desc* d, const void* x, const float* U4, const void* U_planes, const float* scale, const float* shift,
                        const void* residual, void* y, void* workspace, size_t workspace_bytes, int32_t* nan_flag, hipStream_t s) {
-    if (!wino4_split_supported(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4) on bf16 planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
-    const size_t need = wino4_split_workspace_bytes(d);
+    const Wino4Geom g = wino4_geom(d);
+    if (!g.planes) return fail(YOLO_ERR_UNSUPPORTED, "conv winograd F(4x4) on bf16 planes: needs fp32 3x3 stride 1, NHWC output, cin %% 32 == 0");
+    const size_t need = g.v_plane_bytes + g.u_plane_bytes;
     if (!workspace || workspace_bytes < need) return fail(YOLO_ERR_WORKSPACE, "conv winograd F(4x4) on bf16 planes: workspace %zu < %zu bytes", workspace_bytes, need);
     if ((size_t)workspace & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: workspace must be 16-byte aligned");
     if (!U4 || ((size_t)U4 & 15)) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: transformed filters must be 16-byte aligned");
     if ((size_t)U_planes & 15) return fail(YOLO_ERR_ARG, "conv winograd F(4x4) on bf16 planes: filter planes must be 16-byte aligned");
-    if (int rc = wino4_planes_launch(d, x, U4, U_planes, workspace, s)) return rc;
+    if (int rc = wino4_planes_launch(g, d, x, U4, U_planes, workspace, s)) return rc;
 
-    const int th = (d->h + 3) / 4, tw = (d->w + 3) / 4;
-    const int T = d->n * th * tw, Tpad = round_up(T, 64), CoutPad = round_up(d->cout, 64);
     Wino4SArgs q;
     Wino4Args& a = q.e;
-    q.nkc = d->cin / 32;
+    a = wino4_gemm_args(g, d, scale, shift, residual, y, nan_flag);
     a.V = (const float*)workspace;
-    a.U = U_planes ? (const float*)U_planes
-                   : reinterpret_cast<const float*>(static_cast<const char*>(workspace) + (size_t)36 * q.nkc * (Tpad / 64) * W4S_PIECE);
-    a.scale = scale; a.shift = shift; a.res = (const float*)residual; a.y = (float*)y; a.nan_flag = nan_flag;
-    a.T = T; a.Tpad = Tpad; a.C4p = d->cin / 4; a.Cout = d->cout; a.CoutPad = CoutPad;
-    a.th = th; a.tw = tw; a.H = d->h; a.W = d->w;
-    a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off; a.flags = d->flags;
-    a.n_mt = Tpad / 64; a.n_nt = CoutPad / 64;
-    a.n_whole = wino4_whole_blocks(a.n_mt, a.n_nt, wino4_num_cus());
+    a.U = (const float*)wino4_u_planes(g, U_planes, workspace);
+    q.nkc = g.nkc;
     q.xmap = a.n_whole == 0 && a.n_mt % 4 == 0 && a.n_nt % 4 == 0 && (a.n_mt / 4) * (a.n_nt / 4) % 8 == 0;
-    const int grid = q.xmap ? 2 * a.n_mt * a.n_nt : 8 * a.n_nt * (ceil_div(a.n_whole, 8) + 2 * ceil_div(a.n_mt - a.n_whole, 8));
+    const int grid = q.xmap ? 2 * a.n_mt * a.n_nt : wino4_grid(a);
     const bool res = d->flags & YOLO_FLAG_RESIDUAL;
     const size_t lds = (size_t)W4S_SLOTS * W4S_STAGE + W4_TAB;       // (the epilogue's staging, 256 x 68 x 4, lies over the idle ring)
     auto go = [&](auto kern) -> int {

@@ -1,9 +1,7 @@
 // wino4_epilogue.h — what a Winograd F(4x4) GEMM kernel does behind its K loop: the arguments, the tile table, the fold of one row
-// of M into the output tiles and the epilogue, as conv_wino4_f32 has them. The C/D layout of v_mfma_f32_16x16x32_bf16 is that of
-// v_mfma_f32_16x16x4_f32, so conv_wino4s_f32.hip (the GEMMs on bf16 planes) hands over the same registers and uses this header.
-// conv_wino4_f32.hip itself keeps its own text of the same code and does not include this file: through these functions the
-// compiler numbers that kernel's scalar registers differently, and its device code is held byte for byte. A change to
-// the epilogue goes into both.
+// of M into the output tiles and the epilogue. The C/D layout of v_mfma_f32_16x16x32_bf16 is that of v_mfma_f32_16x16x4_f32, so
+// conv_wino4_f32.hip (the f32 GEMMs) and conv_wino4s_f32.hip (the GEMMs on bf16 planes) hand over the same registers: the one text
+// of this code for both.
 #pragma once
 #include "wino_dma.h"
 
@@ -107,10 +105,13 @@ __device__ __forceinline__ void wino4_epilogue(const Wino4Args& p, char* smem, c
             pix[it] = pv[it] ? tab[tl] + i * p.W + j : 0;
         }
     };
+    // (one 64-bit base per thread, so that an access costs one multiply-add of its pixel)
+    float* const ybase = p.y + p.y_off + co_t;
+    const float* const rbase = RES ? p.res + p.r_off + (cv ? co_t : 0) : nullptr;
+    const size_t y_ld = (size_t)p.y_ld, r_ld = (size_t)p.r_ld;
     auto request_res = [&](const int (&pix)[8], f32x4 (&rr)[8]) {
 #pragma unroll
-        for (int it = 0; it < 8; ++it)
-            rr[it] = *reinterpret_cast<const f32x4*>(p.res + (size_t)pix[it] * p.r_ld + p.r_off + (cv ? co_t : 0));
+        for (int it = 0; it < 8; ++it) rr[it] = *reinterpret_cast<const f32x4*>(rbase + (size_t)pix[it] * r_ld);
     };
     // the residual runs one output row ahead: row 0 is requested before the first staging barrier, row i + 1 once row i has taken
     // its residual and before it is stored (rr is free again there, so the look-ahead costs no registers; the loads are older
@@ -162,7 +163,7 @@ __device__ __forceinline__ void wino4_epilogue(const Wino4Args& p, char* smem, c
         }
 #pragma unroll
         for (int it = 0; it < 8; ++it)
-            if (pv[it]) *reinterpret_cast<f32x4*>(p.y + (size_t)pix[it] * p.y_ld + p.y_off + co_t) = va[it];
+            if (pv[it]) *reinterpret_cast<f32x4*>(ybase + (size_t)pix[it] * y_ld) = va[it];
     }
     if ((p.flags & YOLO_FLAG_NANCHECK) && saw_nan) atomicOr(p.nan_flag, 2);
 }
