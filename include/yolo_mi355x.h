@@ -710,6 +710,57 @@ int yolo_fuse_boxes(const float* boxes, int b, int n, double iou_threshold, doub
                     int n_views, int conf_type, float* fused, int32_t* members, int32_t* count, int32_t* assign, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- Soft-NMS and NMS options (csrc/nms_soft.hip; nothing of the reference) ---------------------------------------------- */
+/* Suppression that lowers the score of an overlapped box instead of removing it (Soft-NMS, Bodla et al. 2017), with hard removal,
+ * class-agnostic suppression, a cap on detections and a final score threshold on the same walk. This comment is the contract
+ * (DESIGN.md 7.24 has it step by step; tests/soft_nms_ref.py restates it in numpy). All fp32, every operation rounded once (written
+ * fl), no fused multiply-add, IEEE division; a score is compared with obj_threshold or score_threshold in double, as in yolo_nms;
+ * iou_threshold and sigma are used as (float). boxes: (b, n, 6) fp32 rows [x, y, w, h, obj, cls]. Per image:
+ * 1. Candidates. A row is a candidate iff (double) obj > obj_threshold (NaN and equality fail). Its corners and area are the NMS's
+ *    (as for yolo_fuse_boxes), its class the float cls, its current score s = fl(obj + 0.0f) (-0 becomes +0).
+ * 2. Interaction. Two candidates interact iff class_agnostic != 0 or their cls are equal as floats (a NaN class: with nothing).
+ * 3. The walk. The live set is the candidates with (double) s > score_threshold. Repeat: stop if it is empty, or if max_det > 0 and
+ *    max_det rows have been emitted; else the live row of largest s, ties to the lowest input row, is emitted with the score s and
+ *    leaves the live set. (This is "take the candidate of largest score and stop if !((double) s > score_threshold)": scores only
+ *    fall, so a row that fails the comparison once never passes it again; it also says what a NaN score does - it leaves.) For every
+ *    live row j that interacts with the emitted row i: inter = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0) max(min(y2_i, y2_j) -
+ *    max(y1_i, y1_j), 0), iou = inter / (((a_i + a_j) - inter) + 1e-6f), the NMS's expression, then by method
+ *      0 (hard)      !(iou < thr): j leaves the live set
+ *      1 (linear)    iou > thr: s_j = fl(s_j fl(1.0f - iou))
+ *      2 (Gaussian)  s_j = fl(s_j w(fl(fl(iou iou) / sigma))), always
+ *    and for methods 1 and 2 j leaves the live set unless (double) s_j > score_threshold still holds.
+ * 4. w(t) stands for exp(-t), t >= 0, and is this sequence of fp32 operations and nothing else (not the library's expf):
+ *      t is NaN: w = t. kf = rint(fl(t 0x1.715476p+0f)), half to even. kf > 125.0f: w = 0.0f (beyond exp(-87), the underflow point).
+ *      r = fl(fl(t - fl(kf 0x1.63p-1f)) - fl(kf -0x1.bd0106p-13f))                  (ln 2 in two parts; the first product is exact)
+ *      p = -0x1.a01a02p-13f; then p = fl(fl(p r) + c) for c = 0x1.6c16c2p-10f, -0x1.111112p-7f, 0x1.555556p-5f, -0x1.555556p-3f,
+ *      0x1p-1f, -0x1p+0f, 1.0f in turn (the degree-7 Taylor polynomial of exp(-r) by Horner, |r| <= 0.3466: remainder 5e-9)
+ *      w = the float whose bits are bits(p) - ((int) kf << 23)                        (p is in [0.70, 1.42]: w is normal)
+ *    w(0) == 1.0f exactly, 0 <= w <= 1, and |w - exp(-t)| <= 1e-6 exp(-t) wherever w != 0 (tests/test_soft_nms_host.py, against fp64).
+ * 5. Outputs, all fully written by the call. keep_idx (b, n) int32: the emitted rows' input indices in emission order, -1 behind
+ *    them; keep_count (b) int32; scores (b, n) fp32: scores[b][j] the emitted score of keep_idx[b][j], 0.0f behind them.
+ *    rescore_rows: NULL, or a (b, n, 6) buffer - boxes itself is allowed, any other overlap with boxes is not -: column 4 of every
+ *    emitted row receives its emitted score and nothing else is touched.
+ * Scores only fall and the walk takes the maximum, so the emission order is "emitted score descending, ties by input row ascending",
+ * and rows that do not interact evolve independently: the walk runs per class segment in parallel (one workgroup each; per image
+ * if class_agnostic), each segment stops after max_det emissions of its own, and a merge orders the segments' emissions and applies
+ * max_det. With method 0, class_agnostic 0, max_det 0 and score_threshold == obj_threshold the result is the keep list of yolo_nms,
+ * bit for bit. Outside the bit contract, but terminating and in bounds: non-finite coordinates, and negative scores (they would
+ * rise under a decay; a negative obj_threshold itself is accepted as in yolo_nms, and -0 counts as +0).
+ * YOLO_ERR_ARG, with a message, before anything is launched and without needing a device: a null boxes, keep_idx, keep_count or
+ * scores; b or n negative; method outside 0..2; max_det < 0; iou_threshold not finite or not >= 0; obj_threshold or score_threshold
+ * not finite; score_threshold < obj_threshold; for method 2 a sigma that is not finite and > 0 as (float); for n > 0 a workspace
+ * that is NULL, not 16-byte aligned or smaller than yolo_soft_nms_workspace_bytes (HOST ONLY, no GPU needed; 0 outside the limits);
+ * rescore_rows overlapping boxes without being boxes. n <= 163,456 and b <= 2,047 (the class-sorted ordering of yolo_nms), else
+ * YOLO_ERR_UNSUPPORTED. The first yolo_soft_nms_onchip_rows rows of a segment are held in LDS, the others in the workspace.
+ * Everything is stream-ordered, nothing is read back and nothing is allocated: the call can be captured in a graph like
+ * yolo_track_update (after one call outside a capture on that device, which sizes the kernel's LDS). Every workspace byte that is
+ * read was written by the call. */
+int yolo_soft_nms_onchip_rows(void);
+size_t yolo_soft_nms_workspace_bytes(int b, int n);
+int yolo_soft_nms(const float* boxes, int b, int n, double iou_threshold, double obj_threshold, double score_threshold, int center,
+                  int method, double sigma, int class_agnostic, int max_det, int32_t* keep_idx, int32_t* keep_count, float* scores,
+                  float* rescore_rows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- test-time augmentation (csrc/tta.hip; nothing of the reference) ---------------------------------------------------- */
 /* A view of a batch: x_nchw (n, c, h, w) fp32 -> out_nchw (n, c, oh, ow), resized and / or mirrored; not in place.
  * (oh, ow) == (h, w): a mirrored copy, bit-exact. Otherwise bilinear with half-pixel centres and no antialias. Per axis, in double:

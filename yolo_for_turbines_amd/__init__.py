@@ -15,6 +15,9 @@ from .utils import (save_checkpoint, load_checkpoint, accuracy_counts, build_tar
                     fuse_boxes, tta_views, tta_boxes, detect_tta,
                     non_max_suppression)
 from .track import Tracker, TrackResult, track_images
+# Soft-NMS and the NMS options: attributes of the package (yt.soft_nms, yt.NMSOptions) that are deliberately in neither __all__ -
+# utils.py and its name list mirror the reference's utils module and stay as they are; the new names live in boxes.py.
+from .boxes import NMSOptions, soft_nms
 
 __all__ = ["YOLOLoss", "FusedYOLOLoss", "GraphedTrainStep", "SGD", "Adam", "AdamW", "clip_grad_norm_", "GradScaler", "ModelEMA", "CNNBlock", "ResidualBlock", "ScalePredictionBlock", "YOLOv3", "layer_config", "calc_iou",
            "cells_to_boxes", "decode_boxes", "detect", "detect_images", "detect_tiled", "fuse_boxes", "tta_views", "tta_boxes", "detect_tta", "tile_grid", "tile_pyramid", "iou_aligned", "nms_indices", "non_max_suppression", "build_targets", "calc_mAP", "evaluate_detections", "evaluate_model", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes", "augment_params",

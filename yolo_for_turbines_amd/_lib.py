@@ -240,6 +240,10 @@ _SIGS = {
     "yolo_fuse_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_fuse_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_soft_nms_onchip_rows": (C.c_int, []),
+    "yolo_soft_nms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "yolo_soft_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_track_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "yolo_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "yolo_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 """IoU, box decode, NMS, ``detect`` / ``detect_images`` (csrc/decode.hip, nms_*.hip); anchors: in grid cells, of a dataset (anchors.hip)."""
 import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -162,6 +163,102 @@ def nms_indices(boxes, iou_threshold, obj_threshold, box_format="corners"):
     return keep, count
 
 
+NMSOptions = collections.namedtuple("NMSOptions", "method sigma score_threshold class_agnostic max_det",
+                                    defaults=("gaussian", 0.5, None, False, None))
+NMSOptions.__doc__ = """How :func:`soft_nms` (and ``nms=`` of the detect functions) suppresses: ``method`` "hard" | "linear" | "gaussian"
+(Soft-NMS, Bodla et al. 2017: an overlapped box keeps its place and loses score), ``sigma`` of the Gaussian decay ``exp(-iou^2 / sigma)``,
+``score_threshold`` a rescored box must still exceed to be kept (``None``: the ``obj_threshold`` of the call), ``class_agnostic``: boxes
+of different classes suppress each other too, ``max_det``: at most that many detections per image, the best ones (``None``: no cap)."""
+NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}
+
+
+def _nms_options(nms, obj_threshold):
+    """``nms`` (an :class:`NMSOptions` or a dict of its fields) checked, as the arguments of ``yolo_soft_nms``:
+    (method code, sigma, score_threshold, class_agnostic, max_det)."""
+    if isinstance(nms, dict):
+        unknown = sorted(set(nms) - set(NMSOptions._fields))
+        if unknown:
+            raise ValueError(f"unknown NMS option {unknown[0]!r}; the options are {', '.join(NMSOptions._fields)}")
+        nms = NMSOptions(**nms)
+    if not isinstance(nms, NMSOptions):
+        raise ValueError(f"nms must be None, an NMSOptions or a dict of its fields, got {nms!r}")
+    if not isinstance(nms.method, str) or nms.method not in NMS_METHODS:
+        raise ValueError(f"method must be 'hard', 'linear' or 'gaussian', got {nms.method!r}")
+    try:
+        sigma = float(nms.sigma)
+    except (TypeError, ValueError):
+        sigma = math.nan
+    if isinstance(nms.sigma, bool) or not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be a finite number > 0, got {nms.sigma!r}")
+    obj = float(obj_threshold)
+    if not math.isfinite(obj):
+        raise ValueError(f"obj_threshold must be finite, got {obj_threshold!r}")
+    score = obj
+    if nms.score_threshold is not None:
+        try:
+            score = float(nms.score_threshold)
+        except (TypeError, ValueError):
+            score = math.nan
+        if isinstance(nms.score_threshold, bool) or not math.isfinite(score) or score < obj:
+            raise ValueError(f"score_threshold must be None or a finite number >= obj_threshold ({obj}), got {nms.score_threshold!r}")
+    if not isinstance(nms.class_agnostic, bool):
+        raise ValueError(f"class_agnostic must be a bool, got {nms.class_agnostic!r}")
+    max_det = 0
+    if nms.max_det is not None:
+        if isinstance(nms.max_det, bool) or not isinstance(nms.max_det, int) or not 1 <= nms.max_det < 2 ** 31:
+            raise ValueError(f"max_det must be None or an integer >= 1, got {nms.max_det!r}")
+        max_det = nms.max_det
+    return NMS_METHODS[nms.method], sigma, score, int(bool(nms.class_agnostic)), max_det
+
+
+def _soft_nms(boxes, iou_threshold, obj_threshold, box_format, opts, rescore):
+    """``yolo_soft_nms`` on a contiguous (B, N, 6) fp32 CUDA tensor with the checked options of :func:`_nms_options`; ``rescore``:
+    ``None`` or the (B, N, 6) buffer (``boxes`` itself is allowed) whose column 4 receives the kept rows' new scores."""
+    iou = float(iou_threshold)
+    if not (math.isfinite(iou) and iou >= 0):
+        raise ValueError(f"iou_threshold must be a finite number >= 0, got {iou_threshold!r}")
+    method, sigma, score, agnostic, max_det = opts
+    B, N, _ = boxes.shape
+    dev = boxes.device
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        if N == 0 or B == 0:
+            return (torch.full((B, max(N, 1)), -1, dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+                    torch.zeros((B, max(N, 1)), dtype=torch.float32, device=dev))
+        nbytes = lib.yolo_soft_nms_workspace_bytes(B, N)
+        if nbytes == 0:
+            raise ValueError(f"soft_nms takes at most 2,047 images of at most 163,456 boxes, got {B} x {N}")
+        keep = torch.empty((B, N), dtype=torch.int32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+        ws = _workspace(max(nbytes, 256), dev)
+        L.check(lib.yolo_soft_nms(boxes.data_ptr(), B, N, iou, float(obj_threshold), score, int(box_format == "center"), method, sigma,
+                                  agnostic, max_det, keep.data_ptr(), count.data_ptr(), scores.data_ptr(), L.ptr(rescore), ws.data_ptr(),
+                                  ws.numel(), L.current_stream()), "yolo_soft_nms")
+    return keep, count, scores
+
+
+def soft_nms(boxes, iou_threshold, obj_threshold, box_format="corners", **options):
+    """Batched device Soft-NMS (``yolo_soft_nms``; the arithmetic is stated in include/yolo_mi355x.h). ``boxes``: (B, N, 6) or (N, 6)
+    fp32 CUDA tensor of [x,y,w,h,obj,cls], never written. ``options``: the fields of :class:`NMSOptions` (default: Gaussian decay
+    with sigma 0.5). Returns (keep_idx (B,N) int32, keep_count (B,) int32, scores (B,N) fp32): for image b the first
+    ``keep_count[b]`` entries of ``keep_idx`` index its input rows, best rescored objectness first (ties in input order), and
+    ``scores`` holds that objectness; behind them ``keep_idx`` is -1 and ``scores`` 0. ``method="hard"`` with nothing else set
+    keeps exactly what :func:`nms_indices` keeps. No host synchronisation."""
+    if not boxes.is_cuda:
+        raise RuntimeError("soft_nms runs on MI355X only (no CPU fallback)")
+    opts = _nms_options(options, obj_threshold)
+    single = boxes.dim() == 2
+    if single:
+        boxes = boxes.unsqueeze(0)
+    if boxes.dim() != 3 or boxes.shape[-1] != 6:
+        raise ValueError("boxes must be (B, N, 6)")
+    keep, count, scores = _soft_nms(boxes.float().contiguous(), iou_threshold, obj_threshold, box_format, opts, None)
+    if single:
+        return keep[0], count[0], scores[0]
+    return keep, count, scores
+
+
 def non_max_suppression(boxes, iou_threshold, obj_threshold, box_format="corners"):
     """Reference signature (utils.py:150-191): list of [x,y,w,h,obj,cls] lists in, kept boxes
     out (objectness-descending). The list is shipped to the GPU, suppressed there, and the kept
@@ -175,13 +272,17 @@ def non_max_suppression(boxes, iou_threshold, obj_threshold, box_format="corners
     return t[keep[:k].long()].tolist() if k else []
 
 
-def detect(predictions, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, box_format="center", mutate=False):
+def detect(predictions, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, box_format="center", mutate=False, nms=None):
     """Fused post-processing of a forward pass (the sequence of demo.py:44-55 /
     utils.py:300-321, all images at once, nothing leaves HBM):
     decode three scales into one (B, N, 6) buffer in the reference's concatenation order
     (scale 0, 1, 2), then per-image NMS. Returns (boxes (B,N,6), keep_idx (B,N), keep_count (B,)).
     ``mutate=True`` also performs the in-place sigmoid / exp write-back ``cells_to_boxes`` does to the prediction tensors
-    (utils.py:106-110); the reference's callers of this sequence never read them again, so the default leaves them alone."""
+    (utils.py:106-110); the reference's callers of this sequence never read them again, so the default leaves them alone.
+    ``nms``: ``None`` (the reference's suppression, :func:`nms_indices`) or an :class:`NMSOptions` / a dict of its fields: the
+    suppression of :func:`soft_nms`. The return convention is the same (image b keeps ``boxes[b, keep[b, :count[b]]]``, now best
+    rescored objectness first), and column 4 of the kept rows of ``boxes`` holds the rescored objectness."""
+    opts = None if nms is None else _nms_options(nms, obj_threshold)
     B = predictions[0].shape[0]
     n_per = [3 * p.shape[2] * p.shape[3] for p in predictions]
     total = sum(n_per)
@@ -197,20 +298,26 @@ def detect(predictions, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, b
         for p, a, n in zip(predictions, scaled_anchors, n_per):
             decode_boxes(p, a, (p.shape[2], p.shape[3]), True, out=boxes, box_offset=off, mutate=mutate)
             off += n
+    if opts is not None:
+        keep, count, _ = _soft_nms(boxes, iou_threshold, obj_threshold, box_format, opts, boxes)
+        return boxes, keep, count
     keep, count = nms_indices(boxes, iou_threshold, obj_threshold, box_format)
     return boxes, keep, count
 
 
-def detect_images(model, x, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, box_format="center"):
+def detect_images(model, x, scaled_anchors, iou_threshold=0.45, obj_threshold=0.5, box_format="center", nms=None):
     """``detect(model(x), ...)`` with ONE host synchronisation instead of two back to back: the forward's NaN guards
     (model.py:175,183-184) are read after decode and NMS have been enqueued, so the GPU does not sit idle between the
     forward and the post-processing while the host wakes up and launches them (~0.1-0.25 ms per batch). Same results, same
-    exceptions (``AssertionError`` for a NaN input, ``ValueError("Nan in layer")``), raised before anything is returned."""
+    exceptions (``AssertionError`` for a NaN input, ``ValueError("Nan in layer")``), raised before anything is returned.
+    ``nms``: as for :func:`detect`."""
+    if nms is not None:
+        _nms_options(nms, obj_threshold)                  # a bad option is reported before the forward runs
     eng = model._engine
     with eng.deferred_nan(), torch.no_grad():
         preds = model(x)
         flag = eng.take_pending_flag()
-    out = detect(preds, scaled_anchors, iou_threshold, obj_threshold, box_format)
+    out = detect(preds, scaled_anchors, iou_threshold, obj_threshold, box_format, nms=nms)
     if flag is not None:
         eng.raise_on_nan(flag)
     return out

@@ -26,29 +26,12 @@ namespace yolo {
 
 constexpr int FUSE_ONCHIP = 1024;        // clusters of one segment held in LDS (52 bytes each: 52 KiB per wave, three waves per CU)
 constexpr int FUSE_CHUNK = 64;           // candidates per prefetch chunk: one per lane
-constexpr int FUSE_BUCKETS = 4095;       // class_bucket() values: 0 .. 4093 and the lump 4094
+constexpr int FUSE_BUCKETS = CLASS_BUCKETS;
 constexpr int FUSE_WAVES = 128;          // walk waves per image (class-aware): wave x takes buckets x, x + 128, ...
 constexpr int FUSE_MAX_N = 163456;       // the n up to which yolo_nms orders class-sorted (nms_host.hip): at most 80 chunks of SC keys
 static_assert(FUSE_MAX_N <= SC * 80 && FUSE_MAX_N < (1 << 20), "the ordering's chunk count and the 20-bit index fields");
 
 struct FuseCand { float x1, y1, x2, y2, a, cls, s; int g; };
-
-// ---- segments: seg[b][bucket] = {first row, one past the last row} of the bucket's run in order 2 (zeroed before: empty)
-__global__ __launch_bounds__(256) void fuse_segments_kernel(const unsigned long long* __restrict__ sorted2, const int* __restrict__ nvalid, int n,
-                                                            int agnostic, int* __restrict__ seg) {
-    const int b = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
-    const int nv = nvalid[b];
-    if (q >= nv) return;
-    int* sg = seg + (size_t)b * FUSE_BUCKETS * 2;
-    if (agnostic) {
-        if (q == 0) { sg[0] = 0; sg[1] = nv; }
-        return;
-    }
-    const unsigned long long* s = sorted2 + (size_t)b * n;
-    const unsigned bucket = (unsigned)((s[q] >> 40) & 0xfffull);
-    if (q == 0 || (unsigned)((s[q - 1] >> 40) & 0xfffull) != bucket) sg[bucket * 2] = q;
-    if (q == nv - 1 || (unsigned)((s[q + 1] >> 40) & 0xfffull) != bucket) sg[bucket * 2 + 1] = q + 1;
-}
 
 // bare v_max / v_min: fmaxf() makes the compiler canonicalise both operands first (nms_mask.hip)
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -340,7 +323,7 @@ int yolo_fuse_boxes(const float* boxes, int b, int n, double iou_threshold, doub
         return rc;
     const unsigned long long* order = agnostic ? w.sorted1 : w.sorted2;
     const dim3 gn(ceil_div(n, 256), b);
-    hipLaunchKernelGGL(fuse_segments_kernel, gn, dim3(256), 0, st, w.sorted2, w.nvalid, n, agnostic, w.seg);
+    if (int rc = nms_class_segments(w.sorted2, w.nvalid, b, n, agnostic, w.seg, st)) return rc;
     hipLaunchKernelGGL(fuse_walk_kernel, dim3(agnostic ? 1 : FUSE_WAVES, b), dim3(64), 0, st, boxes, order, w.seg, n, center ? 1 : 0, agnostic,
                        (float)iou_threshold, n_views, conf_type, w.sp, w.crec, w.ckey, w.joined);
     if (int rc = check_launch("fuse walk")) return rc;

@@ -5,6 +5,7 @@
 //   nms_mask.hip   the 64-bit suppression words (plain and class-sorted)
 //   nms_scan.hip   the greedy pass over the words (plain and per class range)
 //   nms_host.hip   workspace, routing (the table is there), yolo_nms
+//   nms_soft.hip   yolo_soft_nms: the rescoring walk (Soft-NMS) on the candidates nms_order.hip ordered; neither mask nor scan
 // Kernels are launched from the unit that defines them (no relocatable device code).
 #pragma once
 #include "common.h"
@@ -37,6 +38,7 @@ __device__ __forceinline__ unsigned long long make_key(float score, int idx, dou
 // atomics per call were most of this kernel's 30 us).
 __device__ __forceinline__ bool key_valid(unsigned long long k) { return ((k >> 20) & 0xffffffffull) != 0xffffffffull; }
 
+constexpr int CLASS_BUCKETS = 4095;      // class_bucket() values: 0 .. 4093 and the lump 4094
 __device__ __forceinline__ unsigned class_bucket(float c) {   // equal float classes -> equal bucket; ascending-sortable
     return (c >= 0.0f && c < 4094.0f && c == floorf(c)) ? (unsigned)c : 4094u;
 }
@@ -69,6 +71,9 @@ int nms_order_library_sort(const float* boxes, int b, int n, double obj_thr, int
 int nms_order_class_sorted(const float* boxes, int b, int n, int W, double obj_thr, int center, unsigned long long* chunked, int* chunk_valid,
                            unsigned long long* sorted1, unsigned long long* sorted2, int* nvalid, unsigned long long* row_any, int* grank,
                            SBox* sbox, int* blk_lo, int* blk_hi, hipStream_t st);
+// the class segments of order 2, for the walks that go class by class (fuse.hip, nms_soft.hip): seg[b][bucket] = {first row, one past
+// the last row} of the bucket's run in sorted2, for agnostic != 0 seg[b][0] = {0, nvalid[b]}; seg (b, CLASS_BUCKETS, 2) zeroed before
+int nms_class_segments(const unsigned long long* sorted2, const int* nvalid, int b, int n, int agnostic, int* seg, hipStream_t st);
 // nms_mask.hip: mask[b][i][cb], and row_any[b][rb] ORed (zeroed before)
 int nms_mask_plain(const SBox* sbox, const int* nvalid, int b, int n, int W, float thr, unsigned long long* mask, unsigned long long* row_any,
                    hipStream_t st);

@@ -236,6 +236,23 @@ __global__ __launch_bounds__(256) void nms_merge2_kernel(const float* __restrict
     if ((q & 63) == 63 || q == nv - 1) blk_hi[(size_t)b * W + (q >> 6)] = cls;
 }
 
+// ---- segments: seg[b][bucket] = {first row, one past the last row} of the bucket's run in order 2 (zeroed before: empty)
+__global__ __launch_bounds__(256) void nms_segments_kernel(const unsigned long long* __restrict__ sorted2, const int* __restrict__ nvalid, int n,
+                                                            int agnostic, int* __restrict__ seg) {
+    const int b = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    const int nv = nvalid[b];
+    if (q >= nv) return;
+    int* sg = seg + (size_t)b * CLASS_BUCKETS * 2;
+    if (agnostic) {
+        if (q == 0) { sg[0] = 0; sg[1] = nv; }
+        return;
+    }
+    const unsigned long long* s = sorted2 + (size_t)b * n;
+    const unsigned bucket = (unsigned)((s[q] >> 40) & 0xfffull);
+    if (q == 0 || (unsigned)((s[q - 1] >> 40) & 0xfffull) != bucket) sg[bucket * 2] = q;
+    if (q == nv - 1 || (unsigned)((s[q + 1] >> 40) & 0xfffull) != bucket) sg[bucket * 2 + 1] = q + 1;
+}
+
 // ---- the same two launches as a stand-alone ascending sort of UNIQUE 64-bit keys (none equal to ~0): the orderings of
 // calc_mAP (utils.py:206,232: detections by class and descending objectness, ground truths by class and image - Python's
 // stable sorts become one sort of (major | minor | original index) keys)
@@ -319,6 +336,11 @@ int nms_order_class_sorted(const float* boxes, int b, int n, int W, double obj_t
                            sbox, blk_lo, blk_hi);
     });
     return check_launch("nms order 2");
+}
+
+int nms_class_segments(const unsigned long long* sorted2, const int* nvalid, int b, int n, int agnostic, int* seg, hipStream_t st) {
+    hipLaunchKernelGGL(nms_segments_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, st, sorted2, nvalid, n, agnostic, seg);
+    return check_launch("nms class segments");
 }
 
 }  // namespace yolo

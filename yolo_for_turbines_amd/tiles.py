@@ -5,7 +5,7 @@ import math
 import torch
 
 from . import _lib as L
-from .boxes import _anchors_to_device, _decode3, _grid_hw, _workspace, nms_indices
+from .boxes import _anchors_to_device, _decode3, _grid_hw, _nms_options, _soft_nms, _workspace, nms_indices
 
 
 def _tile_hw(tile):
@@ -82,7 +82,7 @@ def tile_pyramid(h, w, tile=416, overlap=0.2, scales=(1.0,)):
 
 
 def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_threshold=0.45, obj_threshold=0.5, box_format="center",
-                 batch=32, max_candidates=65536, scales=(1.0,), edge_margin=None):
+                 batch=32, max_candidates=65536, scales=(1.0,), edge_margin=None, nms=None):
     """Detection on frames that are larger than the network input: every frame is cut into overlapping tiles
     (:func:`tile_grid`), the tiles of all frames run through ``model(x)`` in chunks of ``batch``, the decoded boxes
     above ``obj_threshold`` are mapped back to their frame and compacted on the device (``yolo_tile_collect``), and one
@@ -101,6 +101,9 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
     the truncated copy of an object that a neighbouring tile or a coarser level reports whole, and its IoU with the whole box
     is too low for the NMS to remove it. An object is lost if every tile of every level cuts it, so use it with an overlap
     larger than the objects of the finest level or with a coarser level.
+    ``nms``: ``None`` (the hard NMS) or an :class:`NMSOptions` / a dict of its fields: the frame's candidates go through
+    :func:`soft_nms` instead, and column 4 of the kept rows of ``boxes`` holds the rescored objectness. The Gaussian decay has no
+    threshold: a truncated copy along a seam loses score in proportion to its overlap with the whole box.
 
     Returns ``(boxes (F, max_candidates, 6), keep (F, max_candidates) int32, count (F,) int32, candidates (F,) int32)``:
     ``boxes[f, :candidates[f]]`` are frame f's candidates ``[cx, cy, w, h, obj, cls]`` normalised to that frame, in (level, tile,
@@ -117,6 +120,7 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
     oh, ow = _overlap_px(overlap, th, tw)
     if not float(obj_threshold) >= 0:
         raise ValueError(f"obj_threshold must be >= 0 (the zero rows behind the candidates must not pass it), got {obj_threshold}")
+    opts = None if nms is None else _nms_options(nms, obj_threshold)
     batch, cap = int(batch), int(max_candidates)
     if batch < 1 or cap < 1:
         raise ValueError(f"batch and max_candidates must be >= 1, got {batch} and {cap}")
@@ -219,7 +223,10 @@ def detect_tiled(model, images, scaled_anchors, tile=416, overlap=0.2, iou_thres
                                                      tail.data_ptr(), ws.data_ptr(), ws.numel(), stream), "yolo_tile_collect_ex")
         for t in frames:
             t.record_stream(torch.cuda.current_stream())
-        keep, count = nms_indices(cand, iou_threshold, obj_threshold, box_format)
+        if opts is not None:
+            keep, count, _ = _soft_nms(cand, iou_threshold, obj_threshold, box_format, opts, cand)
+        else:
+            keep, count = nms_indices(cand, iou_threshold, obj_threshold, box_format)
         tail_host = tail.tolist()                                   # the one host synchronisation
     eng.raise_on_flags(tail_host[F:])
     for f in range(F):

@@ -9,7 +9,7 @@ import math
 import torch
 
 from . import _lib as L
-from .boxes import detect
+from .boxes import _nms_options, detect
 
 __all__ = ["Tracker", "TrackResult", "track_images"]
 
@@ -169,19 +169,24 @@ class Tracker:
         return TrackResult(out_boxes, out_ids, out_count, det_ids)
 
 
-def track_images(model, x, scaled_anchors, tracker, iou_threshold=0.45):
+def track_images(model, x, scaled_anchors, tracker, iou_threshold=0.45, nms=None):
     """One frame per stream from pixels to tracks: :func:`detect_images` with ``obj_threshold = tracker.low_threshold`` (so the low
     detections survive the NMS for the tracker's second matching), then :meth:`Tracker.update` on its (boxes, keep, count). One
-    host synchronisation, the forward's NaN guard, after everything is enqueued. Returns ``(TrackResult, boxes, keep, count)``."""
+    host synchronisation, the forward's NaN guard, after everything is enqueued. Returns ``(TrackResult, boxes, keep, count)``.
+    ``nms``: as for :func:`detect`; its ``score_threshold`` defaults to ``tracker.low_threshold`` too. With Soft-NMS an overlapped
+    detection reaches the tracker with its lowered objectness instead of being removed: a box behind a confident one falls from
+    HIGH to LOW and is offered to the second matching."""
     if not isinstance(tracker, Tracker):
         raise ValueError("tracker must be a Tracker")
     if tracker.box_format != "center":
         raise ValueError("track_images decodes centre-format boxes: the tracker must have box_format='center'")
+    if nms is not None:
+        _nms_options(nms, tracker.low_threshold)          # a bad option is reported before the forward runs
     eng = model._engine
     with eng.deferred_nan(), torch.no_grad():
         preds = model(x)
         flag = eng.take_pending_flag()
-    boxes, keep, count = detect(preds, scaled_anchors, iou_threshold, tracker.low_threshold, "center")
+    boxes, keep, count = detect(preds, scaled_anchors, iou_threshold, tracker.low_threshold, "center", nms=nms)
     res = tracker.update(boxes, keep, count)
     if flag is not None:
         eng.raise_on_nan(flag)
