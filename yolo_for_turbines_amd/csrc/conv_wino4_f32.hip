@@ -126,9 +126,10 @@ __device__ __forceinline__ void wino4_filter_planes(const Wino4XArgs& p, long lo
 }
 
 // Filter planes made once (YOLO_FLAG_FILTER_PLANES) lie in HBM when their layer's turn comes: a forward reads more filter bytes than
-// the caches hold. conv_wino4s_f32 requests a stage three stages ahead, which covers the memory-side cache but not HBM (measured in
-// the forward, DESIGN 4.15: 151 against 114 us at 26 x 26). So the blocks behind the input transform read the planes once, one dword
-// per 64 bytes, while the input is transformed: p.U points at them, element i = 64 bytes
+// the caches hold. conv_wino4s_f32 requested a stage three stages ahead, which covered the memory-side cache but not HBM (measured in
+// the forward, DESIGN 4.15: 151 against 114 us at 26 x 26); it now requests five ahead and the forward without these reads is still
+// 0.4 ms slower. So the blocks behind the input transform read the planes once, one dword per 64 bytes, while the
+// input is transformed: p.U points at them, element i = 64 bytes
 __device__ __forceinline__ void wino4_touch_planes(const Wino4XArgs& p, long long first, long long stride) {
     const char* pl = reinterpret_cast<const char*>(p.U);
     const long long n = p.utotal * 27 / 8;                           // 36 xi x 6 bytes x utotal / 64

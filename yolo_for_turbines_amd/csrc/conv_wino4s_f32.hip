@@ -15,11 +15,17 @@
 //   stage    one xi x 32 input channels: the 12 KiB piece of V (3 planes x 64 tiles x 64 bytes), then the 12 KiB piece of U. Both are
 //            contiguous in global memory and byte for byte the LDS image: 24 LDS-DMA wave-instructions of 1 KiB, three per wave
 //            (waves 0 - 3 move V, 4 - 7 move U). Stages run xi-fastest inside a pass: g = 6 chunk + x.
-//   ring     four slots of 24 KiB. Stage g + 3 is requested during stage g into the slot of stage g - 1.
-//   step g   wait for the own pieces of stage g + 1 (vmcnt), barrier: stage g + 1 is in LDS for everybody, and everybody has read
-//            stage g - 1 out of its slot. Then: request one piece of stage g + 3 behind each of the first MFMA pairs, read the nine
-//            fragments of stage g + 1 (3 U + 2 x 3 V, ds_read_b128, into the other fragment set), wait for those of stage g
-//            (lgkmcnt(9)), twelve MFMAs.
+//   ring     six slots of 24 KiB, one ring for the whole kernel: the stages are numbered through the six passes (a pass is a whole
+//            number of laps, so the slot of a stage is its xi mod 6, a compile-time constant of the unrolled loop). Stage g + 5 is
+//            requested during stage g into the slot of stage g - 1, across the pass boundaries too: the ring drains once, in the
+//            last lap of pass 5, and up to 120 KiB per CU are in flight.
+//   step g   wait for the own pieces of stage g + 1 (vmcnt: the pieces of stages g + 2 .. g + 4 are younger), barrier: stage g + 1 is
+//            in LDS for everybody, and everybody has read stage g - 1 out of its slot. Then: request one piece of stage g + 5 behind
+//            each of the first MFMA pairs, read the nine fragments of stage g + 1 (3 U + 2 x 3 V, ds_read_b128, into the other
+//            fragment set), wait for those of stage g (lgkmcnt(9)), twelve MFMAs.
+//   pass end the fold (wino4_fold_row) runs with five stages in flight. The fragments of the next pass's stage 0, which the last
+//            step has read, are dropped and read again behind the fold: no barrier is needed for that (stage 0 landed behind the
+//            last step's barrier), and the fold keeps its registers.
 // One workgroup per CU and round; the tile blocks of a short last round run as two workgroups of 32 tiles each (wino4_whole_blocks, the
 // cut of conv_wino4_f32), and such a half workgroup requests only its own 32 rows of the V piece: 18 KiB per stage instead of 24.
 #include "split3.h"
@@ -35,8 +41,10 @@ struct Wino4SArgs {
 };
 
 constexpr int W4S_STAGE = 2 * W4S_PIECE; // bytes per ring stage: the V piece, then the U piece
-constexpr int W4S_SLOTS = 4;             // (a power of two: slot arithmetic by mask)
+constexpr int W4S_SLOTS = 6;             // one lap of the ring is the six xi of a chunk: stage g sits in slot g % 6 = its xi
+constexpr int W4S_AHEAD = W4S_SLOTS - 1; // stage g + 5 is requested during stage g
 constexpr int W4S_DMA = 3;               // DMA wave-instructions per wave and stage
+static_assert(W4S_SLOTS == 6 && W4S_AHEAD == 5, "the slot of a stage is its xi, and the counted waits of the last lap are written out for five stages ahead");
 
 template <int OFF>
 __device__ __forceinline__ void w4s_read_at(s3_u32x4& f, unsigned addr) {
@@ -92,11 +100,11 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
     const unsigned lds0 = (unsigned)(size_t)(wn_lptr)smem;
     const unsigned ldsw = lds0 + own;
     const int nkc = q.nkc;
-    auto issue_piece = [&](int k, int pass, int g, int slot) {               // stage g = 6 chunk + x of the pass
-        const int kc = g / 6, x = g - 6 * kc;
-        wn_glds16_s(src + ((size_t)(6 * pass + x) * nkc + kc) * s_st + k * 1024, lane16, ldsw + slot * W4S_STAGE + k * 1024);
+    // piece k of stage (pass, chunk kc, xi x) into slot x; kc == nkc names chunk 0 of the next pass (the ring runs on across passes)
+    auto issue_piece = [&](int k, int pass, int kc, int x) {
+        const int xi = kc < nkc ? 6 * pass + x : 6 * pass + 6 + x, c = kc < nkc ? kc : 0;
+        wn_glds16_s(src + ((size_t)xi * nkc + c) * s_st + k * 1024, lane16, ldsw + x * W4S_STAGE + k * 1024);
     };
-    auto issue = [&](int pass, int g, int slot) { wn_for<0, W4S_DMA>([&](auto K) { issue_piece(decltype(K)::value, pass, g, slot); }); };
 
     // ---- fragment addresses in slot 0: rows 32 wm + l16 (+ 16) of the V planes, row 16 wn + l16 of the U planes, channels 8 kq ..
     const unsigned sw = w4s_slot(l16, kq) * 16;          // (blocks start at multiples of 16 rows: the row quad is l16's)
@@ -138,10 +146,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
             c[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, __builtin_bit_cast(s3_bf16x8, v[0]), c[0], 0, 0, 0);
             c[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, __builtin_bit_cast(s3_bf16x8, v[1]), c[1], 0, 0, 0);
         };
-        if constexpr (a == 0) {              // (the first stages of passes 1 .. 5 are requested before the previous pass's fold)
-            issue(0, 0, 0);
-            issue(0, 1, 1);
-            issue(0, 2, 2);
+        if constexpr (a == 0) {              // (the first stages of passes 1 .. 5 are requested by the last stages of the pass before)
+            wn_for<0, W4S_AHEAD>([&](auto X) { wn_for<0, W4S_DMA>([&](auto K) { issue_piece(decltype(K)::value, 0, 0, decltype(X)::value); }); });
         }
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc[6][2];
@@ -152,8 +158,12 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
 #pragma unroll
         for (int x = 0; x < 6; ++x) asm volatile("" : "+v"(acc[x][0]), "+v"(acc[x][1]));
         __builtin_amdgcn_sched_barrier(0);
-        wn_wait_vmcnt<2 * W4S_DMA>();                    // stage 0 has landed (mine), ...
-        __builtin_amdgcn_s_barrier();                    // ... everybody's
+        if constexpr (a == 0) {
+            wn_wait_vmcnt<(W4S_AHEAD - 1) * W4S_DMA>();  // stage 0 has landed (mine; stages 1 .. 4 are younger), ...
+            __builtin_amdgcn_s_barrier();                // ... everybody's
+        }
+        // (stage 0 of passes 1 .. 5 is stage g + 1 of the last step of the pass before: it landed behind that step's barrier, and its
+        // slot is written again only behind the barrier of step 1 of this pass)
         __builtin_amdgcn_sched_barrier(0);
         rd_hi(std::integral_constant<int, 0>{}, 0u);     // the order R1 .. R5 in which every stage requests the next one's
         rd_vlo(0u);
@@ -165,21 +175,27 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
             const bool more = kc + 1 < nkc;              // another chunk behind this one
             wn_for<0, 6>([&](auto X) {
                 constexpr int x = decltype(X)::value, set = x & 1;       // (6 is even: the hi set of stage g is x & 1)
-                const int g = 6 * kc + x;
-                const bool next = x < 5 || more;         // stage g + 1 exists
-                const bool ahead = x < 3 || more;        // stage g + 3 exists: it goes into the slot of stage g - 1
-                const unsigned nb = (unsigned)((g + 1) & (W4S_SLOTS - 1)) * W4S_STAGE;
-                const int as = (g + 3) & (W4S_SLOTS - 1);
+                // Stages are numbered through the six passes, g = 6 (a nkc + kc) + x, and the ring never drains between them.
+                const bool on = a < 5 || more;           // not the last lap of the kernel: every stage up to g + 6 - x exists
+                const bool next = x < 5 || on;           // stage g + 1 exists
+                const bool ahead = x < 1 || on;          // stage g + 5 exists: it goes into slot (x + 5) % 6, the slot of stage g - 1
+                constexpr int ax = (x + W4S_AHEAD) % W4S_SLOTS;
+                const int akc = x < 1 ? kc : kc + 1;     // its chunk (nkc: chunk 0 of pass a + 1)
+                unsigned nb = (unsigned)((x + 1) % W4S_SLOTS) * W4S_STAGE;
+                asm volatile("" : "+s"(nb));             // (added per stage: twelve fragment bases kept in registers would not fit)
                 __builtin_amdgcn_sched_barrier(0);
                 // The six products (U part, V part), smallest terms first, the order of conv_split3_f32. The waits count the reads
                 // requested behind the ones a product needs (LDS reads return in order): R3 R4 R5 of the stage before and R1 behind
-                // R2 = 7, and so on. The last stage of a pass reads the same way, from a slot that nothing is written to any
-                // more, into registers that nothing uses: no branch around the reads, one count for every stage.
+                // R2 = 7, and so on. The last stage of a pass reads the same way, into registers that nothing uses (stage 0 of the
+                // next pass, which that pass reads again; after pass 5 a slot that nothing is written to any more): no branch
+                // around the reads, one count for every stage.
                 if (next) {
-                    // stage g + 1 has to be in LDS for everybody before its fragments are read (the only requests younger than its
-                    // pieces are those of stage g + 2); the slot of stage g - 1 is free once everybody is here
-                    if (x < 4 || more) wn_wait_vmcnt<W4S_DMA>();
-                    else wn_wait_vmcnt<0>();
+                    // stage g + 1 has to be in LDS for everybody before its fragments are read (the requests younger than its pieces
+                    // are those of stages g + 2 .. g + 4; stage g + 5 is requested below); the slot of stage g - 1 is free once
+                    // everybody is here. In the last lap of the kernel stages g + 2 .. exist only up to xi 5: 3, 3, 2, 1, 0.
+                    constexpr int young = x < 2 ? W4S_AHEAD - 2 : x < 4 ? 4 - x : 0;
+                    if (on) wn_wait_vmcnt<(W4S_AHEAD - 2) * W4S_DMA>();
+                    else wn_wait_vmcnt<young * W4S_DMA>();
                     __builtin_amdgcn_s_barrier();
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -187,19 +203,19 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
                 asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(uh[set]), "+v"(vl[0]), "+v"(vl[1]));
                 mma(acc[x], uh[set], vl);                // hi lo
                 __builtin_amdgcn_sched_barrier(0);
-                if (ahead) issue_piece(0, a, g + 3, as);
+                if (ahead) issue_piece(0, a, akc, ax);
                 rd_vlo(nb);
                 asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(ul), "+v"(vh[set][0]), "+v"(vh[set][1]));
                 __builtin_amdgcn_sched_barrier(0);
                 mma(acc[x], ul, vh[set]);                // lo hi
                 __builtin_amdgcn_sched_barrier(0);
-                if (ahead) issue_piece(1, a, g + 3, as);
+                if (ahead) issue_piece(1, a, akc, ax);
                 rd_ulo(nb);
                 asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(um), "+v"(vm[0]), "+v"(vm[1]));
                 __builtin_amdgcn_sched_barrier(0);
                 mma(acc[x], um, vm);                     // mid mid
                 __builtin_amdgcn_sched_barrier(0);
-                if (ahead) issue_piece(2, a, g + 3, as);
+                if (ahead) issue_piece(2, a, akc, ax);
                 __builtin_amdgcn_sched_barrier(0);
                 mma(acc[x], uh[set], vm);                // hi mid
                 __builtin_amdgcn_sched_barrier(0);
@@ -212,14 +228,11 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
                 mma(acc[x], uh[set], vh[set]);           // hi hi
             });
         }
+        // The accumulators' last operands have arrived, and so have the reads of the last step: after passes 0 .. 4 those are the
+        // fragments of the next pass's stage 0, which that pass reads again behind the fold (36 registers the fold has no room for).
+        // The ring runs on: stages 0 .. 4 of the next pass are in flight during the fold below.
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                     // everybody is done with the ring: the next pass's first stages / the staging may overwrite it
-        if constexpr (a < 5) {                               // ... and they are requested now: in flight during the fold below
-            issue(a + 1, 0, 0);
-            issue(a + 1, 1, 1);
-            issue(a + 1, 2, 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        if constexpr (a == 5) __syncthreads();               // everybody is done with the ring: the staging may overwrite it
         wino4_fold_row<a>(acc, py);
     };
     if (busy) {
@@ -234,55 +247,56 @@ __global__ __launch_bounds__(512, 1) void conv_wino4s_f32(const Wino4SArgs q) {
         // the barriers of run_pass, in the same places
         constexpr int HD = 2;
         const bool mover = wave < 7;
-        auto issue_half = [&](int pass, int g, int slot) {
+        auto issue_half = [&](int pass, int kc, int x) {
             if (mover) {
-                issue_piece(0, pass, g, slot);
-                issue_piece(1, pass, g, slot);
+                issue_piece(0, pass, kc, x);
+                issue_piece(1, pass, kc, x);
             }
         };
-        const int ng = 6 * nkc;
-        for (int a = 0; a < 6; ++a) {
-            if (a == 0) {
-                issue_half(0, 0, 0);
-                issue_half(0, 1, 1);
-                issue_half(0, 2, 2);
-            }
-            wn_wait_vmcnt<2 * HD>();
-            __builtin_amdgcn_s_barrier();
-            for (int g = 0; g < ng; ++g) {
-                if (g + 1 < ng) {                            // (run_pass: next)
-                    if (g + 2 < ng) wn_wait_vmcnt<HD>();
-                    else wn_wait_vmcnt<0>();
-                    __builtin_amdgcn_s_barrier();
+        for (int x = 0; x < W4S_AHEAD; ++x) issue_half(0, 0, x);
+        wn_wait_vmcnt<(W4S_AHEAD - 1) * HD>();
+        __builtin_amdgcn_s_barrier();
+        for (int a = 0; a < 6; ++a)
+            for (int kc = 0; kc < nkc; ++kc) {
+                const bool on = a < 5 || kc + 1 < nkc;       // (run_pass: on, next, the counts, ahead)
+                for (int x = 0; x < 6; ++x) {
+                    if (x < 5 || on) {
+                        if (on || x < 2) wn_wait_vmcnt<(W4S_AHEAD - 2) * HD>();
+                        else if (x == 2) wn_wait_vmcnt<2 * HD>();
+                        else if (x == 3) wn_wait_vmcnt<HD>();
+                        else wn_wait_vmcnt<0>();
+                        __builtin_amdgcn_s_barrier();
+                    }
+                    if (x < 1 || on) issue_half(a, x < 1 ? kc : kc + 1, (x + W4S_AHEAD) % W4S_SLOTS);
                 }
-                if (g + 3 < ng) issue_half(a, g + 3, (g + 3) & (W4S_SLOTS - 1));      // (run_pass: ahead)
             }
-            __syncthreads();
-            if (a < 5) {
-                issue_half(a + 1, 0, 0);
-                issue_half(a + 1, 1, 1);
-                issue_half(a + 1, 2, 2);
-            }
-        }
+        __syncthreads();
     }
 
-    wino4_epilogue<ACT, RES>(p, smem, tab, py, tid, nt, wm, wn, l16, kq, busy);
+    // The epilogue's thread and lane numbers are made again here (every lane of every wave is active), from the wave number in its
+    // SGPR: carried through the K loops they were spilled, and the reload between two loops made the compiler wait vmcnt(0) with
+    // the ring full.
+    const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    wino4_epilogue<ACT, RES>(p, smem, tab, py, wave * 64 + lane_e, nt, wm, wn, lane_e & 15, lane_e >> 4, busy);
 }
 
 // ------------------------------------------------------------------------------ host side
 // Shapes that the eval plan runs on this kernel: looks at the layer's shape only, never at the batch. The rule of split3_eligible: a
 // shape is listed once its median at batch 32 (tools/conv_bench.py --wino-split both --filter-planes on, 7 rounds of 20 launches,
 // transform pass included, filter planes made once) improved by more than the spread of its own baseline's rounds; where that stays
-// undecided, the whole forward decides (bench.py on builds that differ in the list entry alone). profiles/wino4_planes_once, DESIGN
-// 4.15; medians in us, f32 GEMMs -> bf16 planes:
-//   256 -> 512 at 26 x 26     197 -> 128, with residual 203 -> 135 (baseline spread 23 - 26): listed.
-//   512 -> 1024 at 13 x 13    228 - 236 -> 179 - 181, with residual 230 - 240 -> 182 - 185 (256 half workgroups; baseline spread 43 - 52,
-//                             all of it one slow first round): undecided per shape; the forward with the entry is 0.05 ms faster: listed.
-//   512 -> 1024 at 19 x 19    338 -> 236, with residual 352 -> 293 (baseline spread 47 - 52): listed.
-//   128 -> 256 at 52 x 52     193 - 199 -> 155 - 158, with residual 219 -> 183 - 187 (baseline spread 23 - 29): listed.
-//   64 -> 128 at 104 x 104    253 -> 247, with residual 290 -> 291 (spread 35 - 37): stays.
+// undecided, the whole forward decides (bench.py on builds that differ in the list entry alone). Measured again with the six-slot
+// ring (profiles/wino4_ring; the four-slot figures are in profiles/wino4_planes_once); medians in us,
+// f32 GEMMs -> bf16 planes:
+//   256 -> 512 at 26 x 26     189 -> 122, with residual 196 -> 129 (baseline spread 21 - 24): listed.
+//   512 -> 1024 at 13 x 13    231 -> 153, with residual 234 -> 157 (256 half workgroups; baseline spread 44 - 50): listed.
+//   512 -> 1024 at 19 x 19    339 -> 244, with residual 351 -> 257 (baseline spread 36 - 45): listed.
+//   128 -> 256 at 52 x 52     192 -> 145, with residual 216 -> 171 (baseline spread 22 - 24): listed.
+//   64 -> 128 at 104 x 104    252 -> 233, with residual 284 -> 269 (baseline spread 31 and 28): a gain of 20 and 15, inside the spread:
+//                             undecided per shape. The forward with the entry ran 9.727 - 9.758 ms against 9.731 - 9.794 without, the
+//                             medians 0.015 ms apart and the ranges overlapping: not a gain, stays on the f32 GEMMs.
 // conv_bench.py repeats one layer, whose filters then stay in the memory-side cache; in a forward they come from HBM, which is why the
-// transform pass reads the planes ahead (wino4_touch_planes) and why the forward has the last word.
+// transform pass reads the planes ahead (wino4_touch_planes: still worth 0.4 ms of the forward with five stages in flight) and why
+// the forward has the last word.
 // Nothing else was measured (the 38 x 38 and 76 x 76 maps of the 608 network stay on the f32 GEMMs).
 bool wino4_split_eligible(const yolo_conv_desc* d) {
     if (!wino4_split_supported(d) || d->h != d->w) return false;
