@@ -952,6 +952,80 @@ int yolo_track_update(void* state, int b, int max_tracks, const float* boxes, in
                       const yolo_track_params* p, float* out_boxes, int32_t* out_ids, int32_t* out_count, int32_t* det_ids,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Drawing detections and tracks onto frames (csrc/draw.hip) ----------------------------------------------------
+ * yolo_draw_boxes paints the selected rows of boxes (b, n, 6) fp32 [x, y, w, h, score, cls] onto b frames of h x w pixels: contiguous
+ * uint8 HWC, 3 bytes per pixel (r, g, b). frames_out == frames_in draws in place; otherwise frames_out receives the drawn copy and
+ * the two buffers must not overlap. Every pixel is read once and written at most once, there are no atomics, and the result is
+ * defined to the bit below; pixels outside every command's rectangles keep their input bytes. All arithmetic on coordinates is
+ * fp32 with every operation rounded once (written fl), no fused multiply-add, IEEE division.
+ *
+ * Selection, as for yolo_track_update: with keep_idx (b, n) and keep_count (b) command j < keep_count[s] of frame s is the row
+ * boxes[s][keep_idx[s][j]] (an index outside [0, n) draws nothing); with keep_count alone the first keep_count[s] rows; with neither
+ * every row. keep_count is clamped to [0, n]; keep_idx without keep_count is YOLO_ERR_ARG. ids (b, n) int32, optional, is indexed by
+ * the row, like boxes (the ids of a track result, or det_ids beside the detections).
+ *
+ * Un-mapping (meta != NULL): meta is a device (b, 6) int32 table of the letterbox's (orig_h, orig_w, new_h, new_w, pad_top, pad_left)
+ * and canvas_hw the HOST pair (canvas_h, canvas_w). Before anything else, x = fl(fl(fl(x canvas_w) - pad_left) / new_w),
+ * y = fl(fl(fl(y canvas_h) - pad_top) / new_h); a centre-format row then takes w = fl(fl(w canvas_w) / new_w), h = fl(fl(h canvas_h) / new_h),
+ * a corner-format row maps its second corner like its first. This is unletterbox_boxes(..., meta=) of the Python layer.
+ *
+ * Geometry on the h x w frame (W = (float) w, H = (float) h). center != 0: l = fl(fl(x - fl(w / 2)) W), r = fl(fl(x + fl(w / 2)) W),
+ * t = fl(fl(y - fl(h / 2)) H), b = fl(fl(y + fl(h / 2)) H). center == 0, rows [x0, y0, x1, y1, ..]: l = fl(x0 W), t = fl(y0 H),
+ * r = fl(x1 W), b = fl(y1 H). A row of which one of l, t, r, b is not finite, or with r < l or b < t, draws nothing. Each edge e is
+ * clamped to [-2^20, 2^20] and becomes the integer (int) floorf(fl(e + 0.5f)): the box is [x0, x1) x [y0, y1), x1 and y1 exclusive.
+ * Outline of thickness T, centred on the edge: the outer rectangle is the box grown by T / 2 on every side, the inner rectangle the
+ * box shrunk by T - T / 2 (integer divisions); the ring is outer minus inner, so an empty inner rectangle makes it solid. A row
+ * whose outer rectangle is empty or does not meet the frame draws nothing, not even a label. Everything is clipped to the frame.
+ *
+ * Colour: palette (n_colors, 3) uint8; index (k mod n_colors), the non-negative remainder, with k = the row's id if color_by_id
+ * (then ids must be given) else its class c: c = (int) cls (truncation) if |cls| <= 2^30, else -1 (NaN included).
+ * Blend of a pixel with the colour at alpha a in 0 .. 255, per channel in integers: out = (src (255 - a) + colour a + 127) / 255,
+ * so a = 255 gives colour and a = 0 gives src. The inner rectangle is blended at fill_alpha, the ring at line_alpha.
+ *
+ * Label (labels != 0). The text is: the class name, row c of class_names (n_classes, name_width) uint8, zero-padded, a byte outside
+ * 0x20 .. 0x7E shown as '?' (without class_names: no name); then, if ids is given and the id > 0 (the tracker's tentative and "none"
+ * are <= 0), " #" and the id in decimal; then, if scores != 0, " NN%" with pct = (int) floorf(fl(fl(score 100) + 0.5f)) clamped to
+ * [0, 100] (NaN: 0), two digits, three for 100. The separating blank is left out at the start of the text. Text beyond
+ * yolo_draw_text_capacity() = 32 characters is cut off; an empty text has no plate. With class_names a row whose class is outside
+ * [0, n_classes) draws nothing. Font: yolo_draw_font, 95 glyphs of 0x20 .. 0x7E, 5 x 7 in a 6 x 8 cell, 8 bytes per glyph, one per
+ * row from the top, bit 4 the left column; row 7 and column 5 are blank. Each font pixel is font_scale x font_scale frame pixels.
+ * The plate is 6 font_scale len wide and 8 font_scale high. It stands on the outer rectangle's top-left corner: left = outer x0,
+ * top = outer y0 - height; a top < 0 becomes outer y0 (the plate moves inside the box); a right edge > w makes left = max(0, w -
+ * width). Plate pixels take the colour (alpha 255), glyph pixels white (255, 255, 255).
+ *
+ * Order: commands j = 0, 1, .. in selection order, a later one over an earlier one; inside a command fill, outline, plate, glyphs.
+ *
+ * typedef YoloDrawParams: thickness in [1, 64], font_scale in [1, 8], line_alpha and fill_alpha in [0, 255], else YOLO_ERR_ARG, as
+ * are a null frames_in, frames_out, params, palette or (n > 0) boxes, n_colors < 1, class_names with n_classes < 1 or name_width
+ * < 1, color_by_id without ids and meta without canvas_hw. Limits: 1 <= h, w <= 16384, 1 <= b <= 65535 (the grid's z), 0 <= n <=
+ * 2^24, and a workspace that is not NULL, 16-byte aligned and at least yolo_draw_workspace_bytes(b, n) = round16(4 b) + 112 b n bytes
+ * (0 outside the limits), else YOLO_ERR_UNSUPPORTED; all are returned before any launch. Every workspace byte that is read was
+ * written by the call. Two launches: one thread per (frame, command) writes a 96-byte record and a 16-byte bounding rectangle; one
+ * workgroup per pixel tile (yolo_draw_tile: 128 x 32) tests the frame's commands yolo_draw_chunk() = 256 at a time, keeps the hits
+ * in order and composites its pixels in registers. A thread moves a run of 4 pixels as three dwords when both frame pointers and
+ * 3 w are multiples of 4, else byte by byte; the bytes are the same. In place, a tile that no command touches is neither read nor
+ * written. Stream-ordered, nothing is read back: the call can be captured in a graph. yolo_draw_tile, yolo_draw_chunk,
+ * yolo_draw_text_capacity, yolo_draw_font and yolo_draw_workspace_bytes are HOST ONLY. */
+typedef struct YoloDrawParams {
+    int32_t thickness;       /* T, pixels */
+    int32_t font_scale;
+    int32_t line_alpha;      /* 0 .. 255, of the ring */
+    int32_t fill_alpha;      /* 0 .. 255, of the inner rectangle */
+    int32_t labels;          /* != 0: plates with text */
+    int32_t scores;          /* != 0: the text ends in the score */
+    int32_t color_by_id;     /* != 0: palette index from ids, else from the class */
+    int32_t reserved;        /* 0 */
+} YoloDrawParams;            /* 32 bytes */
+void yolo_draw_tile(int* w, int* h);
+int yolo_draw_chunk(void);
+int yolo_draw_text_capacity(void);
+void yolo_draw_font(unsigned char* rows_95x8);
+size_t yolo_draw_workspace_bytes(int b, int n);
+int yolo_draw_boxes(const uint8_t* frames_in, uint8_t* frames_out, int b, int h, int w, const float* boxes, int n, int center,
+                    const int32_t* keep_idx, const int32_t* keep_count, const int32_t* ids, const int32_t* meta, const int32_t* canvas_hw,
+                    const YoloDrawParams* params, const uint8_t* class_names, int n_classes, int name_width, const uint8_t* palette,
+                    int n_colors, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,11 @@ class TrackParams(C.Structure):
                 ("max_age", C.c_int32), ("center", C.c_int32), ("class_agnostic", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DrawParams(C.Structure):
+    """`YoloDrawParams` (include/yolo_mi355x.h): the style of yolo_draw_boxes, 32 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ("thickness", "font_scale", "line_alpha", "fill_alpha", "labels", "scores", "color_by_id", "reserved")]
+
+
 NORM_KINDS = {2.0: 0, float("inf"): 1}                                 # YOLO_NORM_L2 / YOLO_NORM_INF of the header
 
 CALL_MAX_ARGS = 24
@@ -249,6 +254,14 @@ _SIGS = {
     "yolo_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_track_update": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TrackParams),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_draw_tile": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "yolo_draw_chunk": (C.c_int, []),
+    "yolo_draw_text_capacity": (C.c_int, []),
+    "yolo_draw_font": (None, [C.c_char_p]),
+    "yolo_draw_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "yolo_draw_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(DrawParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "yolo_tta_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_boxes_unflip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_tile_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),

@@ -11,6 +11,8 @@ Two levels:
 # Re-exports only: the code lives in one module per stage (the module map in DESIGN.md).
 from .boxes import STRIDES, calc_iou, cells_to_boxes, decode_boxes, detect, detect_images, iou_aligned, nms_indices, non_max_suppression, scaled_anchors, AnchorFitness, AnchorResult, anchor_draws, anchor_fitness, anchors_layout, kmeans_anchors
 from .data import AUG_NPARAM, augment_batch, augment_params, build_targets, letterbox, train_batch, unletterbox_boxes
+# the reference's two plotting functions (draw.py): attributes of this module that its __all__, pinned to the names of before, leaves out
+from .draw import plot_image_with_boxes, plot_original
 from .fuse import detect_tta, fuse_boxes, tta_boxes, tta_views
 from .metrics import EVAL_MAX_THRESHOLDS, EvalMatches, EvalResult, accuracy_counts, calc_mAP, check_model_accuracy, eval_boxes, evaluate_detections, evaluate_model, get_eval_boxes
 from .model import load_checkpoint, save_checkpoint
