@@ -40,21 +40,32 @@
 // pointer then serves launches with and without the flag. 6 bytes per weight on top of the packed weights.
 // WDMA moves the prepared B rows by LDS-DMA (global_load_lds, 16 bytes per lane) instead of through registers: a B ring of two
 // slots, step kt + 1 requested at the top of step kt and retired by the vmcnt(0) in front of the barrier that ends the step.
+// (One K step of A and B in flight, on every tile: two and three steps of A were built and measured; they gain nothing
+// on 128x128 and 64x64 and cost the 128x64 tile its fourth workgroup.)
 // 64x64 blocks have the two slots already (48 KB), a 128x128 block takes 72 KB with them (still two workgroups per CU), a 128x64
 // block would take 48 KB and lose its fourth workgroup, so that tile copies through registers (ds_write_b128, 36 KB as before).
 #include "conv_f32_epilogue.h"
 #include "split3.h"
+#include "wino_dma.h"      // wn_glds16_s, wn_wait_vmcnt
 
 namespace yolo {
+
+// The barriers of the K loop. A __syncthreads() is a fence too, and with LDS-DMA in the kernel the compiler makes that fence wait
+// vmcnt(0): the barrier in the middle of a step would wait for the A and B requests of the next step, which only the end of the step
+// needs. The WDMA kernels order their LDS traffic themselves: the wave's own LDS reads and writes are done, then the barrier; what
+// has to have landed by DMA is waited for in front of the barrier that ends the step.
+template <bool WDMA>
+__device__ __forceinline__ void s3_sync() {
+    if constexpr (WDMA) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else __syncthreads();
+}
 
 constexpr int S3_ROWB = 64;      // bytes per LDS row: 32 bf16 as four 16-byte slots, slot s of row r stored at s ^ ((r >> 2) & 3)
 
 // byte offset, inside a plane of 64-byte rows, of the 8 bytes that hold k = 4 * chunk .. + 3 of row r
 __device__ __forceinline__ int s3_row_off(int r, int chunk) { return r * S3_ROWB + (((chunk >> 1) ^ ((r >> 2) & 3)) * 16 + (chunk & 1) * 8); }
 
-typedef const __attribute__((address_space(1))) void* s3_gptr;
 typedef __attribute__((address_space(3))) void* s3_lptr;
-__device__ __forceinline__ void s3_glds16(const void* g, void* l) { __builtin_amdgcn_global_load_lds((s3_gptr)g, (s3_lptr)l, 16, 0, 0); }
 
 // Prepared weights of yolo_split3_weights: one block per 32 output channels, the staging geometry of conv_split3_f32 (thread =
 // row tid >> 3, 16-byte chunk tid & 7 of every K step), so that the bytes written are the ones store_lds would have written.
@@ -141,35 +152,50 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
     const char* wq = p.w_planes;
     const size_t plane_b = (size_t)((p.Cout + 127) & ~127) * S3_ROWB;
     const char* wsrc = wq + (size_t)n0 * S3_ROWB + tid * 16;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);          // the same address as wave-uniform base + 16 lane
+    const char* wdma_src = wq + (size_t)n0 * S3_ROWB + wave_u * 1024;
+    const unsigned wdma_dst = (unsigned)(size_t)(s3_lptr)smem_raw + A_BYTES + wave_u * 1024;
 
     f32x4 ra[RA], rb[RB];
+    unsigned av;                     // bit i: row i of what ra holds is a tap inside the image (the others are zeroed when it is split)
     s3_u32x4 rw[3][PB];
     f32x4 chk = {0.f, 0.f, 0.f, 0.f};
-    auto load_global = [&](int kt) {
+    // A of step kt: RA loads, every one issued whatever the tap (a padding tap reads the first pixel of the view, and store_lds puts
+    // zeros in its place): no branch around a load, and nothing here uses a loaded value, so nothing waits before the products.
+    auto load_a = [&](int kt) {
         const int kg = kt * BK;
         const int tap = kg / p.Cin;
         const int coff = kg - tap * p.Cin + chunk * 4;
         const int kh = tap / p.ks, kw = tap - kh * p.ks;
         const long long toff = (long long)(kh * p.W + kw) * p.x_ld + coff;
+        unsigned valid = 0;
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             const bool v = (a_mask[i] >> tap) & 1u;
-            f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            ra[i] = v ? *reinterpret_cast<const f32x4*>(p.x + a_base[i] + toff) : z;
+            valid |= (unsigned)v << i;
+            ra[i] = *reinterpret_cast<const f32x4*>(p.x + (v ? a_base[i] + toff : (long long)p.x_off + coff));
         }
+        av = valid;
+    };
+    auto load_b = [&](int kt) {
         if constexpr (!WREADY) {
 #pragma unroll
             for (int i = 0; i < RB; ++i)
                 rb[i] = *reinterpret_cast<const f32x4*>(wrow + (size_t)(32 * i) * p.Kpad + kt * BK);
         } else {
             const char* src = wsrc + (size_t)kt * 3 * plane_b;
-            char* dst = smem_raw + A_BYTES + (kt & 1) * B_SLOT + wave * 1024;      // (WDMA: the wave's KB of every 4; lane l lands 16 l in)
+            // WDMA: the wave's KB of every 4, lane l lands 16 l in. The request is wn_glds16_s's text, not the builtin: while a
+            // request that the compiler knows of is pending, every vmcnt it needs for the A registers becomes vmcnt(0) (it takes
+            // an LDS-DMA for a flat access that may return out of order). B is requested before A, so the counts that the compiler
+            // makes for the A registers without knowing of these requests cover them: loads return in order.
+            const char* dsrc = wdma_src + (size_t)kt * 3 * plane_b;
+            const unsigned dst = wdma_dst + (kt & 1) * B_SLOT;
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int i = 0; i < PB; ++i) {
                     if constexpr (WDMA)
-                        s3_glds16(src + q * plane_b + i * 4096, dst + q * BN * S3_ROWB + i * 4096);
+                        wn_glds16_s(dsrc + q * plane_b + i * 4096, lane * 16, dst + q * BN * S3_ROWB + i * 4096);
                     else
                         rw[q][i] = *reinterpret_cast<const s3_u32x4*>(src + q * plane_b + i * 4096);
                 }
@@ -181,7 +207,8 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             u32x2 h, m, l;
-            s3_split(ra[i], h, m, l, chk);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            s3_split((av >> i) & 1u ? ra[i] : z, h, m, l, chk);
             *reinterpret_cast<u32x2*>(a + (0 * BM + 32 * i) * S3_ROWB) = h;
             *reinterpret_cast<u32x2*>(a + (1 * BM + 32 * i) * S3_ROWB) = m;
             *reinterpret_cast<u32x2*>(a + (2 * BM + 32 * i) * S3_ROWB) = l;
@@ -219,16 +246,18 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
     const int fsw = (frow >> 2) & 3;                       // the swizzle of this lane's rows (the same in every 32-row tile)
     const int f_slot[2] = {(fh ^ fsw) * 16, ((2 + fh) ^ fsw) * 16};
 
-    load_global(0);
-    store_lds(0, 0);
-    if constexpr (WDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    for (int kt = 0; kt < p.KT; ++kt) {
+    // One K step. MORE: step kt + 1 exists; its B and then its A are requested at the top and split / stored at the end. MORE is a
+    // constant of the text (the loop runs the steps that ask, the last step is written out behind it), so that the requests, the
+    // split and the waits of a step sit in one block that the scheduler orders as a whole.
+    auto step = [&](auto MORE, int kt) {
+        constexpr bool more = decltype(MORE)::value;
         const int cur = DBUF ? (kt & 1) : 0;
         const int bcur = BRING ? (kt & 1) : 0;
-        const bool more = kt + 1 < p.KT;
-        if (more) load_global(kt + 1);           // (WDMA: B slot bcur ^ 1 was last read in step kt - 1, behind that step's barrier)
+        if constexpr (more) {
+            load_b(kt + 1);                          // (WDMA: B slot bcur ^ 1 was last read in step kt - 1, behind that step's barrier)
+            load_a(kt + 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);           // the requests go out before the products ...
         const char* Ab = smem_raw + cur * BUF_BYTES + a_frag;
         const char* Bb = smem_raw + bcur * B_SLOT + b_frag;
 #pragma unroll
@@ -255,11 +284,21 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32(const ConvArgs p) {
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][QA[t]], bf[j][QB[t]], acc[i][j], 0, 0, 0);
         }
-        if (!DBUF) __syncthreads();              // one buffer: everybody has read step kt before step kt + 1 lands
-        if (more) store_lds(DBUF ? (cur ^ 1) : 0, BRING ? (bcur ^ 1) : 0);
-        if constexpr (WDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the DMA of step kt + 1 has landed before the barrier
-        __syncthreads();
-    }
+        __builtin_amdgcn_sched_barrier(0);           // ... and the split, which has to wait for them, stays behind the products
+        if (!DBUF) s3_sync<WDMA>();                  // one buffer: everybody has read step kt before step kt + 1 lands
+        if constexpr (more) store_lds(DBUF ? (cur ^ 1) : 0, BRING ? (bcur ^ 1) : 0);
+        if constexpr (WDMA) wn_wait_vmcnt<0>();      // the DMA of step kt + 1 has landed before the barrier
+        s3_sync<WDMA>();
+    };
+
+    load_b(0);
+    load_a(0);
+    store_lds(0, 0);
+    if constexpr (WDMA) wn_wait_vmcnt<0>();
+    s3_sync<WDMA>();
+
+    for (int kt = 0; kt + 1 < p.KT; ++kt) step(std::true_type{}, kt);
+    step(std::false_type{}, p.KT - 1);
 
     // A block that staged an Inf or a NaN computes its tile again with exact f32 products, straight from global memory (rare, so
     // slow is fine) and in conv_igemm_f32's order: k = 8 s + 4 (l >> 5) + e for MFMA (s, e) of each K step.
@@ -380,6 +419,10 @@ int split3_weights_launch(const yolo_conv_desc* d, const void* w_packed, void* o
 // columns, so 128x128 also wins 512 -> 1024 stride 2 at 26 x 26 (345 against 357) and the 1x1 layers with a multiple of 128 output
 // channels and many K steps: 256 -> 128 and 384 -> 128 at 52 x 52 (46.4 / 63.0 against 49.8 / 68.9), 768 -> 256 at 26 x 26 (64.9
 // against 65.8). 512 -> 256 at 26 x 26 (46.6 against 47.2) gains less than its own spread and stays.
+// Fitted again after the K step was rewritten (profiles/split3_ahead/conv_bench.txt: every tile 2 - 5 % faster, in step): the
+// same choices. 128x128 / 128x64 / 64x64 now: stride 2 with 64 .. 512 channels 305 / 354 / 395, 283 / 331 / 368, 294 / 338 / 359, 322 /
+// 336 / 356; 256 -> 128 and 384 -> 128 at 52 x 52 43.8 / 46.4 and 59.7 / 65.2; 768 -> 256 at 26 x 26 60.6 / 63.1; 512 -> 256 at 26 x 26 43.9 /
+// 44.4, still inside its spread; 1024 -> 512 at 13 x 13 53.6 / 53.8 / 44.7.
 static int pick_split3_tile(const ConvArgs& a, bool ready) {
     if (a.ks == 3 && a.stride == 2 && a.Cin >= 64 && (ready || a.Cin < 512)) return kTileF32Reg128x128;
     if (a.ks == 1 && (long long)a.H * a.W * a.Cout < 100000) return kTileF32Reg64x64;
