@@ -1026,6 +1026,66 @@ int yolo_draw_boxes(const uint8_t* frames_in, uint8_t* frames_out, int b, int h,
                     const YoloDrawParams* params, const uint8_t* class_names, int n_classes, int name_width, const uint8_t* palette,
                     int n_colors, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The frame front end: RGB24 / BGR24 / NV12 frames to the network's input, batched (csrc/frames.hip) ----------
+ * PARITY UNPINNED, for the resize as for yolo_letterbox and for the NV12 conversion too: both follow OpenCV's published integer
+ * arithmetic (BT.601 limited range with OpenCV's own literals, so that a cv2.cvtColor user is meant to see the same bits), neither
+ * was run against cv2; they are tested against a numpy restatement (tests/frames_ref.py).
+ *
+ * Frames lie in a uint8 device pool; a device table has one yolo_frame_row per frame: the byte offset of the frame's first row from
+ * pool (any int64, so frames that were allocated apart can be addressed from the lowest of them), its size h x w in pixels and its
+ * row pitch in bytes. RGB24 / BGR24: h rows of w packed pixels, pitch >= 3 w. NV12: h rows of w luma bytes, then at offset + h pitch
+ * the h / 2 rows of interleaved (U, V) pairs with the same pitch, pitch >= w, h and w even. The table is 8-byte aligned.
+ *
+ * yolo_frames_letterbox: out (n, 3, canvas_h, canvas_w) fp32, planes in R, G, B order whatever the source order, is "convert frame i
+ * to packed RGB uint8 at its own resolution, then yolo_letterbox_hw it onto the canvas", to the bit: the resized size (new_h, new_w)
+ * and the padding (canvas - new) / 2 per axis are computed in the kernel from (h, w, size, canvas), each output pixel blends four
+ * source pixels, each converted to uint8 RGB first, with the fixed-point coefficients of yolo_letterbox, and is scaled by
+ * (float) u8 * (1.0f / 255.0f); 0.0f in the padding. meta_out (n, 6) int32, device, optional: (orig_h, orig_w, new_h, new_w,
+ * pad_top, pad_left) per frame, the table yolo_draw_boxes and yolo_boxes_to_frames take. One launch for the batch, its grid
+ * depends on (n, canvas_h, canvas_w) only; nothing is read back, so the call can be captured in a graph. THE CALLER GUARANTEES what
+ * the device cannot report without a wait: every row has h, w >= 1 (NV12: even), a pitch of at least the row's bytes, and a resized
+ * size that fits the canvas (yolo_letterbox_canvas gives such a canvas). YOLO_ERR_ARG: a null pool, table or out, n < 1, an unknown
+ * format or csc, size or a canvas side <= 0, and n ceil(canvas_h / 16) ceil(canvas_w / 64) > INT_MAX (the frame index is folded into
+ * the grid's x, which is the only limit on n). yolo_frames_tile: the 64 x 16 output tile of one workgroup (HOST ONLY).
+ *
+ * NV12 -> RGB: chroma is replicated over its 2 x 2 luma block; with u = U - 128, v = V - 128, y = max(0, Y - yoff) CY, in int32,
+ *   R = clip((y + (1 << 19) + CVR v) >> 20), G = clip((y + (1 << 19) + CVG v + CUG u) >> 20), B = clip((y + (1 << 19) + CUB u) >> 20),
+ * arithmetic shifts, clip to 0 .. 255. csc picks (CY, CVR, CVG, CUG, CUB, yoff), which yolo_frames_csc_constants returns (HOST ONLY):
+ *   YOLO_CSC_BT601       1220542, 1673527, -852492, -409993, 2116026, 16   (OpenCV's ITUR_BT_601_* literals)
+ *   YOLO_CSC_BT601_FULL  1048576, 1470104, -748826, -360853, 1858077,  0
+ *   YOLO_CSC_BT709       1220945, 1879825, -558796, -223607, 2215014, 16
+ *   YOLO_CSC_BT709_FULL  1048576, 1651297, -490864, -196424, 1945738,  0
+ * the last three round(c 2^20) of the exact coefficients from the standard's Kr, Kb. csc is ignored for RGB24 / BGR24.
+ *
+ * yolo_frames_to_rgb: the conversion alone, out (n, h, w, 3) packed RGB uint8 at source resolution; all n frames are h x w (the
+ * arguments; of the table the call reads offset and pitch), 1 <= h, w <= 16384, NV12 even, else YOLO_ERR_ARG.
+ *
+ * yolo_boxes_to_frames: boxes (b, n, 6) fp32 rows [x, y, w, h, score, cls] normalised to the canvas -> out, normalised to each
+ * frame, with meta (b, 6) as above: x = ((double) x canvas_w - pad_left) / new_w, y = ((double) y canvas_h - pad_top) / new_h,
+ * w = ((double) w canvas_w) / new_w, h = ((double) h canvas_h) / new_h, every operation in fp64 in that order and one rounding to
+ * fp32; columns 4 and 5 are copied. This is unletterbox_boxes(..., meta=) of the Python layer rounded to fp32 (yolo_draw_boxes maps
+ * in fp32 steps instead). out may be boxes. n == 0 launches nothing. Stream-ordered, no read-back. */
+#define YOLO_FRAMES_RGB24 0
+#define YOLO_FRAMES_BGR24 1
+#define YOLO_FRAMES_NV12 2
+#define YOLO_CSC_BT601 0
+#define YOLO_CSC_BT601_FULL 1
+#define YOLO_CSC_BT709 2
+#define YOLO_CSC_BT709_FULL 3
+typedef struct yolo_frame_row {
+    int64_t offset;          /* bytes from pool to the frame's first row */
+    int32_t h, w;            /* pixels */
+    int32_t pitch;           /* bytes per row */
+    int32_t reserved;        /* 0 */
+} yolo_frame_row;            /* 24 bytes */
+void yolo_frames_tile(int* w, int* h);
+int yolo_frames_csc_constants(int csc, int32_t* out6);
+int yolo_frames_letterbox(const uint8_t* pool, const yolo_frame_row* table, int n, int format, int csc, int size, int canvas_h,
+                          int canvas_w, float* out, int32_t* meta_out, void* stream);
+int yolo_frames_to_rgb(const uint8_t* pool, const yolo_frame_row* table, int n, int h, int w, int format, int csc, uint8_t* out,
+                       void* stream);
+int yolo_boxes_to_frames(const float* boxes, int b, int n, const int32_t* meta, int canvas_h, int canvas_w, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

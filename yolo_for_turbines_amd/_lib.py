@@ -63,6 +63,14 @@ class DrawParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("thickness", "font_scale", "line_alpha", "fill_alpha", "labels", "scores", "color_by_id", "reserved")]
 
 
+class FrameRow(C.Structure):
+    """`yolo_frame_row` (include/yolo_mi355x.h): where one frame lies in the pool, 24 bytes."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
+FRAME_FORMATS = {"rgb": 0, "bgr": 1, "nv12": 2}                        # YOLO_FRAMES_* / YOLO_CSC_* of the header
+CSC_KINDS = {"bt601": 0, "bt601-full": 1, "bt709": 2, "bt709-full": 3}
+
 NORM_KINDS = {2.0: 0, float("inf"): 1}                                 # YOLO_NORM_L2 / YOLO_NORM_INF of the header
 
 CALL_MAX_ARGS = 24
@@ -262,6 +270,12 @@ _SIGS = {
     "yolo_draw_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(DrawParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                   C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_frames_tile": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "yolo_frames_csc_constants": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
+    "yolo_frames_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "yolo_frames_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "yolo_boxes_to_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_tta_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_boxes_unflip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_tile_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
