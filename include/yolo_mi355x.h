@@ -127,7 +127,8 @@ const char* yolo_last_error(void);
 /* 101: the six SGD step entry points of 100 (by value, _hp, _amp, _hp_ema, _amp_ema, _clip) are one, yolo_sgd_step, with the
  * argument list the _clip one had and clip_state_dev optional like every other option.
  * 102: yolo_wgrad_plan; yolo_conv_wgrad refuses a channel slice that does not fit its buffer and, for 16-bit dtypes, operands or a
- * workspace that are not 16-byte aligned. */
+ * workspace that are not 16-byte aligned.
+ * 104: yolo_conv_patch_plan; conv_patch_f32 (tiles 5 - 7) writes y / residual views that are not multiples of 4 element by element. */
 int yolo_version(void);
 /* The A/B environment switches (INTEGRATION.md has the table) are read once, when the library is loaded. This writes what was
  * read as "NAME=value\n" per switch, in the table's order (a boolean is 0 / 1 in the sense of its name: YOLO_NO_DMA=1 means the
@@ -257,6 +258,13 @@ int yolo_wino4_appended_wanted(const yolo_conv_desc* d);
  * *half tile blocks, those of a last round that would fill at most half the compute units, run as two workgroups of 32 tiles.
  * The result of a tile does not depend on the cut. */
 int yolo_conv_wino4_blocks(const yolo_conv_desc* d, int* whole, int* half);
+/* How a launch of d on the patch kernel conv_patch_f32 (tile 5, 6 or 7; nothing is launched, no device is needed) is cut, from the
+ * code the launch itself runs: out = { TH, TW (output rows x columns of a block's spatial tile; rows are global rows n * h + row, so a
+ * tile may straddle images; a 1x1 runs as one row of n * h * w pixels in tiles of 128), PC (patch columns: TW + 2, or 128), the bound on a
+ * tile's patch rows that the LDS patch is sized for, patch pixels per LDS buffer (of 36 floats each), tiles across the width, tiles
+ * down the rows, workgroups }. YOLO_ERR_ARG for a tile that is not 5, 6 or 7 or a bad shape, YOLO_ERR_UNSUPPORTED where the
+ * kernel does not run d (stride 2, cin not a multiple of 32, a patch that does not fit). */
+int yolo_conv_patch_plan(const yolo_conv_desc* d, int tile, int32_t out[8]);
 /* YOLO_FLAG_WINO_SPLIT_BF16 for plans (flags and tile of d are not looked at; the layer's shape only, never the batch).
  * yolo_conv_wino4_split_supported: 1 when the library honours the flag on the layer once it runs as tile 15 on finished filters.
  * yolo_conv_wino4_split_eligible: 1 when, in addition, the shape measured faster that way at batch 32 (the eval plan's list). */

@@ -152,6 +152,7 @@ _SIGS = {
     "yolo_wino4_appended_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "yolo_wino4_appended_wanted": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_wino4_blocks": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "yolo_conv_patch_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_int32)]),
     "yolo_conv_wino4_split_supported": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_conv_wino4_split_eligible": (C.c_int, [C.POINTER(ConvDesc)]),
     "yolo_wino4_filter_plane_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),

@@ -17,6 +17,13 @@
 // (16 different rows, same column chunk) hit 16 different 16-byte slots.  Register-staged
 // double buffering: global loads of step t+1 are issued before the MFMAs of step t and written
 // to the other LDS buffer after them; one barrier per K step.
+//
+// Bits against conv_patch_f32 (conv_f32_v2.hip), which adds the same products in the same order where cin == 32 or ksize == 1:
+// identical, except for Mish on the element-by-element path of conv_f32_epilogue (cout % 4 != 0, a y / residual view that is no
+// multiple of 4, the head layout). There the activation runs on the accumulator registers and hipcc vectorises Mish's n = e (e + 2),
+// n + 2 into v_pk_mul_f32 + v_add_f32 (two roundings); on the 16-byte path, and everywhere in conv_patch_f32, it runs on the way into
+// the LDS transpose and n + 2 becomes one v_fma_f32 (one rounding). The results differ in their last bits, both within the fp64
+// bound of tests/test_gpu_conv_f32_edges.py.
 #include "conv_f32_epilogue.h"
 
 namespace yolo {

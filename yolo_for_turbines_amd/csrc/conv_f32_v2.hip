@@ -316,7 +316,9 @@ __global__ __launch_bounds__(256) void conv_patch_f32(const Conv2Args p) {
     const int HoWo = p.Ho * p.Wo;
     constexpr int OLD = 68;                         // staging row stride (floats): 64 + 4 pad
     float* ost = patch;                             // [128][OLD] = 34,816 B <= patch region
-    const bool vec_ok = (p.out_mode != YOLO_OUT_HEAD) && (p.Cout % 4 == 0);
+    // 16-byte stores and residual loads need y / residual views that are multiples of 4 (as conv_f32_epilogue's aligned4)
+    const bool vec_ok = (p.out_mode != YOLO_OUT_HEAD) && (p.Cout % 4 == 0) && ((p.y_ld | p.y_off) & 3) == 0 &&
+                        (!has_res || ((p.r_ld | p.r_off) & 3) == 0);
     bool saw_nan = false;
     __syncthreads();                                // every wave is done reading the patch
     // residual rows of EVERY pass: requested before the accumulators go through LDS (they were loaded one by one, each
@@ -510,11 +512,36 @@ int v2_blocks(const yolo_conv_desc* d, int bn) {
     return ceil_div(d->n * d->h, th) * ceil_div(d->w, tw) * ceil_div(d->cout, bn);
 }
 
+// The launch geometry of conv_patch_f32 for descriptor d with BN = bn: everything the kernel's addressing depends on, made in one
+// place for the launch and for yolo_conv_patch_plan. *prmax_out: the bound on a tile's patch rows that patch_cap was sized for.
+static int v2_plan(const yolo_conv_desc* d, int bn, bool single_buffer, Conv2Args& a, int* prmax_out) {
+    const long long M = (long long)d->n * d->h * d->w;
+    if (M > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "conv: N*H*W exceeds int32");
+    int prmax = 1;
+    if (d->ksize == 1) {
+        a.H = 1; a.W = (int)M; a.rows_total = 1;
+        a.TH = 1; a.TW = 128; a.PC = 128;
+    } else {
+        a.H = d->h; a.W = d->w; a.rows_total = d->n * d->h;
+        pick_patch_tile(d->h, d->w, 3, &a.TH, &a.TW, &prmax);
+        a.PC = a.TW + 2;
+    }
+    a.bufmask = single_buffer ? 0 : 1;
+    a.patch_cap = round_up(prmax * a.PC, 32);
+    if (a.patch_cap < 128) a.patch_cap = 128;              // the epilogue stages a 128 x 68 float tile in the patch region
+    if (single_buffer) a.patch_cap = V2_PATCH_CAP;         // ... which then needs the whole (single) buffer: 256 px x 144 B = 36.9 KB
+    if (a.patch_cap > V2_PATCH_CAP) return fail(YOLO_ERR_UNSUPPORTED, "conv v2: patch too large");
+    a.tiles_w = ceil_div(a.W, a.TW);
+    a.tiles_n = ceil_div(d->cout, bn);
+    a.nblocks = a.tiles_n * a.tiles_w * ceil_div(a.rows_total, a.TH);
+    a.nchunks = d->cin / 32;
+    a.KT = a.nchunks * d->ksize * d->ksize;
+    *prmax_out = prmax;
+    return YOLO_OK;
+}
+
 template <int KS, int BN>
 static int launch_v2(Conv2Args& a, hipStream_t s) {
-    a.tiles_n = ceil_div(a.Cout, BN);
-    const int tiles_r = ceil_div(a.rows_total, a.TH);
-    a.nblocks = a.tiles_n * a.tiles_w * tiles_r;
     // resident blocks per CU (2, or 3 with a single patch buffer) x 256 CUs are dispatched at once
     a.first_wave = (a.bufmask ? 2 : 3) * 256;
     const long mfma_cycles = (long)a.KT * 32 * (BN / 64) * 64;  // one block's matrix work per wave
@@ -533,25 +560,8 @@ int conv_v2_launch(const yolo_conv_desc* d, const void* x, const float* wf, cons
     a.Cin = d->cin; a.Cout = d->cout;
     a.x_ld = d->x_ld; a.x_off = d->x_off; a.y_ld = d->y_ld; a.y_off = d->y_off; a.r_ld = d->r_ld; a.r_off = d->r_off;
     a.Ho = d->h; a.Wo = d->w;
-    const long long M = (long long)d->n * d->h * d->w;
-    if (M > 0x7fffffffLL) return fail(YOLO_ERR_UNSUPPORTED, "conv: N*H*W exceeds int32");
     int prmax = 1;
-    if (d->ksize == 1) {
-        a.H = 1; a.W = (int)M; a.rows_total = 1;
-        a.TH = 1; a.TW = 128; a.PC = 128;
-    } else {
-        a.H = d->h; a.W = d->w; a.rows_total = d->n * d->h;
-        pick_patch_tile(d->h, d->w, 3, &a.TH, &a.TW, &prmax);
-        a.PC = a.TW + 2;
-    }
-    a.bufmask = single_buffer ? 0 : 1;
-    a.patch_cap = round_up(prmax * a.PC, 32);
-    if (a.patch_cap < 128) a.patch_cap = 128;              // the epilogue stages a 128 x 68 float tile in the patch region
-    if (single_buffer) a.patch_cap = V2_PATCH_CAP;         // ... which then needs the whole (single) buffer: 256 px x 144 B = 36.9 KB
-    if (a.patch_cap > V2_PATCH_CAP) return fail(YOLO_ERR_UNSUPPORTED, "conv v2: patch too large");
-    a.tiles_w = ceil_div(a.W, a.TW);
-    a.nchunks = d->cin / 32;
-    a.KT = a.nchunks * d->ksize * d->ksize;
+    if (int rc = v2_plan(d, bn, single_buffer, a, &prmax)) return rc;
     a.act = d->act; a.out_mode = d->out_mode; a.flags = d->flags;
     a.nc5 = d->out_mode == YOLO_OUT_HEAD ? d->cout / 3 : 1;
 #ifdef V2_STAMPS
@@ -562,3 +572,18 @@ int conv_v2_launch(const yolo_conv_desc* d, const void* x, const float* wf, cons
 }
 
 }  // namespace yolo
+
+extern "C" int yolo_conv_patch_plan(const yolo_conv_desc* d, int tile, int32_t out[8]) {
+    using namespace yolo;
+    if (!d || !out) return fail(YOLO_ERR_ARG, "conv_patch_plan: null pointer");
+    if (tile < kTileF32V2Bn64 || tile > kTileF32V2Single) return fail(YOLO_ERR_ARG, "conv_patch_plan: tile %d is not 5, 6 or 7", tile);
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->cin <= 0 || d->cout <= 0 || (d->ksize != 1 && d->ksize != 3))
+        return fail(YOLO_ERR_ARG, "conv_patch_plan: bad shape");
+    if (!v2_eligible(d)) return fail(YOLO_ERR_UNSUPPORTED, "conv: tile %d needs stride 1 and cin %% 32 == 0", tile);
+    Conv2Args a;
+    int prmax = 1;
+    if (int rc = v2_plan(d, tile == kTileF32V2Bn128 ? 128 : 64, tile == kTileF32V2Single, a, &prmax)) return rc;
+    const int32_t v[8] = {a.TH, a.TW, a.PC, prmax, a.patch_cap, a.tiles_w, ceil_div(a.rows_total, a.TH), a.nblocks};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return YOLO_OK;
+}

@@ -166,7 +166,7 @@ using namespace yolo;
 extern "C" {
 
 const char* yolo_last_error(void) { return yolo::err_buf(); }
-int yolo_version(void) { return 103; }
+int yolo_version(void) { return 104; }
 
 size_t yolo_packed_weight_bytes(int cout, int cin, int ksize, int dtype) {
     if (cout <= 0 || cin <= 0 || (ksize != 1 && ksize != 3)) return 0;
