@@ -844,6 +844,65 @@ int yolo_tile_collect_ex(const float* boxes, int n_tiles, int n_per, const int32
                          int n_images, int tile_h, int tile_w, double obj_threshold, float edge_margin, float* cand, int cap,
                          int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- training on tiles: box-aware crops of full-size images (csrc/crops.hip), the training-side counterpart of the tiled
+ * detection above. Nothing of the reference: its dataset was tiled offline, which fixes the tile size, the overlap and the scale
+ * once and gives every epoch the same cuts. Here the pool of images stays on the device and every batch is cut from it with fresh
+ * windows. Parity with cv2 / albumentations UNPINNED, as for the training augmentation. This comment is the contract; the kernels and
+ * tests/crops_ref.py are both written from it. ---------------------------------------------------------------------------------- */
+/* Per-crop parameter row, float64 (the kernels hold no randomness). U_PICK, JX, JY are draws in [0, 1); BACKGROUND is a switch (on
+ * when != 0); SCALE is the pyramid scale of the crop's level, in (0, 8] (a value outside, NaN too, is taken as 1). */
+#define YOLO_CROP_U_PICK 0
+#define YOLO_CROP_BACKGROUND 1
+#define YOLO_CROP_JX 2
+#define YOLO_CROP_JY 3
+#define YOLO_CROP_SCALE 4
+#define YOLO_CROP_NPARAM 5
+/* Tables, all on the DEVICE and read only there (nothing on the host depends on an image's size): the pool layout of the training
+ * augmentation - pool uint8 HWC images at byte offsets `offsets` (int64 [n_pool]; any offsets, odd ones too), hw_dev int32
+ * [n_pool][2], boxes float64 [n_pool][max_in][5] yolo (x, y, w, h, class), nbox int32 [n_pool] (-1 = no label file) - and per crop
+ * src_dev int32 [b] (the pool index), crop_params [b][YOLO_CROP_NPARAM], optionally origins_dev int32 [b][2] = [y0, x0] and
+ * aug_params [b][YOLO_AUG_NPARAM] (NULL = no augmentation). Tile (tile_h, tile_w): multiples of 32. 1 <= b <= 65535.
+ * A src entry outside [0, n_pool) gives an empty crop (windows row {-1, 0, 0, 1, 1, -1}, count 0, zero pixels); nothing is read for it.
+ *
+ * WINDOW of crop b, fp64 with every operation rounded once. k = src[b], (h, w) = hw[k].
+ * 1. (LH, LW) = the level of (h, w) at SCALE by the arithmetic of yolo_tile_level_hw: max(1, rint(h SCALE)), half to even.
+ * 2. The crop is an OBJECT crop iff BACKGROUND == 0 and nbox[k] > 0; then picked = min((int) floor(U_PICK nbox[k]), nbox[k] - 1).
+ *    Otherwise (a background crop) picked = -1.
+ * 3. Per axis (x shown; y alike with LH, tile_h, JY, cy): if LW <= tile_w, x0 = 0 (one tile at 0, zero-padded at the right / bottom,
+ *    as yolo_tile_grid has it). Otherwise an object crop takes x0 = (int) floor(cx LW - JX (tile_w - 1)) with cx the picked row's
+ *    centre as given, a background crop x0 = (int) floor(JX (LW - tile_w + 1)); both are then clamped to [0, LW - tile_w] (the clamp
+ *    is taken on the double, NaN -> 0). So the window lies inside the level whenever the level is at least a tile, and the picked
+ *    box's centre lies in the closed tile [0, 1]^2 whenever it lies in the image.
+ * 4. With origins_dev, (y0, x0) is taken as given - any values, as for yolo_tile_gather - and picked = -1.
+ * 5. windows[b] = {k, y0, x0, LH, LW, picked} (int32 [b][6]); yolo_crop_images reads it: run yolo_crop_boxes first, same stream.
+ *
+ * BOXES of crop b: every row i < nbox[k], in order:
+ * 1. yolo -> (x_min, y_min, x_max, y_max) = (x - w / 2, y - h / 2, x_min + w, y_min + h), each clipped to [0, 1]; the row is dropped
+ *    if its area (b2 w - b0 w)(b3 h - b1 h) on the (h, w) image is 0 (the rules of the training augmentation).
+ * 2. To tile coordinates: t0 = (b0 LW - x0) / tile_w, t1 = (b1 LH - y0) / tile_h, and t2, t3 alike.
+ * 3. ta = (t2 tile_w - t0 tile_w)(t3 tile_h - t1 tile_h); c = t clipped to [0, 1]; ca the same expression on c.
+ * 4. The row is kept iff ca != 0 and ca / ta >= min_visibility (a double in [0, 1]; NaN or a value outside is YOLO_ERR_ARG; the
+ *    reference's BboxParams has 0.4). A picked box that is larger than the tile can fall under min_visibility and be dropped: the
+ *    crop then simply has fewer boxes, or none.
+ * 5. With aug_params the row goes through the box chain of the training augmentation on the (tile_h, tile_w) canvas
+ *    (ShiftScaleRotate with its own 0.4 visibility rule, flip); without, it is stored as it is: centre and size in fp64, one
+ *    rounding to fp32.
+ * out_boxes (b, max_out, 5) fp32 + counts (b): rows past counts[b] are zeroed; kept rows beyond max_out are not written.
+ *
+ * PIXELS of crop b: pixel (ty, tx) of the uint8 canvas is level pixel (y0 + ty, x0 + tx): the image resized to (LH, LW) by the
+ * library's one uint8 INTER_LINEAR (the arithmetic of yolo_letterbox; the identity at scale 1; no area filter, so a scale below 0.5
+ * skips source pixels), 0 outside the level. Without aug_params out_chw = (float) u8 * (1.0f / 255.0f): at scale 1 the bits of
+ * yolo_tile_gather, at other scales those of yolo_tile_gather_scaled, and staging may be NULL. With aug_params the canvas gets the HSV
+ * shift (on the zero padding too, as the reference shifts its padded canvas), is stored to `staging`
+ * (yolo_augment_workspace_bytes(b, tile_h, tile_w); its uint8 rounding between the HSV shift and the warp is part of the
+ * semantics), and the warp / flip / normalise of yolo_augment_images follows. Every crop is augmented, also one of an image
+ * without a label file. out_chw: fp32 (b, 3, tile_h, tile_w). */
+int yolo_crop_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, int n_pool, const int32_t* src_dev,
+                    const double* crop_params, const int32_t* origins_dev, const double* aug_params, int b, int tile_h, int tile_w,
+                    double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows, void* stream);
+int yolo_crop_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
+                     const double* aug_params, int b, int tile_h, int tile_w, void* staging, float* out_chw, void* stream);
+
 /* ---- anchors of a dataset: IoU k-means++ with restarts, and the fitness of an anchor set (csrc/anchors.hip) ---------------- */
 /* wh: n rows (w, h) fp32 on the device, 8-byte aligned, every row with 0 < w, h <= 1 (the caller filters; the Python wrapper does).
  * This comment is the contract: the kernels and the CPU restatement of the tests are both written from it.
