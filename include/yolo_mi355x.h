@@ -468,6 +468,62 @@ int yolo_augment_images(const unsigned char* pool, const int64_t* offsets, const
                         const int32_t* hw, int n_pool, const int32_t* src, const double* params, const int32_t* sel, int b, int out_h,
                         int out_w, void* staging, float* out_chw, void* stream);
 
+/* ---- augmentation extras: rotation, vertical flip, MixUp, Cutout (csrc/augment.h; nothing of the reference, whose transform list
+ * was chosen for ground-level photographs). A second per-row table, float64 [b][YOLO_AUGX_NPARAM], next to the YOLO_AUG_* one; both
+ * users of augment.h take it: the *_ex entry points below and yolo_crop_*_ex. Parity with cv2 / albumentations UNPINNED, as for the
+ * rest of the augmentation. This comment is the contract; the kernels and tests/augx_ref.py are both written from it. Box arithmetic
+ * is fp64 with one rounding per operation (no fused multiply-add), rounded to fp32 at the store; pixel arithmetic is the fixed point
+ * of the warp. Out of scope: the `ellipse` rotate method, shear, perspective.
+ *
+ * chain(r) is row r's output WITHOUT MixUp and Cutout: its own YOLO_AUG_* row, its own mosaic or crop window, and of its own extras
+ * the rotation and the vertical flip. A row that takes no transform at all (an image without a label file in yolo_augment_*:
+ * "letterbox only") takes no rotation and no vertical flip either; MixUp and Cutout work on outputs and apply to every row.
+ *
+ * ROTATION (ROT_COS, ROT_SIN: cos and sin of the angle, formed by the caller in fp64; the kernels evaluate neither). Part of
+ * ShiftScaleRotate, behind its gate YOLO_AUG_DO_SSR. The matrix is getRotationMatrix2D((W/2, H/2), theta, scale):
+ *   alpha = SCALE cos, beta = SCALE sin, cx = 0.5 W, cy = 0.5 H,
+ *   m = [alpha, beta, (1 - alpha) cx - beta cy; -beta, alpha, beta cx + (1 - alpha) cy], then m02 += DX W, m12 += DY H.
+ * With cos = 1, sin = 0 this is the matrix without the extras bit for bit. Pixels: the fixed-point warpAffine of that matrix,
+ * constant border 0 per tap. Boxes (albumentations 1.x bbox_shift_scale_rotate, `largest_box`): the corners (b0, b1), (b2, b1),
+ * (b0, b3), (b2, b3) in pixels (x W, y H) map to ((m00 px + m01 py + m02) / W, (m10 px + m11 py + m12) / H), sums taken left to
+ * right; the box is their min / max envelope t; ta = (t2 W - t0 W)(t3 H - t1 H); c = t clipped to [0, 1], ca alike; kept iff
+ * ca != 0 and ca / ta >= 0.4. A row with exactly cos = 1 and sin = 0 takes the two-corner expressions of the chain without extras.
+ *
+ * VERTICAL FLIP (DO_VFLIP != 0), after the horizontal flip: output row y reads warped row H - 1 - y; boxes y0, y1 = 1 - y1, 1 - y0.
+ *
+ * MIXUP. p = MIX_PARTNER if it is an integer value in [0, b_count) other than the row itself, else none (-1, a non-integer, NaN).
+ * out[b] = chain(b) l + chain(p) m with l = (float) MIX_LAMBDA, m = 1.0f - l, per channel
+ * ((float) pa * (1.0f / 255.0f)) * l + ((float) pb * (1.0f / 255.0f)) * m, every operation rounded once in fp32, no fused
+ * multiply-add. Not transitive: the partner contributes chain(p), whatever its own MIX_PARTNER and rectangles say. Boxes: row b's
+ * kept boxes in their order, then the partner's kept boxes in their order, each set by its own row's rules; kept rows beyond
+ * max_out are not written. A partner without a label file contributes pixels and no boxes.
+ *
+ * CUTOUT, last, on the mixed output. Rectangle k < CUT_N (0 .. 4; values below 1 or NaN are 0, above 4 are 4) covers the pixels
+ * X0 <= x < X1, Y0 <= y < Y1 with X0 = (int)(clip01(x0) W), Y0 = (int)(clip01(y0) H), X1, Y1 alike (clip01(NaN) = 0); these pixels
+ * of the three planes become (float) CUT_FILL. Rectangles are in OUTPUT coordinates: no flip moves them. Boxes: with
+ * R = (X0 / W, Y0 / H, X1 / W, Y1 / H) in fp64 and inter = max(0, min(b2, R2) - max(b0, R0)) max(0, min(b3, R3) - max(b1, R1)),
+ * a box (own or the partner's, after every other step) is dropped iff inter > CUT_COVER ((b2 - b0)(b3 - b1)) for some k: strict,
+ * each rectangle alone. An empty rectangle (X1 <= X0 or Y1 <= Y0) erases nothing and drops nothing. */
+#define YOLO_AUGX_ROT_COS 0
+#define YOLO_AUGX_ROT_SIN 1
+#define YOLO_AUGX_DO_VFLIP 2
+#define YOLO_AUGX_MIX_PARTNER 3
+#define YOLO_AUGX_MIX_LAMBDA 4
+#define YOLO_AUGX_CUT_N 5
+#define YOLO_AUGX_CUT_COVER 6
+#define YOLO_AUGX_CUT_FILL 7
+#define YOLO_AUGX_CUT_RECT 8        /* + 4k .. + 4k + 3 = (x0, y0, x1, y1) of rectangle k < 4, normalised to the output canvas */
+#define YOLO_AUGX_NPARAM 24
+/* yolo_augment_boxes / yolo_augment_images with `extra` (device, [b][YOLO_AUGX_NPARAM]); NULL = exactly the calls above, which
+ * forward here. With extra, max_out should hold a row's boxes plus its partner's. Still one launch over the output for the warp,
+ * blend and erase, no atomics, nothing read back. */
+int yolo_augment_boxes_ex(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, const int32_t* src_dev,
+                          const int32_t* hw, int n_pool, const int32_t* src, const double* params, const double* extra, int b,
+                          int out_h, int out_w, float* out_boxes, int32_t* counts, int max_out, int32_t* sel, void* stream);
+int yolo_augment_images_ex(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, const int32_t* src_dev,
+                           const int32_t* hw, int n_pool, const int32_t* src, const double* params, const double* extra,
+                           const int32_t* sel, int b, int out_h, int out_w, void* staging, float* out_chw, void* stream);
+
 /* ---- evaluation: average precision per class (utils.py:193-274) ----------------------------- */
 /* rows are [image, x, y, w, h, objectness, class] fp32. dets_sorted: class ascending, objectness descending (stable);
  * gts_sorted: class ascending, image ascending (stable); *_class_offsets: [num_classes + 1] row ranges.
@@ -902,6 +958,17 @@ int yolo_crop_boxes(const double* boxes, const int32_t* nbox, int max_in, const 
                     double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows, void* stream);
 int yolo_crop_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
                      const double* aug_params, int b, int tile_h, int tile_w, void* staging, float* out_chw, void* stream);
+/* The same with the augmentation extras ("augmentation extras" above): extra device [b][YOLO_AUGX_NPARAM], NULL = exactly the two
+ * calls above, which forward here; extra without aug_params is YOLO_ERR_ARG. chain(r) is crop r as above plus its rotation and
+ * vertical flip. With extra EVERY crop is stored to `staging`, also one without ShiftScaleRotate: another crop may mix it in, and
+ * which crops are partners is known on the device only. max_out should hold a crop's boxes plus its partner's (2 max_in). */
+int yolo_crop_boxes_ex(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, int n_pool, const int32_t* src_dev,
+                       const double* crop_params, const int32_t* origins_dev, const double* aug_params, const double* extra, int b,
+                       int tile_h, int tile_w, double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows,
+                       void* stream);
+int yolo_crop_images_ex(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
+                        const double* aug_params, const double* extra, int b, int tile_h, int tile_w, void* staging, float* out_chw,
+                        void* stream);
 
 /* ---- anchors of a dataset: IoU k-means++ with restarts, and the fitness of an anchor set (csrc/anchors.hip) ---------------- */
 /* wh: n rows (w, h) fp32 on the device, 8-byte aligned, every row with 0 < w, h <= 1 (the caller filters; the Python wrapper does).

@@ -24,6 +24,8 @@ from .draw import draw_boxes, draw_tracks, plot_image_with_boxes, plot_original
 from .frames import FrameStager, boxes_to_frames, detect_frames, frames_to_rgb, preprocess_frames
 # ... and training on tiles (crops.py): yt.CropPool, yt.crop_params, yt.crop_batch, yt.train_crops
 from .crops import CropPool, crop_batch, crop_params, train_crops
+# ... and the augmentation extras (extras.py): yt.extra_params, the table behind extra= of augment_batch and CropPool.batch
+from .extras import EXTRA_NPARAM, extra_params
 
 __all__ = ["YOLOLoss", "FusedYOLOLoss", "GraphedTrainStep", "SGD", "Adam", "AdamW", "clip_grad_norm_", "GradScaler", "ModelEMA", "CNNBlock", "ResidualBlock", "ScalePredictionBlock", "YOLOv3", "layer_config", "calc_iou",
            "cells_to_boxes", "decode_boxes", "detect", "detect_images", "detect_tiled", "fuse_boxes", "tta_views", "tta_boxes", "detect_tta", "tile_grid", "tile_pyramid", "iou_aligned", "nms_indices", "non_max_suppression", "build_targets", "calc_mAP", "evaluate_detections", "evaluate_model", "accuracy_counts", "check_model_accuracy", "eval_boxes", "get_eval_boxes", "letterbox", "unletterbox_boxes", "augment_params",

@@ -14,6 +14,7 @@ import torch
 from . import _lib as L
 from .boxes import _anchors_to_device
 from .data import AUG_NPARAM, augment_params, build_targets
+from .extras import _extra_table
 from .tiles import _level_hw, _overlap_px, _tile_hw, _tile_origins
 
 __all__ = ["crop_params", "CropPool", "crop_batch", "train_crops"]
@@ -179,7 +180,7 @@ class CropPool:
         return self._staging[key]
 
     def batch(self, B, tile=416, index=None, crop_params=None, params=None, generator=None, origins=None, scale=(1.0, 1.0),
-              background=0.1, min_visibility=0.4, augment=True, out=None):
+              background=0.1, min_visibility=0.4, augment=True, out=None, extra=None):
         """``B`` crops of ``tile`` (t or (th, tw), multiples of 32) from the pool. ``index`` (B,) int32: the image of every crop;
         ``crop_params`` (B, 5): the table of :func:`crop_params`; ``params`` (B, 29): the table of :func:`augment_params`. Tables
         that are omitted are drawn from ``generator`` in this order: ``index`` (``torch.randint``), ``crop_params`` (with ``scale``
@@ -194,7 +195,11 @@ class CropPool:
         pinned staging copy, device tensors (int32 / float64, contiguous) are used in place; there is no host synchronisation and
         nothing is read back, so a device ``index`` is not range-checked here: an entry outside the pool gives an empty crop. With
         every table a device tensor and ``out=`` (the four outputs of an earlier call) the call is capturable in a
-        ``torch.cuda.graph``, and a replay follows the tables' current contents."""
+        ``torch.cuda.graph``, and a replay follows the tables' current contents.
+
+        ``extra`` (B, 24): the table of :func:`extras.extra_params` (rotation, vertical flip, MixUp, Cutout; needs ``augment``). A
+        host table is validated, a device table is used in place; ``M`` is then ``2 * pool.max_boxes``, a crop's boxes followed by
+        its MixUp partner's. ``None``: the call without the extras."""
         th, tw = _tile_hw(tile)
         B = int(B)
         if not 1 <= B <= MAX_CROPS:
@@ -208,6 +213,8 @@ class CropPool:
         n = len(self)
         if not augment and params is not None:
             raise ValueError("params (the augmentation table) was given with augment=False")
+        if not augment and extra is not None:
+            raise ValueError("extra (the augmentation extras) was given with augment=False")
         if index is None:
             index = torch.randint(0, n, (B,), generator=generator)
         index = _table("index", index, (B,), torch.int32)
@@ -222,11 +229,12 @@ class CropPool:
         if augment:
             ap = _table("params", augment_params(B, generator) if params is None else params, (B, AUG_NPARAM), torch.float64)
         org = None if origins is None else _table("origins", origins, (B, 2), torch.int32)
+        ex = None if extra is None else _extra_table(extra, B)
         dev = self.device
-        for name, t in (("index", index), ("crop_params", cp), ("params", ap), ("origins", org)):
+        for name, t in (("index", index), ("crop_params", cp), ("params", ap), ("origins", org), ("extra", ex)):
             if t is not None and t.is_cuda and t.device != dev:
                 raise ValueError(f"{name} is on {t.device}, the pool on {dev}")
-        M = self.max_boxes
+        M = self.max_boxes if ex is None else 2 * self.max_boxes
         shapes = ((B, 3, th, tw), torch.float32), ((B, M, 5), torch.float32), ((B,), torch.int32), ((B, 6), torch.int32)
         if out is not None:
             if not isinstance(out, (tuple, list)) or len(out) != 4:
@@ -235,7 +243,7 @@ class CropPool:
                 if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
                     raise ValueError(f"out: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
         # one pinned staging buffer for the host tables: float64 crop / augmentation rows, then int32 index / origins
-        host_f = [t for t in (cp, ap) if t is not None and not t.is_cuda]
+        host_f = [t for t in (cp, ap, ex) if t is not None and not t.is_cuda]
         host_i = [t for t in (index, org) if t is not None and not t.is_cuda]
         n_f, n_i = sum(t.numel() for t in host_f), sum(t.numel() for t in host_i)
         with torch.cuda.device(dev):
@@ -263,7 +271,7 @@ class CropPool:
                         v = d32[at_i:at_i + t.numel()].view(t.shape)
                         at_i += t.numel()
                     return v
-                cp, ap = placed(cp), placed(ap)
+                cp, ap, ex = placed(cp), placed(ap), placed(ex)
                 index, org = placed(index), placed(org)
             if out is None:
                 out = tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in shapes)
@@ -271,6 +279,14 @@ class CropPool:
             staging = self._workspace(B, th, tw) if ap is not None else None
             stream = L.current_stream()
             lib = L.lib()
+            if ex is not None:
+                L.check(lib.yolo_crop_boxes_ex(self.boxes.data_ptr(), self.nbox.data_ptr(), self.max_boxes, self.hw.data_ptr(), n,
+                                               index.data_ptr(), cp.data_ptr(), L.ptr(org), ap.data_ptr(), ex.data_ptr(), B, th, tw, vis,
+                                               ob.data_ptr(), ct.data_ptr(), M, win.data_ptr(), stream), "yolo_crop_boxes_ex")
+                L.check(lib.yolo_crop_images_ex(self.pool.data_ptr(), self.offsets.data_ptr(), self.hw.data_ptr(), n, win.data_ptr(),
+                                                ap.data_ptr(), ex.data_ptr(), B, th, tw, staging.data_ptr(), x.data_ptr(), stream),
+                        "yolo_crop_images_ex")
+                return x, ob, ct, win
             L.check(lib.yolo_crop_boxes(self.boxes.data_ptr(), self.nbox.data_ptr(), M, self.hw.data_ptr(), n, index.data_ptr(),
                                         cp.data_ptr(), L.ptr(org), L.ptr(ap), B, th, tw, vis, ob.data_ptr(), ct.data_ptr(), M,
                                         win.data_ptr(), stream), "yolo_crop_boxes")

@@ -58,15 +58,13 @@ __device__ __forceinline__ bool cutout_hit(const double o[4], int a, double x, d
     return fmax(0.0, xb - xa) * fmax(0.0, yb - ya) > 0.0;
 }
 
-__global__ void aug_boxes(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in, const int* __restrict__ hw,
-                          const int* __restrict__ src, const double* __restrict__ params, int B, int H, int W, float* __restrict__ out,
-                          int* __restrict__ counts, int max_out, int* __restrict__ sel) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const double* p = params + (size_t)b * YOLO_AUG_NPARAM;
-    const int* s4 = src + 4 * b;
-    float* ob = out + (size_t)b * max_out * 5;
-    int n = 0;
+// The kept boxes of output row s4 = src[r] under its parameter row p, appended to ob at *np (at most max_out rows); returns the path
+// the row takes. EX: the chain runs with the row's extras e and the rectangles of ec, the extras of the row being written.
+template <bool EX>
+__device__ __forceinline__ int row_boxes(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in,
+                                         const int* __restrict__ hw, const int* s4, const double* p, const double* e, const double* ec,
+                                         int H, int W, float* ob, int* np, int max_out) {
+    int n = *np;
     int path = SEL_STANDARD;
     if (nbox[s4[0]] < 0) {
         path = SEL_LETTERBOX;                                                // no label file: letterbox only (dataset.py:162-165)
@@ -108,7 +106,7 @@ __global__ void aug_boxes(const double* __restrict__ boxes, const int* __restric
                     double bb[4];
                     yolo_to_albu(bx + bw / 2, by + bh / 2, bw, bh, bb);      // set_train_transforms(mosaic=True) on S x S
                     if (!area_nz(bb, S, S)) continue;
-                    if (n < max_out && finish_box(bb, in[4], p, S, S, ob + 5 * n)) ++n;
+                    if (n < max_out && finish_box_x<EX>(bb, in[4], p, e, ec, S, S, ob + 5 * n)) ++n;
                 }
             }
         }
@@ -127,9 +125,43 @@ __global__ void aug_boxes(const double* __restrict__ boxes, const int* __restric
             bb[2] = (bb[2] * nw + left) / W;
             bb[1] = (bb[1] * nh + top) / H;
             bb[3] = (bb[3] * nh + top) / H;
-            if (n < max_out && finish_box(bb, in[4], p, H, W, ob + 5 * n)) ++n;
+            if (n < max_out && finish_box_x<EX>(bb, in[4], p, e, ec, H, W, ob + 5 * n)) ++n;
         }
     }
+    *np = n;
+    return path;
+}
+
+__global__ void aug_boxes(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in, const int* __restrict__ hw,
+                          const int* __restrict__ src, const double* __restrict__ params, int B, int H, int W, float* __restrict__ out,
+                          int* __restrict__ counts, int max_out, int* __restrict__ sel) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float* ob = out + (size_t)b * max_out * 5;
+    int n = 0;
+    const int path = row_boxes<false>(boxes, nbox, max_in, hw, src + 4 * b, params + (size_t)b * YOLO_AUG_NPARAM, nullptr, nullptr, H, W,
+                                      ob, &n, max_out);
+    for (int k = 5 * n; k < 5 * max_out; ++k) ob[k] = 0.f;
+    counts[b] = n;
+    sel[b] = path;
+}
+
+// with the extras: the row's own chain, then its MixUp partner's chain appended (each by its own row's rules, both under the
+// rectangles of row b); sel[b] stays the path of row b's own image
+__global__ void aug_boxes_ex(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in, const int* __restrict__ hw,
+                             const int* __restrict__ src, const double* __restrict__ params, const double* __restrict__ extra, int B,
+                             int H, int W, float* __restrict__ out, int* __restrict__ counts, int max_out, int* __restrict__ sel) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float* ob = out + (size_t)b * max_out * 5;
+    const double* e = extra + (size_t)b * YOLO_AUGX_NPARAM;
+    int n = 0;
+    const int path = row_boxes<true>(boxes, nbox, max_in, hw, src + 4 * b, params + (size_t)b * YOLO_AUG_NPARAM, e, e, H, W, ob, &n,
+                                     max_out);
+    const int pt = mix_partner(e, b, B);
+    if (pt >= 0)
+        row_boxes<true>(boxes, nbox, max_in, hw, src + 4 * pt, params + (size_t)pt * YOLO_AUG_NPARAM,
+                        extra + (size_t)pt * YOLO_AUGX_NPARAM, e, H, W, ob, &n, max_out);
     for (int k = 5 * n; k < 5 * max_out; ++k) ob[k] = 0.f;
     counts[b] = n;
     sel[b] = path;
@@ -182,6 +214,18 @@ __global__ __launch_bounds__(256) void aug_warp_normalize(const unsigned char* _
                       out + (size_t)b * 3 * H * W + idx);
 }
 
+// aug_warp_normalize with the extras: chain(b), blended with chain(partner), then erased; still one thread per output pixel
+__global__ __launch_bounds__(256) void aug_warp_normalize_ex(const unsigned char* __restrict__ staging, const double* __restrict__ params,
+                                                             const double* __restrict__ extra, const int* __restrict__ sel, int B, int H,
+                                                             int W, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= H * W) return;
+    const int pt = mix_partner(extra + (size_t)b * YOLO_AUGX_NPARAM, b, B);
+    extras_px(staging, params, extra, b, pt, sel[b] != SEL_LETTERBOX, pt >= 0 && sel[pt] != SEL_LETTERBOX, H, W, idx,
+              out + (size_t)b * 3 * H * W + idx);
+}
+
 // host validation shared by both entry points; on success *S is the resize target (the longer canvas side)
 static int check_tables(const int32_t* hw, int n_pool, const int32_t* src, int B, int H, int W, const char* what) {
     if (!hw || !src || n_pool <= 0 || B <= 0 || H < 32 || W < 32 || H % 32 || W % 32)
@@ -227,21 +271,32 @@ size_t yolo_augment_workspace_bytes(int b, int out_h, int out_w) {
     return ((size_t)b * out_h * out_w * 3 + 255) / 256 * 256;
 }
 
-int yolo_augment_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, const int32_t* src_dev,
-                       const int32_t* hw, int n_pool, const int32_t* src, const double* params, int b, int out_h, int out_w,
-                       float* out_boxes, int32_t* counts, int max_out, int32_t* sel, void* stream) {
+int yolo_augment_boxes_ex(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, const int32_t* src_dev,
+                          const int32_t* hw, int n_pool, const int32_t* src, const double* params, const double* extra, int b,
+                          int out_h, int out_w, float* out_boxes, int32_t* counts, int max_out, int32_t* sel, void* stream) {
     if (!boxes || !nbox || !hw_dev || !src_dev || !params || !out_boxes || !counts || !sel || max_in <= 0 || max_out <= 0)
         return fail(YOLO_ERR_ARG, "augment_boxes: bad arguments");
     const int rc = check_tables(hw, n_pool, src, b, out_h, out_w, "augment_boxes");
     if (rc != YOLO_OK) return rc;
-    hipLaunchKernelGGL(aug_boxes, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, src_dev, params, b,
-                       out_h, out_w, out_boxes, counts, max_out, sel);
+    if (extra)
+        hipLaunchKernelGGL(aug_boxes_ex, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, src_dev,
+                           params, extra, b, out_h, out_w, out_boxes, counts, max_out, sel);
+    else
+        hipLaunchKernelGGL(aug_boxes, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, src_dev,
+                           params, b, out_h, out_w, out_boxes, counts, max_out, sel);
     return check_launch("augment_boxes");
 }
 
-int yolo_augment_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, const int32_t* src_dev,
-                        const int32_t* hw, int n_pool, const int32_t* src, const double* params, const int32_t* sel, int b, int out_h,
-                        int out_w, void* staging, float* out_chw, void* stream) {
+int yolo_augment_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, const int32_t* src_dev,
+                       const int32_t* hw, int n_pool, const int32_t* src, const double* params, int b, int out_h, int out_w,
+                       float* out_boxes, int32_t* counts, int max_out, int32_t* sel, void* stream) {
+    return yolo_augment_boxes_ex(boxes, nbox, max_in, hw_dev, src_dev, hw, n_pool, src, params, nullptr, b, out_h, out_w, out_boxes,
+                                 counts, max_out, sel, stream);
+}
+
+int yolo_augment_images_ex(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, const int32_t* src_dev,
+                           const int32_t* hw, int n_pool, const int32_t* src, const double* params, const double* extra,
+                           const int32_t* sel, int b, int out_h, int out_w, void* staging, float* out_chw, void* stream) {
     if (!pool || !offsets || !hw_dev || !src_dev || !params || !sel || !staging || !out_chw)
         return fail(YOLO_ERR_ARG, "augment_images: bad arguments");
     const int rc = check_tables(hw, n_pool, src, b, out_h, out_w, "augment_images");
@@ -252,8 +307,19 @@ int yolo_augment_images(const unsigned char* pool, const int64_t* offsets, const
                        (unsigned char*)staging);
     int e = check_launch("augment_images (canvas)");
     if (e != YOLO_OK) return e;
-    hipLaunchKernelGGL(aug_warp_normalize, grid, dim3(256), 0, s, (const unsigned char*)staging, params, sel, out_h, out_w, out_chw);
+    if (extra)
+        hipLaunchKernelGGL(aug_warp_normalize_ex, grid, dim3(256), 0, s, (const unsigned char*)staging, params, extra, sel, b, out_h,
+                           out_w, out_chw);
+    else
+        hipLaunchKernelGGL(aug_warp_normalize, grid, dim3(256), 0, s, (const unsigned char*)staging, params, sel, out_h, out_w, out_chw);
     return check_launch("augment_images (warp)");
+}
+
+int yolo_augment_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, const int32_t* src_dev,
+                        const int32_t* hw, int n_pool, const int32_t* src, const double* params, const int32_t* sel, int b, int out_h,
+                        int out_w, void* staging, float* out_chw, void* stream) {
+    return yolo_augment_images_ex(pool, offsets, hw_dev, src_dev, hw, n_pool, src, params, nullptr, sel, b, out_h, out_w, staging,
+                                  out_chw, stream);
 }
 
 }  // extern "C"

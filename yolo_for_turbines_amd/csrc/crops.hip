@@ -11,6 +11,9 @@
 //                       augment.hip, a crop without it is flipped, normalised and written straight to the output (the warp would
 //                       only copy its canvas pixel: the same bits without the staging round trip);
 //   crop_warp_normalize the warp / flip / normalise of augment.h on the staged crops.
+// With the augmentation extras (rotation, vertical flip, MixUp, Cutout: yolo_crop_*_ex) crop_boxes_ex appends the partner's boxes,
+// crop_tile<true, true> stages EVERY crop (a crop without ShiftScaleRotate may be another crop's MixUp partner, and which crops are
+// partners is known on the device only) and crop_warp_normalize_ex warps, blends and erases in one launch.
 // A level pixel is resize_px of resample.h (the library's one INTER_LINEAR; the identity at scale 1), so without augmentation the
 // output has the bits of yolo_tile_gather / yolo_tile_gather_scaled. PARITY UNPINNED, like augment.hip.
 // Built with -ffp-contract=off: the window and box arithmetic is fp64 with every operation rounded once.
@@ -38,6 +41,63 @@ __device__ __forceinline__ int window_origin(int L, int t, double j, bool object
     return (int)fmin(fmax(v, 0.0), (double)(L - t));         // NaN -> 0
 }
 
+// Crop r: its windows row (written to win unless NULL) and its kept boxes, appended to ob at *np (at most max_out rows). EX: the box
+// chain runs with the crop's extras e and the rectangles of ec, the extras of the crop being written.
+template <bool EX>
+__device__ __forceinline__ void crop_row_boxes(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in,
+                                               const int* __restrict__ hw, int n_pool, const int* __restrict__ src,
+                                               const double* __restrict__ crop_params, const int* __restrict__ origins,
+                                               const double* __restrict__ aug_params, const double* e, const double* ec, int r, int th,
+                                               int tw, double min_vis, float* ob, int* np, int max_out, int* win) {
+    const int k = src[r];
+    int n = *np;
+    if ((unsigned)k >= (unsigned)n_pool) {                   // an index outside the pool: an empty crop, nothing is read
+        if (win) { win[0] = -1; win[1] = win[2] = 0; win[3] = win[4] = 1; win[5] = -1; }
+        return;
+    }
+    const double* cp = crop_params + (size_t)r * YOLO_CROP_NPARAM;
+    const int h = hw[2 * k], w = hw[2 * k + 1], nb = min(nbox[k], max_in);
+    double scale = cp[YOLO_CROP_SCALE];
+    if (!(scale > 0.0 && scale <= 8.0)) scale = 1.0;
+    const int LH = level_side(h, scale), LW = level_side(w, scale);
+    int picked = -1, y0, x0;
+    if (origins) {
+        y0 = origins[2 * r]; x0 = origins[2 * r + 1];
+    } else {
+        double cx = 0.0, cy = 0.0;
+        if (cp[YOLO_CROP_BACKGROUND] == 0.0 && nb > 0) {
+            const double u = floor(cp[YOLO_CROP_U_PICK] * nb);
+            picked = (int)fmin(fmax(u, 0.0), (double)(nb - 1));
+            const double* in = boxes + ((size_t)k * max_in + picked) * 5;
+            cx = in[0]; cy = in[1];
+        }
+        x0 = window_origin(LW, tw, cp[YOLO_CROP_JX], picked >= 0, cx);
+        y0 = window_origin(LH, th, cp[YOLO_CROP_JY], picked >= 0, cy);
+    }
+    if (win) { win[0] = k; win[1] = y0; win[2] = x0; win[3] = LH; win[4] = LW; win[5] = picked; }
+    const double* ap = aug_params ? aug_params + (size_t)r * YOLO_AUG_NPARAM : nullptr;
+    for (int i = 0; i < nb && i < max_in; ++i) {
+        const double* in = boxes + ((size_t)k * max_in + i) * 5;
+        double bb[4];
+        yolo_to_albu(in[0], in[1], in[2], in[3], bb);
+        if (!area_nz(bb, h, w)) continue;
+        const double t[4] = {(bb[0] * LW - x0) / tw, (bb[1] * LH - y0) / th, (bb[2] * LW - x0) / tw, (bb[3] * LH - y0) / th};
+        const double ta = (t[2] * tw - t[0] * tw) * (t[3] * th - t[1] * th);
+        double c[4];
+        for (int q = 0; q < 4; ++q) c[q] = clip01(t[q]);
+        const double ca = (c[2] * tw - c[0] * tw) * (c[3] * th - c[1] * th);
+        if (!(ca != 0.0 && ca / ta >= min_vis)) continue;
+        if (n >= max_out) continue;
+        if (ap) {
+            if (finish_box_x<EX>(c, in[4], ap, e, ec, th, tw, ob + 5 * n)) ++n;
+        } else {
+            store_box(c, in[4], ob + 5 * n);
+            ++n;
+        }
+    }
+    *np = n;
+}
+
 __global__ void crop_boxes(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in, const int* __restrict__ hw,
                            int n_pool, const int* __restrict__ src, const double* __restrict__ crop_params,
                            const int* __restrict__ origins, const double* __restrict__ aug_params, int B, int th, int tw,
@@ -45,53 +105,31 @@ __global__ void crop_boxes(const double* __restrict__ boxes, const int* __restri
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float* ob = out + (size_t)b * max_out * 5;
-    int* win = windows + (size_t)b * kCropWin;
-    const int k = src[b];
     int n = 0;
-    if ((unsigned)k >= (unsigned)n_pool) {                   // an index outside the pool: an empty crop, nothing is read
-        win[0] = -1; win[1] = win[2] = 0; win[3] = win[4] = 1; win[5] = -1;
-    } else {
-        const double* cp = crop_params + (size_t)b * YOLO_CROP_NPARAM;
-        const int h = hw[2 * k], w = hw[2 * k + 1], nb = min(nbox[k], max_in);
-        double scale = cp[YOLO_CROP_SCALE];
-        if (!(scale > 0.0 && scale <= 8.0)) scale = 1.0;
-        const int LH = level_side(h, scale), LW = level_side(w, scale);
-        int picked = -1, y0, x0;
-        if (origins) {
-            y0 = origins[2 * b]; x0 = origins[2 * b + 1];
-        } else {
-            double cx = 0.0, cy = 0.0;
-            if (cp[YOLO_CROP_BACKGROUND] == 0.0 && nb > 0) {
-                const double u = floor(cp[YOLO_CROP_U_PICK] * nb);
-                picked = (int)fmin(fmax(u, 0.0), (double)(nb - 1));
-                const double* in = boxes + ((size_t)k * max_in + picked) * 5;
-                cx = in[0]; cy = in[1];
-            }
-            x0 = window_origin(LW, tw, cp[YOLO_CROP_JX], picked >= 0, cx);
-            y0 = window_origin(LH, th, cp[YOLO_CROP_JY], picked >= 0, cy);
-        }
-        win[0] = k; win[1] = y0; win[2] = x0; win[3] = LH; win[4] = LW; win[5] = picked;
-        const double* ap = aug_params ? aug_params + (size_t)b * YOLO_AUG_NPARAM : nullptr;
-        for (int i = 0; i < nb && i < max_in; ++i) {
-            const double* in = boxes + ((size_t)k * max_in + i) * 5;
-            double bb[4];
-            yolo_to_albu(in[0], in[1], in[2], in[3], bb);
-            if (!area_nz(bb, h, w)) continue;
-            const double t[4] = {(bb[0] * LW - x0) / tw, (bb[1] * LH - y0) / th, (bb[2] * LW - x0) / tw, (bb[3] * LH - y0) / th};
-            const double ta = (t[2] * tw - t[0] * tw) * (t[3] * th - t[1] * th);
-            double c[4];
-            for (int q = 0; q < 4; ++q) c[q] = clip01(t[q]);
-            const double ca = (c[2] * tw - c[0] * tw) * (c[3] * th - c[1] * th);
-            if (!(ca != 0.0 && ca / ta >= min_vis)) continue;
-            if (n >= max_out) continue;
-            if (ap) {
-                if (finish_box(c, in[4], ap, th, tw, ob + 5 * n)) ++n;
-            } else {
-                store_box(c, in[4], ob + 5 * n);
-                ++n;
-            }
-        }
-    }
+    crop_row_boxes<false>(boxes, nbox, max_in, hw, n_pool, src, crop_params, origins, aug_params, nullptr, nullptr, b, th, tw, min_vis, ob,
+                          &n, max_out, windows + (size_t)b * kCropWin);
+    for (int q = 5 * n; q < 5 * max_out; ++q) ob[q] = 0.f;
+    counts[b] = n;
+}
+
+// with the extras (aug_params is not NULL): the crop's own boxes, then those of its MixUp partner's crop appended, each by its own
+// row's rules and both under the rectangles of crop b
+__global__ void crop_boxes_ex(const double* __restrict__ boxes, const int* __restrict__ nbox, int max_in, const int* __restrict__ hw,
+                              int n_pool, const int* __restrict__ src, const double* __restrict__ crop_params,
+                              const int* __restrict__ origins, const double* __restrict__ aug_params, const double* __restrict__ extra,
+                              int B, int th, int tw, double min_vis, float* __restrict__ out, int* __restrict__ counts, int max_out,
+                              int* __restrict__ windows) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float* ob = out + (size_t)b * max_out * 5;
+    const double* e = extra + (size_t)b * YOLO_AUGX_NPARAM;
+    int n = 0;
+    crop_row_boxes<true>(boxes, nbox, max_in, hw, n_pool, src, crop_params, origins, aug_params, e, e, b, th, tw, min_vis, ob, &n, max_out,
+                         windows + (size_t)b * kCropWin);
+    const int pt = mix_partner(e, b, B);
+    if (pt >= 0)
+        crop_row_boxes<true>(boxes, nbox, max_in, hw, n_pool, src, crop_params, origins, aug_params, extra + (size_t)pt * YOLO_AUGX_NPARAM,
+                             e, pt, th, tw, min_vis, ob, &n, max_out, nullptr);
     for (int q = 5 * n; q < 5 * max_out; ++q) ob[q] = 0.f;
     counts[b] = n;
 }
@@ -101,7 +139,8 @@ __global__ void crop_boxes(const double* __restrict__ boxes, const int* __restri
 // scale 1, and a wave writes four 256-byte fp32 row segments per plane (or four 192-byte segments of the staging canvas).
 // al4: the pool's first byte is 4-byte aligned, so a lane's 12 source bytes may come from the dwords around them.
 // vec: bit 0 the staging canvas takes dword stores, bit 1 the output takes 16-byte stores.
-template <bool AUG>
+// ALL: every crop is stored to the staging canvas, also one without ShiftScaleRotate (the extras: another crop may mix it in).
+template <bool AUG, bool ALL = false>
 __global__ __launch_bounds__(kCropThreads) void crop_tile_kernel(const unsigned char* __restrict__ pool, const long long* __restrict__ offsets,
                                                                   const int* __restrict__ hw, int n_pool, const int* __restrict__ windows,
                                                                   const double* __restrict__ aug_params, int th, int tw, int tiles_x,
@@ -195,7 +234,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_tile_kernel(const unsigned 
             const double hue = p[YOLO_AUG_HUE], sat = p[YOLO_AUG_SAT], val = p[YOLO_AUG_VAL];
             for (int e = 0; e < 4; ++e) hsv_shift(px[e], hue, sat, val);
         }
-        if (p[YOLO_AUG_DO_SSR] == 0.0) {
+        if (!ALL && p[YOLO_AUG_DO_SSR] == 0.0) {
             // no warp for this crop: warp_normalize_px would copy the canvas pixel, so flip and normalise here and skip the
             // staging round trip (crop_warp_normalize leaves such a crop alone)
             const bool flip = p[YOLO_AUG_DO_FLIP] != 0.0;
@@ -244,6 +283,17 @@ __global__ __launch_bounds__(256) void crop_warp_normalize(const unsigned char* 
                       out + (size_t)b * 3 * H * W + idx);
 }
 
+// aug_warp_normalize_ex of augment.hip on the crops, all of them staged: chain(b), blended with chain(partner), then erased
+__global__ __launch_bounds__(256) void crop_warp_normalize_ex(const unsigned char* __restrict__ staging, const double* __restrict__ params,
+                                                              const double* __restrict__ extra, int B, int H, int W,
+                                                              float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= H * W) return;
+    const int pt = mix_partner(extra + (size_t)b * YOLO_AUGX_NPARAM, b, B);
+    extras_px(staging, params, extra, b, pt, true, true, H, W, idx, out + (size_t)b * 3 * H * W + idx);
+}
+
 static int crop_args(const char* what, int n_pool, int b, int th, int tw) {
     if (n_pool <= 0 || b <= 0 || b > 65535) return fail(YOLO_ERR_ARG, "%s: bad arguments (n_pool %d, b %d: 1 .. 65535 crops)", what, n_pool, b);
     if (th < 32 || tw < 32 || th % 32 || tw % 32 || (long long)th * tw > 0x7fffffffll / 3)
@@ -257,23 +307,40 @@ using namespace yolo;
 
 extern "C" {
 
-int yolo_crop_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, int n_pool, const int32_t* src_dev,
-                    const double* crop_params, const int32_t* origins_dev, const double* aug_params, int b, int tile_h, int tile_w,
-                    double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows, void* stream) {
+int yolo_crop_boxes_ex(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, int n_pool, const int32_t* src_dev,
+                       const double* crop_params, const int32_t* origins_dev, const double* aug_params, const double* extra, int b,
+                       int tile_h, int tile_w, double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows,
+                       void* stream) {
     if (!boxes || !nbox || !hw_dev || !src_dev || !crop_params || !out_boxes || !counts || !windows || max_in <= 0 || max_out <= 0)
         return fail(YOLO_ERR_ARG, "crop_boxes: bad arguments");
+    if (extra && !aug_params) return fail(YOLO_ERR_ARG, "crop_boxes: extra (the augmentation extras) needs aug_params");
     if (int rc = crop_args("crop_boxes", n_pool, b, tile_h, tile_w)) return rc;
     if (!(min_visibility >= 0.0 && min_visibility <= 1.0))   // NaN too
         return fail(YOLO_ERR_ARG, "crop_boxes: min_visibility %g is not in [0, 1]", min_visibility);
-    hipLaunchKernelGGL(crop_boxes, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, n_pool, src_dev,
-                       crop_params, origins_dev, aug_params, b, tile_h, tile_w, min_visibility, out_boxes, counts, max_out, windows);
+    if (extra)
+        hipLaunchKernelGGL(crop_boxes_ex, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, n_pool,
+                           src_dev, crop_params, origins_dev, aug_params, extra, b, tile_h, tile_w, min_visibility, out_boxes, counts,
+                           max_out, windows);
+    else
+        hipLaunchKernelGGL(crop_boxes, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, boxes, nbox, max_in, hw_dev, n_pool,
+                           src_dev, crop_params, origins_dev, aug_params, b, tile_h, tile_w, min_visibility, out_boxes, counts, max_out,
+                           windows);
     return check_launch("crop_boxes");
 }
 
-int yolo_crop_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
-                     const double* aug_params, int b, int tile_h, int tile_w, void* staging, float* out_chw, void* stream) {
+int yolo_crop_boxes(const double* boxes, const int32_t* nbox, int max_in, const int32_t* hw_dev, int n_pool, const int32_t* src_dev,
+                    const double* crop_params, const int32_t* origins_dev, const double* aug_params, int b, int tile_h, int tile_w,
+                    double min_visibility, float* out_boxes, int32_t* counts, int max_out, int32_t* windows, void* stream) {
+    return yolo_crop_boxes_ex(boxes, nbox, max_in, hw_dev, n_pool, src_dev, crop_params, origins_dev, aug_params, nullptr, b, tile_h,
+                              tile_w, min_visibility, out_boxes, counts, max_out, windows, stream);
+}
+
+int yolo_crop_images_ex(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
+                        const double* aug_params, const double* extra, int b, int tile_h, int tile_w, void* staging, float* out_chw,
+                        void* stream) {
     if (!pool || !offsets || !hw_dev || !windows || !out_chw || (aug_params && !staging))
         return fail(YOLO_ERR_ARG, "crop_images: bad arguments");
+    if (extra && !aug_params) return fail(YOLO_ERR_ARG, "crop_images: extra (the augmentation extras) needs aug_params");
     if (int rc = crop_args("crop_images", n_pool, b, tile_h, tile_w)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int tiles_x = ceil_div(tile_w, kCropTileW);
@@ -285,13 +352,28 @@ int yolo_crop_images(const unsigned char* pool, const int64_t* offsets, const in
                            tile_h, tile_w, tiles_x, al4, vec_out, (unsigned char*)nullptr, out_chw);
         return check_launch("crop_images");
     }
+    const int vec = vec_out | (int)(((uintptr_t)staging & 3) == 0);
+    const dim3 wgrid(ceil_div(tile_h * tile_w, 256), b);
+    if (extra) {
+        hipLaunchKernelGGL((crop_tile_kernel<true, true>), grid, block, 0, s, pool, (const long long*)offsets, hw_dev, n_pool, windows,
+                           aug_params, tile_h, tile_w, tiles_x, al4, vec, (unsigned char*)staging, out_chw);
+        int e = check_launch("crop_images (canvas)");
+        if (e != YOLO_OK) return e;
+        hipLaunchKernelGGL(crop_warp_normalize_ex, wgrid, dim3(256), 0, s, (const unsigned char*)staging, aug_params, extra, b, tile_h,
+                           tile_w, out_chw);
+        return check_launch("crop_images (warp)");
+    }
     hipLaunchKernelGGL(crop_tile_kernel<true>, grid, block, 0, s, pool, (const long long*)offsets, hw_dev, n_pool, windows, aug_params, tile_h,
-                       tile_w, tiles_x, al4, vec_out | (int)(((uintptr_t)staging & 3) == 0), (unsigned char*)staging, out_chw);
+                       tile_w, tiles_x, al4, vec, (unsigned char*)staging, out_chw);
     int e = check_launch("crop_images (canvas)");
     if (e != YOLO_OK) return e;
-    hipLaunchKernelGGL(crop_warp_normalize, dim3(ceil_div(tile_h * tile_w, 256), b), dim3(256), 0, s, (const unsigned char*)staging,
-                       aug_params, tile_h, tile_w, out_chw);
+    hipLaunchKernelGGL(crop_warp_normalize, wgrid, dim3(256), 0, s, (const unsigned char*)staging, aug_params, tile_h, tile_w, out_chw);
     return check_launch("crop_images (warp)");
+}
+
+int yolo_crop_images(const unsigned char* pool, const int64_t* offsets, const int32_t* hw_dev, int n_pool, const int32_t* windows,
+                     const double* aug_params, int b, int tile_h, int tile_w, void* staging, float* out_chw, void* stream) {
+    return yolo_crop_images_ex(pool, offsets, hw_dev, n_pool, windows, aug_params, nullptr, b, tile_h, tile_w, staging, out_chw, stream);
 }
 
 }  // extern "C"

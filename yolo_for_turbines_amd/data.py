@@ -132,7 +132,7 @@ def _resized_hw(h, w, size):
     return max(nh, 1), max(nw, 1)
 
 
-def augment_batch(images, boxes, image_size=416, params=None, generator=None, mosaic=None, device=None):
+def augment_batch(images, boxes, image_size=416, params=None, generator=None, mosaic=None, device=None, extra=None):
     """``YOLODataset.apply_augmentations`` (dataset.py:75-111) for a whole batch on the device, with no host synchronisation.
 
     ``images``: list of uint8 (H, W, 3) tensors or arrays (CPU: staged with one pinned copy; or already on the device).
@@ -143,13 +143,15 @@ def augment_batch(images, boxes, image_size=416, params=None, generator=None, mo
     ``[i, -1, -1, -1]`` is the standard transform of image i. ``params``: the (B, 29) table of :func:`augment_params`
     (drawn from ``generator`` when omitted). Returns ``(x (B, 3, H, W) fp32, boxes (B, M, 5) fp32, counts (B,) int32)``, all
     on the device: the padded box table is the input of :func:`build_targets`. Parity with cv2 / albumentations is unpinned
-    (see csrc/augment.hip)."""
-    x, out_boxes, counts, launch = _augment_prepare(images, boxes, image_size, params, generator, mosaic, device)
+    (see csrc/augment.hip). ``extra``: the (B, 24) table of :func:`extras.extra_params` (rotation, vertical flip, MixUp, Cutout);
+    ``M`` then holds a row's boxes plus its MixUp partner's (the exact sum for a host table, twice the largest row for a device
+    table, which is used in place and not read). ``None``: the call without the extras."""
+    x, out_boxes, counts, launch = _augment_prepare(images, boxes, image_size, params, generator, mosaic, device, extra)
     launch()
     return x, out_boxes, counts
 
 
-def _augment_prepare(images, boxes, image_size, params, generator, mosaic, device):
+def _augment_prepare(images, boxes, image_size, params, generator, mosaic, device, extra=None):
     """augment_batch up to the launches: validated tables uploaded, outputs allocated; ``launch()`` enqueues the kernels
     (tools/augment_bench.py times it alone)."""
     dev = torch.device("cuda" if device is None else device)
@@ -192,11 +194,25 @@ def _augment_prepare(images, boxes, image_size, params, generator, mosaic, devic
     # host tables: box rows per pool image (None -> -1), the pool layout, the source slots
     nbox = [-1 if b is None else len(b) for b in boxes]
     max_in = max([1] + nbox)
-    max_out = max(1, max(sum(max(nbox[k], 0) for k in r if k >= 0) for r in src))
+    own = [sum(max(nbox[k], 0) for k in r if k >= 0) for r in src]
+    max_out = max(1, max(own))
+    ex_host = False
+    if extra is not None:
+        from .extras import EXTRA_NPARAM, _extra_table, _host_partners
+        extra = _extra_table(extra, B)
+        ex_host = not extra.is_cuda
+        on = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        if extra.is_cuda and extra.device != on:             # used in place: the kernels would read another device's memory
+            raise ValueError(f"extra is on {extra.device}, the batch on {on}")
+        if ex_host:
+            max_out = max(1, max(o + (own[q] if q >= 0 else 0) for o, q in zip(own, _host_partners(extra, B))))
+        else:
+            max_out = 2 * max_out
+    n_ex = B * EXTRA_NPARAM if ex_host else 0
     hw_l = [int(v) for t in ts for v in t.shape[:2]]
     src_l = [k for r in src for k in r]
     # one pinned staging buffer for every small table: float64 params + boxes, then int64 offsets, then int32 hw / src / nbox
-    n_f = (0 if params.device.type == "cuda" else B * AUG_NPARAM) + n * max_in * 5
+    n_f = (0 if params.device.type == "cuda" else B * AUG_NPARAM) + n * max_in * 5 + n_ex
     n_i = n + (2 * n + 4 * B + n + 1) // 2
     host = torch.empty(n_f + n_i, dtype=torch.float64, pin_memory=True)
     hf = host[:n_f]
@@ -204,11 +220,13 @@ def _augment_prepare(images, boxes, image_size, params, generator, mosaic, devic
     if params.device.type != "cuda":
         hf[:B * AUG_NPARAM] = params.to(torch.float64).reshape(-1)
         off_p = B * AUG_NPARAM
-    bx = hf[off_p:].view(n, max_in, 5)
+    bx = hf[off_p:off_p + n * max_in * 5].view(n, max_in, 5)
     bx.zero_()
     for i, bl in enumerate(boxes):
         if bl is not None and len(bl):
             bx[i, :len(bl)] = torch.as_tensor(bl, dtype=torch.float64).reshape(-1, 5)
+    if ex_host:
+        hf[n_f - n_ex:] = extra.reshape(-1)
     hi = host[n_f:].view(torch.int64)
     cpu = [i for i, t in enumerate(ts) if t.device.type != "cuda"]
     offs, o = [0] * n, 0
@@ -235,7 +253,8 @@ def _augment_prepare(images, boxes, image_size, params, generator, mosaic, devic
                 pool[offs[i]:offs[i] + ts[i].numel()].copy_(ts[i].to(dev).reshape(-1))
                 ts[i].record_stream(torch.cuda.current_stream())
         dp = params.to(dev, torch.float64).contiguous() if params.device.type == "cuda" else dtab[:B * AUG_NPARAM]
-        dbox = dtab[off_p:n_f]
+        dbox = dtab[off_p:n_f - n_ex]
+        dex = None if extra is None else (dtab[n_f - n_ex:n_f] if ex_host else extra)
         di = dtab[n_f:].view(torch.int64)
         d32 = di[n:].view(torch.int32)
         dhw, dsrc, dnbox = d32[:2 * n], d32[2 * n:2 * n + 4 * B], d32[2 * n + 4 * B:3 * n + 4 * B]
@@ -250,6 +269,14 @@ def _augment_prepare(images, boxes, image_size, params, generator, mosaic, devic
     def launch():
         with torch.cuda.device(dev):
             stream = L.current_stream()
+        if dex is not None:
+            L.check(L.lib().yolo_augment_boxes_ex(dbox.data_ptr(), dnbox.data_ptr(), max_in, dhw.data_ptr(), dsrc.data_ptr(), hw_c, n,
+                                                  src_c, dp.data_ptr(), dex.data_ptr(), B, H, W, out_boxes.data_ptr(), counts.data_ptr(),
+                                                  max_out, sel.data_ptr(), stream), "yolo_augment_boxes_ex")
+            L.check(L.lib().yolo_augment_images_ex(pool.data_ptr(), di.data_ptr(), dhw.data_ptr(), dsrc.data_ptr(), hw_c, n, src_c,
+                                                   dp.data_ptr(), dex.data_ptr(), sel.data_ptr(), B, H, W, staging.data_ptr(),
+                                                   x.data_ptr(), stream), "yolo_augment_images_ex")
+            return
         L.check(L.lib().yolo_augment_boxes(dbox.data_ptr(), dnbox.data_ptr(), max_in, dhw.data_ptr(), dsrc.data_ptr(), hw_c, n, src_c,
                                            dp.data_ptr(), B, H, W, out_boxes.data_ptr(), counts.data_ptr(), max_out, sel.data_ptr(),
                                            stream), "yolo_augment_boxes")
