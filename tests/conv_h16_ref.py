@@ -216,6 +216,9 @@ def _ints(shape, g, xmax=8):
     return torch.where(v >= 0, v + 1, v).float()            # +-{1..xmax}
 
 
+ints = _ints                                                 # (the name other case modules use)
+
+
 def operands(c, dtype, gauss=False):
     """The data of a case, seeded from it: x / w / scale / shift / residual as the launch gets them (x and residual whole
     buffers of their ld, rounded to the dtype; w fp32 OIHW holding values the dtype represents exactly)."""

@@ -51,11 +51,11 @@ import pytest
 import torch
 
 from tests import conv_f32_cases as K
+from tests.conv_f32_launch import GUARD, SENT
+from tests.conv_f32_launch import bits as _bits, same_bits as _same_bits, sentinel_buffer as _sentinel_buffer, values as _values, y_shape as _y_shape
 
 pytestmark = pytest.mark.gpu
 
-SENT = -12288.0
-GUARD = 256
 WORST = {"A": 0.0, "B": 0.0, "E": 0.0}
 
 
@@ -65,33 +65,6 @@ def L():
     _lib.lib()                        # must load: no fallback
     assert torch.cuda.is_available()
     return _lib
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _sentinel_buffer(shape):
-    """(raw bytes, fp32 view of `shape`): the view filled with the sentinel, 256 guard bytes of 0xA5 behind it."""
-    n = 1
-    for s in shape:
-        n *= s
-    raw = torch.full((4 * n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    view = raw[:4 * n].view(torch.float32).view(shape)
-    view.fill_(SENT)
-    return raw, view
-
-
-def _y_shape(c):
-    ho, wo = K.out_hw(c)
-    if c["out"] == K.OUT_HEAD:
-        return (c["n"], 3, ho, wo, c["cout"] // 3)
-    f = 2 if c["out"] == K.OUT_UP else 1
-    return (c["n"], f * ho, f * wo, c["y_ld"])
 
 
 class Dev:
@@ -153,23 +126,6 @@ def _launch(L, dev, tile, flags=None, ws=False):
         assert bool((wsb[need:] == 0xA5).all()), (c["name"], tile, "wrote past the stated workspace")
     assert dev.inputs_unchanged(), (c["name"], tile, "an input changed")
     return _values(c, y.cpu(), tile), int(flag.item())
-
-
-def _values(c, y, tile=None):
-    """(n, ho, wo, cout) of an output buffer; everything outside the layer's channels must still be the sentinel, the four pixels of
-    a 2x upsampling store equal."""
-    if c["out"] == K.OUT_HEAD:
-        n, _, ho, wo, nc5 = y.shape
-        return y.permute(0, 2, 3, 1, 4).reshape(n, ho, wo, 3 * nc5)
-    keep = torch.ones(y.shape[-1], dtype=torch.bool)
-    keep[c["y_off"]:c["y_off"] + c["cout"]] = False
-    assert bool((y[..., keep] == SENT).all()), (c["name"], tile, "channels outside [y_off, y_off + cout) were written")
-    v = y[..., c["y_off"]:c["y_off"] + c["cout"]]
-    if c["out"] == K.OUT_UP:
-        a = v[:, ::2, ::2]
-        assert _same_bits(a, v[:, 1::2, ::2]) and _same_bits(a, v[:, ::2, 1::2]) and _same_bits(a, v[:, 1::2, 1::2]), (c["name"], tile)
-        v = a
-    return v.contiguous()
 
 
 def _ratio(name, got):
